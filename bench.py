@@ -10,6 +10,7 @@ seeded geometric-init weights, seeded CLIP weights / text embeddings, procedural
 drawn with the reference's sampling code.
 
 Prints ONE JSON line (rank 0).  value = whole-job rays/s (all ranks), weak scaling (one view per GPU per step).
+--dump-outputs DIR also writes what the last timed step computed as DIR/<name>.npy (see dump_outputs).
 """
 import argparse
 import json
@@ -274,6 +275,25 @@ def timed_steps(runner, steps, warmup, dev, sync_debug=False):
     return dt, per_kernel
 
 
+def dump_outputs(runner, out_dir):
+    """--dump-outputs DIR: what the timed path computed in its LAST step, as a caller of Runner.train_clip_iteration holds it afterwards --
+    the returned loss and the step's loss terms (Runner.last_stats, float64), the trained parameters after the Adam update and the gradient
+    that update used (float32, flattened in Runner.params_to_train order: SDF net, variance, colour net; 2 x 1.6 MB for the full nets).
+    The run is seeded (train.seed = 0), so the same arguments give the same inputs.  Returns the file names written."""
+    os.makedirs(out_dir, exist_ok=True)
+    st = runner.last_stats
+    arrays = {}
+    for name, key in (("loss", "loss"), ("color_loss", "color"), ("eikonal_loss", "eikonal"), ("cosine", "cosine"), ("s_val", "s_val"), ("psnr", "psnr")):
+        if st.get(key) is not None:
+            arrays[name] = np.asarray([float(st[key])], dtype=np.float64)
+    ps = runner.params_to_train
+    arrays["params"] = torch.cat([p.detach().reshape(-1).float() for p in ps]).cpu().numpy()
+    arrays["grads"] = torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).detach().reshape(-1).float() for p in ps]).cpu().numpy()
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return sorted(name + ".npy" for name in arrays)
+
+
 def kernel_rooflines(per_kernel, steps):
     """per MLP kernel: frac = algorithmic FLOPs / kernel time / dense MFMA peak, with the HBM view beside it.  One
     "launch" below = the kernel's launches of ONE step taken together (the backward pair runs once per slab of the view)."""
@@ -318,13 +338,16 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extra", action="store_true", help="skip the extra_configs legs (BASELINE configs 2 and 3-per-GPU)")
     ap.add_argument("--sync-debug", action="store_true", help="development aid: warn (with a stack) on every host-device synchronisation inside the timed steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed (loss terms, parameters, gradients) as DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` on its own: start the N ranks here (one process per GPU, RCCL over xGMI), exactly the way
         # the driver would (`python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...`)
-        have = torch.cuda.device_count()
-        if have < args.gpus and not os.environ.get("AVC_SINGLE_DEVICE"):
+        # (the device count only when it matters: this launching process never uses a device itself)
+        have = torch.cuda.device_count() if not os.environ.get("AVC_SINGLE_DEVICE") else None
+        if have is not None and have < args.gpus:
             sys.exit("bench.py: --gpus %d requested but only %d device(s) are visible (set AVC_SINGLE_DEVICE=1 AVC_DIST_BACKEND=gloo "
                      "to exercise the multi-rank path on one GPU)" % (args.gpus, have))
         import socket
@@ -366,6 +389,7 @@ def main():
     free0, total0 = torch.cuda.mem_get_info(dev)
     runner = build_runner(args.res, args.spp, args.small, dev)
     dt, per_kernel = timed_steps(runner, args.steps, args.warmup, dev, args.sync_debug)
+    dumped = dump_outputs(runner, args.dump_outputs) if args.dump_outputs and rank == 0 else None
     # footprint of the headline run: the operand panels are sized from the memory that was FREE when the run started (Engine.plan:
     # min(AVC_PANEL_GIB, 80 % of the free HBM); the G slab is halved before anything else gives), so the numbers below change with it
     eng0 = runner.renderer.engine
@@ -411,6 +435,8 @@ def main():
             "roofline": roofs.get(dominant),
             "roofline_all": roofs,
         }
+        if dumped is not None:
+            out["dumped_outputs"] = {"dir": args.dump_outputs, "files": dumped}
         # Some boxes of the pool sustain only ~3.9 TB/s of MIXED read + write HBM traffic (6 elsewhere); the backward kernel is the one
         # kernel of the step above that ceiling and then takes ~1.45 x as long as the weight-gradient launch instead of ~1.0 x
         # (profiles/r05_slow_box.md: same bytes by PMC, the waves wait at 2.3 GHz).  Say so in the line instead of leaving a riddle.

@@ -21,7 +21,8 @@ $AVC_SMPL_MODEL and refuse one whose hash differs.
 
 A section whose package or asset is missing is reported and skipped; the exit status is the number of REQUESTED sections that could not
 be written.  `--stand-in` (tests only) replaces each third-party call by this repo's oracle to exercise the plumbing; files written that
-way say `source = "stand-in"` and the pin tests refuse them as pins.
+way say `source = "stand-in"` and the pin tests refuse them as pins (the HIP-side tests compare the kernels with such a file while a
+row is unpinned, and report that with a warning).
 """
 import argparse
 import hashlib

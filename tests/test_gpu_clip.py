@@ -406,16 +406,25 @@ def test_runner_takes_clip_weights_from_a_checkpoint_file_without_standins(tmp_p
 
 
 @gpu
-def test_real_openai_weights_when_supplied():
-    """Runs only where the licensed artefacts exist: $AVC_CLIP_WEIGHTS = OpenAI's ViT-B-32.pt (or a state-dict / safetensors copy)
-    and $AVC_CLIP_BPE = bpe_simple_vocab_16e6.txt.gz.  HIP encoders vs the fp32 oracle ON THE REAL WEIGHTS (the seeded-weight tests
-    above cannot show the dynamic range of trained weights), and the tokenizer against the known ids of CLIP's README example."""
+def test_real_openai_weights_when_supplied(tmp_path):
+    """Where the licensed artefacts exist: $AVC_CLIP_WEIGHTS = OpenAI's ViT-B-32.pt (or a state-dict / safetensors copy) and $AVC_CLIP_BPE =
+    bpe_simple_vocab_16e6.txt.gz.  HIP encoders vs the fp32 oracle ON THE REAL WEIGHTS (the seeded-weight tests above cannot show the
+    dynamic range of trained weights), and the tokenizer against the known ids of CLIP's README example.  Without $AVC_CLIP_WEIGHTS the
+    same checks run on a checkpoint file written here -- the offline proxy for trained weights' dynamic range (clip_vit_oracle.
+    outlier_state_dict) plus a seeded text tower, loaded through the same file path -- the text tower on fixed token ids."""
     import os
-    wpath, bpath = os.environ.get("AVC_CLIP_WEIGHTS"), os.environ.get("AVC_CLIP_BPE")
-    if not wpath or not os.path.exists(wpath):
-        pytest.skip("$AVC_CLIP_WEIGHTS not set: no real CLIP checkpoint on this machine")
     from oracle import clip_text_oracle as T
     from avatarclip_amd import clip_vit as V
+    wpath, bpath = os.environ.get("AVC_CLIP_WEIGHTS"), os.environ.get("AVC_CLIP_BPE")
+    real = bool(wpath) and os.path.exists(wpath)
+    if not real:
+        import warnings
+        warnings.warn(UserWarning("$AVC_CLIP_WEIGHTS not set: the HIP towers were checked on the outlier-proxy checkpoint, not on OpenAI's "
+                                  "weights (parity on the real weights stays unpinned)"))
+        seeded = dict(C.outlier_state_dict(0))
+        seeded.update(T.random_state_dict(0))
+        wpath = str(tmp_path / "clip_seeded.pt")
+        torch.save(seeded, wpath)
     sd = {k: v.float() for k, v in V.load_state_dict(wpath).items()}
     model = V.ClipVisionB32(sd, torch.device("cuda"))
     g = torch.Generator().manual_seed(5)
@@ -423,6 +432,14 @@ def test_real_openai_weights_when_supplied():
     emb = model.encode_image(img.cuda()).float().cpu()
     ref = C.encode_image(sd, img)
     assert torch.cosine_similarity(emb, ref, dim=-1).min() > 0.999
+    if not real:
+        tok = torch.zeros(2, 77, dtype=torch.long)
+        for i, n in enumerate((5, 12)):                  # <start>, n word ids, <end>, padding
+            tok[i, 0], tok[i, n + 1] = 49406, 49407
+            tok[i, 1:n + 1] = torch.randint(1, 49406, (n,), generator=g)
+        out = model.encode_text(tok).float().cpu()
+        assert torch.cosine_similarity(out, T.encode_text(sd, tok), dim=-1).min() > 0.999
+        return
     if bpath and os.path.exists(bpath):
         from avatarclip_amd import tokenizer as TK
         tk = TK.SimpleTokenizer(bpath)

@@ -410,3 +410,36 @@ def test_cli_train_clip_from_a_conf_file(tmp_path):
     assert p.returncode == 0, p.stderr[-2000:]
     assert "loss" in p.stdout
     assert (tmp_path / "exp" / "smoke" / "checkpoints" / "ckpt_000003.pth").exists()
+
+
+@gpu
+def test_bench_dump_outputs_reproduce_run_to_run(tmp_path):
+    """`bench.py --dump-outputs DIR` end to end: the result line names the files, they hold float32 / float64 arrays (<= 64 MB in all), and
+    two runs with the same arguments write the same arrays (seeded inputs; an iteration is bit-reproducible)"""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "AVC_DIST_BACKEND", "AVC_SINGLE_DEVICE"):
+        env.pop(k, None)
+    dumps = []
+    for run in ("a", "b"):
+        out_dir = str(tmp_path / run)
+        cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--res", "64", "--small",
+               "--no-cpu-baseline", "--dump-outputs", out_dir]
+        r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=root)
+        assert r.returncode == 0, r.stderr[-3000:]
+        line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+        assert line["steps"] == 2 and line["ms_per_step"] > 0 and line["dumped_outputs"]["dir"] == out_dir
+        files = line["dumped_outputs"]["files"]
+        assert {"loss.npy", "color_loss.npy", "eikonal_loss.npy", "cosine.npy", "params.npy", "grads.npy"} <= set(files)
+        assert sorted(files) == sorted(os.listdir(out_dir))
+        arrays = {f: np.load(os.path.join(out_dir, f)) for f in files}
+        assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in arrays.values())
+        assert sum(a.nbytes for a in arrays.values()) <= 64 << 20 and arrays["params.npy"].shape == arrays["grads.npy"].shape
+        dumps.append(arrays)
+    a, b = dumps
+    assert sorted(a) == sorted(b)
+    for f in a:
+        assert np.array_equal(a[f], b[f]), (f, float(np.abs(a[f].astype(np.float64) - b[f]).max()))

@@ -5,6 +5,7 @@ import os
 import re
 
 import numpy as np
+import pytest
 import torch
 
 from tests.helpers import load_case, GOLDEN, ROOT
@@ -196,7 +197,8 @@ def test_conf_parser_reads_every_reference_conf():
     import glob
     import os
     from avatarclip_amd.conf import ConfigFactory
-    root = "/root/reference/AvatarGen/AppearanceGen/confs"
+    from oracle import ref_loader
+    root = os.path.join(ref_loader.REF_AG, "confs")
     files = sorted(glob.glob(os.path.join(root, "**", "*.conf"), recursive=True))
     if not files:
         pytest.skip("reference checkout not present")

@@ -61,3 +61,34 @@ def test_runner_loop_matches_independent_oracle_iteration_on_cpu():
         assert abs(r.optimizer.param_groups[0]["lr"] - st.opt.param_groups[0]["lr"]) < 1e-12
     for pa, pb in zip(r.params_to_train, st.params()):
         assert (pa.detach() - pb.detach()).abs().max() < 1e-6
+
+
+def test_bench_dump_outputs_writes_the_last_step(tmp_path):
+    """bench.py --dump-outputs: the last step's returned loss, its loss terms and the parameters / gradients the caller holds afterwards,
+    as float32 / float64 .npy files (a CPU runner on the oracle kernels stands in for the timed path)"""
+    import os
+    import bench
+    from tests.dp_common import build_runner
+    r = build_runner(torch.device("cpu"), 16, 16, True)
+    for i in range(2):
+        loss = r.train_clip_iteration(i)
+        r.update_learning_rate()
+    files = bench.dump_outputs(r, str(tmp_path / "out"))
+    assert {"loss.npy", "color_loss.npy", "eikonal_loss.npy", "cosine.npy", "params.npy", "grads.npy"} <= set(files)
+    arrays = {f: np.load(os.path.join(str(tmp_path / "out"), f)) for f in files}
+    assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+    assert arrays["loss.npy"][0] == float(loss)
+    st = r.last_stats
+    for f, key in (("color_loss.npy", "color"), ("eikonal_loss.npy", "eikonal"), ("cosine.npy", "cosine"), ("s_val.npy", "s_val")):
+        assert arrays[f][0] == float(st[key]), f
+    # parameter by parameter, in Runner.params_to_train order: the values after the second Adam step and the gradient that step used
+    ps, grads, params = r.params_to_train, arrays["grads.npy"], arrays["params.npy"]
+    assert params.size == grads.size == sum(p.numel() for p in ps)
+    o = 0
+    for p in ps:
+        n = p.numel()
+        assert np.array_equal(params[o:o + n], p.detach().reshape(-1).numpy())
+        assert p.grad is not None and np.array_equal(grads[o:o + n], p.grad.reshape(-1).numpy())
+        o += n
+    assert np.abs(grads).sum() > 0

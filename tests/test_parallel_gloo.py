@@ -142,7 +142,9 @@ def test_replica_layout_and_environment(tmp_path, monkeypatch):
     outs = [str(tmp_path / ("r%d.json" % i)) for i in range(9)]
     cmds = [[sys.executable, "-c", prog, outs[i], "3" if i == 4 else "0"] for i in range(9)]
     monkeypatch.delenv("GPU_MAX_HW_QUEUES", raising=False)
-    rcs = replicas.launch_commands(cmds, gpus=[0, 1], log_dir=str(tmp_path / "logs"), env=dict(os.environ, RANK="3", WORLD_SIZE="8"))
+    # an unrestricted parent (no device-visibility variable inherited from the machine running the test; the restricted case follows below)
+    unrestricted = {k: v for k, v in os.environ.items() if k not in ("HIP_VISIBLE_DEVICES", "CUDA_VISIBLE_DEVICES", "ROCR_VISIBLE_DEVICES")}
+    rcs = replicas.launch_commands(cmds, gpus=[0, 1], log_dir=str(tmp_path / "logs"), env=dict(unrestricted, RANK="3", WORLD_SIZE="8"))
     assert rcs == [0, 0, 0, 0, 3, 0, 0, 0, 0]
     for i in range(9):
         e = json.load(open(outs[i]))
