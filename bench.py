@@ -11,6 +11,10 @@ drawn with the reference's sampling code.
 
 Prints ONE JSON line (rank 0).  value = whole-job rays/s (all ranks), weak scaling (one view per GPU per step).
 --dump-outputs DIR also writes what the last timed step computed as DIR/<name>.npy (see dump_outputs).
+A plain run sets up, warms up, times the steps and reports them (the per-kernel figures come from events of those same steps).
+--full adds the legs that take runs of their own (see optional_legs): the extra_configs (BASELINE configs 2 and 3-per-GPU, the
+reference's default silhouette mode) and the CPU baseline: about 70 s more on one MI355X, where a plain run spends about 6 s
+outside its steps.
 """
 import argparse
 import json
@@ -327,7 +331,7 @@ def step_flops(res, spp):
     return res * res * ((spp // 2 + (spp // 2) * 3 // 4) * F_SDF_ONLY + spp * 3 * F_PT)
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
@@ -335,12 +339,26 @@ def main():
     ap.add_argument("--res", type=int, default=512)
     ap.add_argument("--spp", type=int, default=64)
     ap.add_argument("--small", action="store_true", help="128-wide nets (confs/examples_small)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the extra_configs legs (BASELINE configs 2 and 3-per-GPU)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the extra_configs legs and the CPU baseline (single-GPU runs only; see optional_legs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the extra_configs legs (BASELINE configs 2 and 3-per-GPU)")
     ap.add_argument("--sync-debug", action="store_true", help="development aid: warn (with a stack) on every host-device synchronisation inside the timed steps")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last step computed (loss terms, parameters, gradients) as DIR/<name>.npy (rank 0)")
-    args = ap.parse_args()
+    return ap.parse_args(argv)
+
+
+def optional_legs(args, world):
+    """(extra_configs, cpu_baseline): whether this run adds the legs its headline does not need.  Only --full runs them, and only
+    in a single-GPU run; the extra_configs legs also need the headline's own configuration (full nets, 512^2, 64 spp)."""
+    single = args.full and world == 1
+    extras = single and not args.no_extra and not args.small and (args.res, args.spp) == (512, 64)
+    return extras, single and not args.no_cpu_baseline
+
+
+def main():
+    args = parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` on its own: start the N ranks here (one process per GPU, RCCL over xGMI), exactly the way
@@ -445,8 +463,9 @@ def main():
             out["box_note"] = ("mlp_bwd_kernel %.1f ms vs weight_grad_all_kernel %.1f ms: this box caps mixed read+write HBM traffic "
                                "(profiles/r05_slow_box.md); on the other boxes the two are equal and the step is ~%.0f ms shorter"
                                % (kb, kw, kb - kw))
-    # ---- extra_configs (rank 0 of a single-GPU run): BASELINE config 2 (224^2, 64 spp) and config 3's per-GPU share (512^2, 128 spp)
-    if world == 1 and not args.no_extra and not args.small and (args.res, args.spp) == (512, 64):
+    run_extras, run_cpu_baseline = optional_legs(args, world)
+    # ---- extra_configs (--full, rank 0 of a single-GPU run): BASELINE config 2 (224^2, 64 spp) and config 3's per-GPU share (512^2, 128 spp)
+    if run_extras:
         import gc
         del runner
         gc.collect()
@@ -493,7 +512,7 @@ def main():
         torch.cuda.empty_cache()
         out["extra_configs"] = extras
     if rank == 0:
-        if not args.no_cpu_baseline and world == 1:
+        if run_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args.spp)
             out["speedup_vs_cpu_baseline"] = out["value"] / out["cpu_baseline"]["value"]
         print(json.dumps(out))

@@ -295,3 +295,19 @@ def test_softplus_direct_form_and_relu_mask_bit_order_restated():
         for r in range(16):
             assert ((bits >> ((r >> 1) + 8 * (r & 1))) & 1) == int(a[r] > 0), (r, a)
         assert bits < (1 << 16)
+
+
+def test_bench_runs_its_extra_legs_only_with_full():
+    """a plain `bench.py` run is the headline alone; --full adds the extra_configs legs and the CPU baseline (single-GPU runs), and
+    --no-extra / --no-cpu-baseline drop one of them again"""
+    import bench
+    plain = ["--gpus", "1", "--steps", "10", "--warmup", "5"]
+    assert bench.optional_legs(bench.parse_args(plain), 1) == (False, False)
+    assert bench.optional_legs(bench.parse_args(plain + ["--dump-outputs", "d"]), 1) == (False, False)
+    full = plain + ["--full"]
+    assert bench.optional_legs(bench.parse_args(full), 1) == (True, True)
+    assert bench.optional_legs(bench.parse_args(full + ["--no-extra"]), 1) == (False, True)
+    assert bench.optional_legs(bench.parse_args(full + ["--no-cpu-baseline"]), 1) == (True, False)
+    assert bench.optional_legs(bench.parse_args(full + ["--small"]), 1) == (False, True)
+    assert bench.optional_legs(bench.parse_args(full + ["--res", "224"]), 1) == (False, True)
+    assert bench.optional_legs(bench.parse_args(["--gpus", "2", "--full"]), 2) == (False, False)
