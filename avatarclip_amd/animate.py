@@ -12,13 +12,16 @@ What is built                                                                  r
   VPoserRealNVP    (conditional flow: decode / encode / sample / get_pose)      pose_generation.py:176-286
   MotionInterpolation (linear walk through VPoser's latent space)               motion_generation.py:100-137
   MotionOptimizer  (transformer motion-VAE decoder + reconstruction / delta     motion_generation.py:140-358
-                    losses; `clip_coef` must be 0, see below)
+                    losses + the CLIP term when clip_coef > 0, see below)
+  PoseOptimizer    (SMPL body pose optimised against the CLIP score)            pose_generation.py:102-135
+  VPoserOptimizer  (VPoser latent optimised against the CLIP score)             pose_generation.py:138-173
   build_pose_generator / build_motion_generator / main (conf-driven CLI)        builder.py, main.py
 
-What is NOT built, and why: PoseOptimizer, VPoserOptimizer and MotionOptimizer's CLIP term (clip_coef > 0) differentiate the CLIP score with
-respect to the POSE through neural_renderer's backward pass -- a hand-designed pseudo-gradient of the rasteriser that cannot be restated without
-its source.  Those entry points raise NotImplementedError naming exactly that; the reference's own `motion_ablation/baseline`
-(clip_coef = 0) and `motion_ablation/interpolation` confs, and both pose confs that need no renderer gradient, run.
+The renderer gradient is OPT-IN: PoseOptimizer, VPoserOptimizer and MotionOptimizer's CLIP term (clip_coef > 0, the reference's default, so its
+confs/base.conf) differentiate the CLIP score with respect to the POSE through the rasteriser, which takes neural_renderer's backward pass -- the
+approximate gradient of Kato, Ushiku and Harada (CVPR 2018), restated and unpinned (mesh_render.py, csrc/avc_raster_grad.hip).
+`AnimateContext(renderer_gradient=True)` (CLI: --renderer_gradient) makes the default render differentiable and lets them run; without it they
+raise NotImplementedError as before, and a user-supplied `render_fn` combined with the switch is taken to be differentiable.
 """
 import math
 import os
@@ -104,13 +107,17 @@ class AnimateContext:
       vposer        VPoser-like object: decode(z[B,32]) -> {'pose_body': [B,21,3]}, encode(pose[B,63]).mean -> [B,32]
       render_fn     callable(vertices[bs,V,3] tensor, faces, angles) -> images [len(angles) * bs, 3, H, W] in [0,1], camera-major
                     (None: the HIP rasteriser below; the reference textures the body with data/smpl_uv.obj, which its repository does not hold)
+      renderer_gradient False (default): render_fn's images carry no gradient and the generators that need one refuse to run; True: the default
+                    render_fn is the differentiable HIP path (mesh_render.render_grey_batch), a given render_fn is taken to be differentiable
     """
 
-    def __init__(self, perceptor, text_feature, smpl, vposer, render_fn=None, device=None, image_size=256):
+    def __init__(self, perceptor, text_feature, smpl, vposer, render_fn=None, device=None, image_size=256, renderer_gradient=False):
         self.perceptor, self.text_feature, self.smpl, self.vp = perceptor, text_feature, smpl, vposer
         self.device = torch.device(device) if device is not None else smpl["v_template"].device
         self.image_size = image_size
-        self.render_fn = render_fn if render_fn is not None else self._render_hip
+        self.renderer_gradient = bool(renderer_gradient)
+        default = self._render_hip_grad if self.renderer_gradient else self._render_hip
+        self.render_fn = render_fn if render_fn is not None else default
 
     def get_text_feature(self, text):
         with torch.no_grad():
@@ -144,6 +151,26 @@ class AnimateContext:
                 out.append(g.unsqueeze(0).expand(3, -1, -1))
         return torch.stack(out)
 
+    def _render_hip_grad(self, vertices, faces, angles):
+        """_render_hip with autograd to the vertices (mesh_render.render_grey_batch: one batched forward-with-save, neural_renderer's approximate
+        backward): the same elevation draws in the same order, the len(angles) x bs renders camera-major in one call"""
+        from .mesh_render import render_grey_batch
+        from .shapegen_render import get_points_from_angles
+        eyes = [get_points_from_angles(CAMERA_DISTANCE, np.random.randn() * 0.3, a) for a in angles]     # draw order: once per angle, before the batch loop
+        bs = vertices.shape[0]
+        eye_all = [e.astype(np.float32) for e in eyes for _ in range(bs)]
+        dir_all = [(-e / np.linalg.norm(e)).astype(np.float32) for e in eyes for _ in range(bs)]
+        v = vertices.unsqueeze(0).expand(len(eyes), -1, -1, -1).reshape(len(eyes) * bs, *vertices.shape[1:])
+        g = render_grey_batch(v, faces, eye_all, dir_all, image_size=self.image_size)
+        return g.unsqueeze(1).expand(-1, 3, -1, -1)
+
+    def release_graphs(self):
+        """Runner.train_clip_iteration's call at the top of every generator iteration: a graph-replayed encode_image that never reached backward
+        does not hold its instance"""
+        release = getattr(self.perceptor, "release_graphs", None)
+        if release is not None:
+            release()
+
     def get_pose_feature(self, pose, angles=None):
         """mean CLIP embedding of the posed body over the cameras -> [bs, 512]  (pose_generation.py:63-89)"""
         angles = DEFAULT_ANGLES if angles is None else tuple(angles)
@@ -161,18 +188,79 @@ class AnimateContext:
 
 
 _NO_RENDERER_GRADIENT = ("%s optimises the CLIP score with respect to the pose THROUGH the rasteriser: it needs neural_renderer's backward pass (a hand-designed "
-                         "pseudo-gradient), which is not part of this repository (DESIGN.md section 8).  Available without it: VPoserCodebook, VPoserRealNVP, "
-                         "MotionInterpolation, MotionOptimizer with clip_coef = 0 (the reference's motion_ablation/baseline conf)")
+                         "pseudo-gradient), which this context does not enable (DESIGN.md section 8).  Build the context with "
+                         "AnimateContext(..., renderer_gradient=True) (CLI: --renderer_gradient) to run it on the restated approximate gradient.  Available "
+                         "without it: VPoserCodebook, VPoserRealNVP, MotionInterpolation, MotionOptimizer with clip_coef = 0 (the reference's "
+                         "motion_ablation/baseline conf)")
 
 
-class PoseOptimizer:
+def _needs_renderer_gradient(ctx, what):
+    if not getattr(ctx, "renderer_gradient", False):
+        raise NotImplementedError(_NO_RENDERER_GRADIENT % what)
+
+
+class _ClipPoseOptimizer:
+    """the loop PoseOptimizer / VPoserOptimizer share (pose_generation.py:115-128, :151-166): a parameter drawn on the host with torch.randn, the
+    optimiser getattr(torch.optim, optim_name)(**optim_cfg), num_iteration steps of 1 - cos(mean CLIP embedding over the 5 cameras, text)"""
+    DIM = 63
+
+    def __init__(self, ctx, optim_name="Adam", optim_cfg=None, num_iteration=500, topk=5, name=None, smpl_path=None, vposer_path=None):
+        self.ctx, self.name, self.topk = ctx, name or type(self).__name__, int(topk)
+        self.optim_name, self.optim_cfg, self.num_iteration = optim_name, dict(optim_cfg or {"lr": 0.01}), int(num_iteration)
+
+    def _pose_of(self, param):
+        raise NotImplementedError
+
+    def _result(self, param, last_pose):
+        raise NotImplementedError
+
+    def get_pose(self, text_feature):
+        param = nn.Parameter(torch.randn(self.DIM))                       # drawn on the host, as the reference does
+        opt = getattr(torch.optim, self.optim_name)([param], **self.optim_cfg)
+        new_pose = None
+        for _ in range(self.num_iteration):
+            self.ctx.release_graphs()
+            new_pose = self._pose_of(param)
+            clip_feature = self.ctx.get_pose_feature(new_pose).squeeze(0)
+            loss = (1 - F.cosine_similarity(clip_feature, text_feature, dim=-1)).mean()
+            opt.zero_grad()
+            loss.backward()
+            opt.step()
+        return self._result(param, new_pose)
+
+    def get_topk_poses(self, text):
+        tf = self.ctx.get_text_feature(text)
+        poses = self.ctx.sort_poses_by_score(text, [self.get_pose(tf) for _ in range(self.topk)])
+        return torch.stack(poses, dim=0)
+
+
+class PoseOptimizer(_ClipPoseOptimizer):
+    """pose_generation.py:102-135: the 63 body-pose values themselves are optimised; returns the parameter after its last step"""
+
     def __init__(self, ctx=None, **conf):
-        raise NotImplementedError(_NO_RENDERER_GRADIENT % "PoseOptimizer (pose_generation.py:102-135)")
+        _needs_renderer_gradient(ctx, "PoseOptimizer (pose_generation.py:102-135)")
+        super().__init__(ctx, **conf)
+
+    def _pose_of(self, param):
+        return param.to(self.ctx.device)
+
+    def _result(self, param, last_pose):
+        return pose_padding(param.data).to(self.ctx.device)
 
 
-class VPoserOptimizer:
+class VPoserOptimizer(_ClipPoseOptimizer):
+    """pose_generation.py:138-173: VPoser's 32-d latent is optimised; returns the pose decoded in the last iteration, before its step"""
+    DIM = 32
+
     def __init__(self, ctx=None, **conf):
-        raise NotImplementedError(_NO_RENDERER_GRADIENT % "VPoserOptimizer (pose_generation.py:138-173)")
+        _needs_renderer_gradient(ctx, "VPoserOptimizer (pose_generation.py:138-173)")
+        super().__init__(ctx, **conf)
+
+    def _pose_of(self, param):
+        return self.ctx.vp.decode(param.to(self.ctx.device).unsqueeze(0))["pose_body"].contiguous().view(-1)
+
+    def _result(self, param, last_pose):
+        return pose_padding(last_pose.detach())
 
 
 # ----------------------------------------------------------------------------------------------------------------- candidate poses
@@ -359,15 +447,16 @@ class MotionXTransformerDecoder(nn.Module):
 class MotionOptimizer(nn.Module):
     """motion_generation.py:249-358: a latent code of the pretrained motion VAE optimised (Adam, 5 000 iterations) so that the decoded motion
     passes through the candidate poses IN ORDER (for candidate j the best-matching frame's 6-d rotation error, weighted recon_coef[j]) while the
-    frame-to-frame change is REWARDED (- delta_coef x mse).  The reference adds clip_coef x a CLIP term through the rasteriser; here clip_coef
-    must be 0 (see the module docstring).  Decoder / encoder parameter names are the reference's: data/motion_vae.pth's `state_dict` loads as it is."""
+    frame-to-frame change is REWARDED (- delta_coef x mse).  clip_coef > 0 adds clip_coef x the CLIP term of every clip_num_part-th frame
+    (random phase) rendered at azimuth 150 through the rasteriser, which needs AnimateContext(renderer_gradient=True) (module docstring).  Decoder / encoder parameter names are the reference's: data/motion_vae.pth's `state_dict` loads as it is."""
 
     def __init__(self, ctx, num_frame=60, latent_dim=256, num_layers=4, num_heads=4, ckpt_path=None, state_dict=None, optim_name="Adam", optim_cfg=None,
                  num_iteration=5000, recon_coef=(1, 0.8, 0.6, 0.4, 0.2), clip_coef=0.001, delta_coef=0.01, clip_num_part=30, name="MotionOptimizer",
                  smpl_path=None, vposer_path=None):
         super().__init__()
         if float(clip_coef) > 0:
-            raise NotImplementedError(_NO_RENDERER_GRADIENT % ("MotionOptimizer with clip_coef = %g (motion_generation.py:333-345)" % clip_coef))
+            _needs_renderer_gradient(ctx, "MotionOptimizer with clip_coef = %g (motion_generation.py:333-345)" % clip_coef)
+        self.clip_coef, self.clip_num_part = float(clip_coef), int(clip_num_part)
         self.ctx, self.name, self.num_frame, self.latent_dim = ctx, name, int(num_frame), int(latent_dim)
         kw = dict(seq_len=self.num_frame, latent_dim=latent_dim, num_heads=num_heads, ff_size=latent_dim * 4, num_layers=num_layers)
         self.encoder = MotionXTransformerEncoder(output_dim=latent_dim, **kw)
@@ -396,15 +485,29 @@ class MotionOptimizer(nn.Module):
         delta = F.mse_loss(motion[:-1], motion[1:])
         return recon, delta
 
+    def clip_loss(self, motion, text_feature):
+        """motion_generation.py:333-344: frames st_idx, st_idx + clip_num_part, ... (st_idx drawn from numpy's generator BEFORE the render's
+        elevation draw) rendered at azimuth 150, 1 - cos against the text, weighted by their position in time"""
+        self.ctx.release_graphs()
+        st_idx = np.random.randint(self.clip_num_part)
+        part_poses = motion[st_idx::self.clip_num_part].contiguous()
+        feats = self.ctx.get_pose_feature(part_poses, (150,))
+        return clip_score.motion_clip_loss(feats, text_feature, st_idx, self.clip_num_part, self.num_frame)
+
     def get_motion(self, text, poses):
         poses = poses[..., :63].contiguous().to(self.ctx.device)
         latent = nn.Parameter(torch.randn(self.latent_dim))               # drawn on the host, as the reference does
         opt = getattr(torch.optim, self.optim_name)([latent], **self.optim_cfg)
         motion = None
+        text_feature = self.ctx.get_text_feature(text) if self.clip_coef > 0 else None
         for _ in range(self.num_iteration):
             motion = self.decode(latent.to(self.ctx.device))
             recon, delta = self.losses(motion, poses)
-            loss = recon - (delta * self.delta_coef if self.delta_coef > 0 else 0.0)
+            if self.clip_coef > 0:
+                loss = recon + self.clip_coef * self.clip_loss(motion, text_feature)
+            else:
+                loss = recon
+            loss = loss - (delta * self.delta_coef if self.delta_coef > 0 else 0.0)
             opt.zero_grad()
             loss.backward()
             opt.step()
@@ -445,7 +548,7 @@ def run(conf, ctx, pose_assets=None, motion_assets=None):
 
 
 def main(argv=None):
-    """python -m avatarclip_amd.animate --conf confs/base.conf --clip_weights ViT-B-32.pt --bpe bpe_simple_vocab_16e6.txt.gz --smpl SMPL_NEUTRAL.pkl
+    """python -m avatarclip_amd.animate [--renderer_gradient] --conf confs/base.conf --clip_weights ViT-B-32.pt --bpe bpe_simple_vocab_16e6.txt.gz --smpl SMPL_NEUTRAL.pkl
     --vposer data/vposer [--codebook data/codebook.pth] [--realnvp data/pose_realnvp.pth] [--motion_vae data/motion_vae.pth]
     (AvatarAnimate/main.py with the assets its constructors load named on the command line; VPoser itself comes from the `human_body_prior` package)"""
     import argparse
@@ -454,6 +557,9 @@ def main(argv=None):
     ap = argparse.ArgumentParser(description=main.__doc__)
     ap.add_argument("--conf", default="./confs/base.conf")
     ap.add_argument("--gpu", type=int, default=0)
+    ap.add_argument("--renderer_gradient", action="store_true",
+                    help="differentiate the renders (neural_renderer's approximate backward, restated): PoseOptimizer, VPoserOptimizer and "
+                         "MotionOptimizer with clip_coef > 0 (the reference's confs/base.conf) need it")
     for name in ("clip_weights", "bpe", "smpl", "vposer"):
         ap.add_argument("--" + name, required=True)
     for name in ("codebook", "realnvp", "motion_vae"):
@@ -469,7 +575,8 @@ def main(argv=None):
     perceptor = clip_vit.ClipVisionB32({k: v.float() for k, v in clip_vit.load_state_dict(args.clip_weights).items()}, dev)
     tk = tokenizer.SimpleTokenizer(args.bpe)
     text_feature = lambda text: perceptor.encode_text(tokenizer.tokenize([text], tk))[0]
-    ctx = AnimateContext(perceptor, text_feature, smpl_lbs.load_smpl_arrays(args.smpl, dev), vp.to(dev).eval(), device=dev)
+    ctx = AnimateContext(perceptor, text_feature, smpl_lbs.load_smpl_arrays(args.smpl, dev), vp.to(dev).eval(), device=dev,
+                         renderer_gradient=args.renderer_gradient)
     with open(args.conf) as fh:
         conf = ConfigFactory.parse_string(fh.read())
     pose_assets = {"codebook_path": args.codebook} if args.codebook else ({"ckpt_path": args.realnvp} if args.realnvp else {})

@@ -8,7 +8,7 @@ import torch
 from . import build as _build
 
 _lib = None
-ABI_VERSION = 2          # AVC_ABI_VERSION of include/avc.h this binding was written against
+ABI_VERSION = 3          # AVC_ABI_VERSION of include/avc.h this binding was written against
 
 c_int, c_long, c_float, c_void_p = ctypes.c_int, ctypes.c_long, ctypes.c_float, ctypes.c_void_p
 P = c_void_p
@@ -50,6 +50,8 @@ _SIGS = {
     "avc_rasterize_faces": (c_int, [P, P, c_int, c_int, c_float, c_float, P, P, P]),
     "avc_rasterize_scratch_bytes": (c_long, [c_int, c_int]),
     "avc_rasterize_mesh": (c_int, [P, c_int, P, c_int, P, c_float, P, c_int, c_float, c_float, P, P, c_int, c_int, P, P]),
+    "avc_rasterize_mesh_save": (c_int, [P, c_int, c_int, P, c_int, P, c_float, P, c_int, c_float, c_float, P, P, P, P, P]),
+    "avc_rasterize_mesh_grad": (c_int, [P, P, c_int, c_int, P, c_int, P, P, c_int, c_float, P, P, P, P, P, P]),
     "avc_dense_params_fwd": (c_int, [c_int, P, P, P, P, P, P, P, P, P]),
     "avc_dense_params_bwd": (c_int, [c_int, P, P, P, P, P, P, P, P, P, P, P]),
     "avc_weight_grad_all": (c_int, [P, c_int, P, c_int, c_int, P, c_long, P, P, c_int, c_int, c_int, P]),

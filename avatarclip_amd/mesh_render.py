@@ -1,0 +1,159 @@
+"""Differentiable renders of a mesh for AvatarAnimate's CLIP-guided optimisers (AvatarAnimate/models/render.py:10-39):
+N grey renders of N vertex sets of one topology in one call, with autograd to the vertices.
+
+Forward: neural_renderer's conventions as `smpl_prior.MeshPrior.render_grey` applies them (vertices @ rot_mat, fill_back, ambient 0.5 +
+directional 0.5 face light, 60 degree field of view, 2 x super-sampling) on the HIP rasteriser (`avc_rasterize_mesh_save`,
+csrc/avc_raster_grad.hip): the images are bit-identical to MeshPrior's.  Backward: neural_renderer's approximate gradient (Kato, Ushiku and
+Harada, "Neural 3D Mesh Renderer", CVPR 2018, section 3.3; `avc_rasterize_mesh_grad`, rules in DESIGN.md section 8) to the projected
+vertices and to the face light; the projection Jacobian (zero for vertices behind the camera, the reference README's patch) and the light's
+dependence on the face normals are torch.  No CPU fallback."""
+import numpy as np
+import torch
+
+from . import h2d
+from . import lib as L
+from .smpl_prior import ROT_MAT
+
+DEFAULT_EPS = 1e-4          # neural_renderer's DEFAULT_EPS
+VIEWING_ANGLE, NEAR, FAR = 30.0, 0.1, 100.0
+
+_topologies = {}            # faces bytes -> (faces2 int32 [2F,3], vf_ptr, vf_ent) on a device
+_scratch = {}               # (device, stream, (N, F, S), bytes) -> 0xFF-filled z-buffer scratch (every call leaves it so)
+
+
+def camera_frame(eye, direction):
+    """neural_renderer/look.py's frame in float32 on the host, as MeshPrior.render_grey builds it -> [12]: eye, x, y, z axes"""
+    f = np.float32
+    z = np.asarray(direction, f)
+    z = z / f(np.sqrt((z * z).sum(dtype=f)))
+    x = np.cross(np.array([0.0, 1.0, 0.0], f), z).astype(f)
+    x = x / f(np.sqrt((x * x).sum(dtype=f)))
+    y = np.cross(z, x).astype(f)
+    y = y / f(np.sqrt((y * y).sum(dtype=f)))
+    return np.concatenate([np.asarray(eye, f), x, y, z])
+
+
+def face_light(v, faces, light_ambient=0.5, light_directional=0.5, light_direction=(0.0, 1.0, 0.0)):
+    """neural_renderer/lighting.py in world space for one vertex set [V,3] -> light of the fill_back face list [2F]: MeshPrior.__init__'s
+    expression, differentiable"""
+    fv = v[faces]
+    n = torch.cross(fv[:, 0] - fv[:, 1], fv[:, 2] - fv[:, 1], dim=1)
+    n = n / n.norm(dim=1, keepdim=True).clamp(min=1e-5)
+    c = n @ torch.tensor(light_direction, dtype=v.dtype, device=v.device)
+    return torch.cat([light_ambient + light_directional * c.clamp(min=0), light_ambient + light_directional * (-c).clamp(min=0)])
+
+
+def project(v, cam, width):
+    """look + perspective in torch (the arithmetic the kernel does, as a differentiable function): v [N,V,3], cam [N,12] -> ndc [N,V,3]"""
+    R = cam[:, 3:].reshape(-1, 3, 3)
+    c = torch.einsum("nvk,njk->nvj", v - cam[:, None, :3], R)
+    front = c[..., 2:3] > 0
+    z = torch.where(front, c[..., 2:3], torch.ones_like(c[..., 2:3]))
+    ndc = torch.cat([c[..., :2] / z / width, c[..., 2:3]], -1)
+    return torch.where(front, ndc, torch.zeros_like(ndc))
+
+
+def project_vjp(v, cam, width, grad_ndc):
+    """the transpose of project's Jacobian applied to grad_ndc [N,V,3] -> [N,V,3]; zero for vertices behind the camera"""
+    R = cam[:, 3:].reshape(-1, 3, 3)
+    c = torch.einsum("nvk,njk->nvj", v - cam[:, None, :3], R)
+    cz = c[..., 2]
+    front = cz > 0
+    iz = torch.where(front, 1.0 / torch.where(front, cz, torch.ones_like(cz)), torch.zeros_like(cz))
+    gx, gy, gz = grad_ndc.unbind(-1)
+    dc = torch.stack([gx * iz / width, gy * iz / width,
+                      torch.where(front, gz - (gx * c[..., 0] + gy * c[..., 1]) * iz * iz / width, torch.zeros_like(gz))], -1)
+    return torch.einsum("nvj,njk->nvk", dc, R)
+
+
+def vertex_face_csr(faces2, V):
+    """vertex -> (3 face + corner) entries of a face list [F,3], in face order: (ptr [V+1], ent) int32"""
+    f = np.asarray(faces2, np.int64).reshape(-1)
+    if f.size and (f.min() < 0 or f.max() >= V):
+        raise ValueError("face indices outside [0, %d)" % V)
+    order = np.argsort(f, kind="stable")
+    ptr = np.zeros(V + 1, np.int64)
+    np.cumsum(np.bincount(f, minlength=V), out=ptr[1:])
+    return ptr.astype(np.int32), order.astype(np.int32)
+
+
+def _topology(faces, V, device):
+    f = np.ascontiguousarray(np.asarray(faces.detach().cpu() if torch.is_tensor(faces) else faces).astype(np.int64).reshape(-1, 3))
+    key = (f.tobytes(), V, str(device))
+    t = _topologies.get(key)
+    if t is None:
+        f2 = np.concatenate([f, f[:, ::-1]], 0)               # fill_back=True: every face also in reversed order
+        ptr, ent = vertex_face_csr(f2, V)
+        t = _topologies[key] = (torch.from_numpy(f2.astype(np.int32)).to(device), torch.from_numpy(f).to(device),
+                                torch.from_numpy(ptr).to(device), torch.from_numpy(ent).to(device))
+    return t
+
+
+def _scratch_for(device, layout, need):
+    """the z-buffers + large-face lists of one (N, F, S) layout.  A successful call leaves the z-buffers and the list counts empty, not the list
+    entries (face indices): a buffer is only ever reused for the same layout, where those bytes are list entries again."""
+    key = (str(device), L.stream(), layout, need)
+    z = _scratch.get(key)
+    if z is None:
+        for k in [k for k in _scratch if k[:2] == key[:2]]:
+            del _scratch[k]
+        z = _scratch[key] = torch.full((need,), 255, dtype=torch.uint8, device=device)
+    return z
+
+
+class _RasterFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, v_world, light2, cam, faces2, vf_ptr, vf_ent, S, width, eps):
+        N, V = v_world.shape[:2]
+        F2 = faces2.shape[0]
+        dev = v_world.device
+        lib = L.load()
+        vw, lt = v_world.detach().float().contiguous(), light2.detach().float().contiguous()
+        ndc = torch.empty(N, V, 3, device=dev, dtype=torch.float32)
+        image = torch.empty(N, S, S, device=dev, dtype=torch.float32)
+        fidx = torch.empty(N, 2 * S, 2 * S, device=dev, dtype=torch.int32)
+        need = N * lib.avc_rasterize_scratch_bytes(F2, 2 * S)
+        scratch = _scratch_for(dev, (N, F2, S), need)
+        try:
+            L.check(lib.avc_rasterize_mesh_save(L.ptr(vw), N, V, L.ptr(faces2), F2, L.ptr(cam), width, L.ptr(lt), S, NEAR, FAR, L.ptr(ndc),
+                                                L.ptr(image), L.ptr(fidx), L.ptr(scratch), L.stream()), "avc_rasterize_mesh_save")
+        except Exception:
+            _scratch.clear()            # an interrupted render leaves keys behind: never reuse that scratch
+            raise
+        ctx.save_for_backward(vw, lt, cam, faces2, vf_ptr, vf_ent, ndc, fidx)
+        ctx.S, ctx.width, ctx.eps = S, width, eps
+        ctx.mark_non_differentiable(ndc, fidx)
+        return image, ndc, fidx
+
+    @staticmethod
+    def backward(ctx, g_image, _g_ndc, _g_fidx):
+        vw, lt, cam, faces2, vf_ptr, vf_ent, ndc, fidx = ctx.saved_tensors
+        N, V = vw.shape[:2]
+        F2 = faces2.shape[0]
+        lib = L.load()
+        g = g_image.float().contiguous()
+        face_grad = torch.empty(N, F2, 6, device=vw.device, dtype=torch.float32)
+        grad_ndc = torch.empty(N, V, 3, device=vw.device, dtype=torch.float32)
+        grad_light = torch.empty(N, F2, device=vw.device, dtype=torch.float32)
+        L.check(lib.avc_rasterize_mesh_grad(L.ptr(g), L.ptr(ndc), N, V, L.ptr(faces2), F2, L.ptr(lt), L.ptr(fidx), ctx.S, ctx.eps, L.ptr(vf_ptr),
+                                            L.ptr(vf_ent), L.ptr(face_grad), L.ptr(grad_ndc), L.ptr(grad_light), L.stream()), "avc_rasterize_mesh_grad")
+        gv = project_vjp(vw, cam, ctx.width, grad_ndc) if ctx.needs_input_grad[0] else None
+        return gv, grad_light, None, None, None, None, None, None, None
+
+
+def render_grey_batch(v_world, faces, eyes, directions, image_size=256, eps=DEFAULT_EPS, return_state=False):
+    """v_world [N,V,3] (before rot_mat), faces [F,3], eyes / directions: N camera positions / viewing directions -> grey images [N,S,S]
+    (row 0 = top, no x flip; 0 = background) with autograd to v_world.  return_state: also (ndc [N,V,3], face index [N,2S,2S] y up)."""
+    dev = v_world.device
+    if dev.type != "cuda":
+        raise RuntimeError("render_grey_batch rasterises on the MI355X (no CPU fallback)")
+    N, V = v_world.shape[:2]
+    if len(eyes) != N or len(directions) != N:
+        raise ValueError("one camera per vertex set: %d vertex sets, %d eyes, %d directions" % (N, len(eyes), len(directions)))
+    faces2, f, vf_ptr, vf_ent = _topology(faces, V, dev)
+    v = v_world.float() @ torch.tensor(ROT_MAT, dtype=torch.float32, device=dev)
+    light2 = torch.stack([face_light(v[i], f) for i in range(N)])
+    cam = h2d.upload(np.stack([camera_frame(e, d) for e, d in zip(eyes, directions)]).reshape(-1), dev).reshape(N, 12)
+    width = float(np.tan(np.deg2rad(VIEWING_ANGLE)))
+    image, ndc, fidx = _RasterFn.apply(v, light2, cam, faces2, vf_ptr, vf_ent, int(image_size), width, float(eps))
+    return (image, ndc, fidx) if return_state else image

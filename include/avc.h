@@ -23,10 +23,11 @@ extern "C" {
 #define AVC_NET_SMALL 1 /* confs/examples_small:        SDF 39-128-128-89(+39)-129,     colour 134-128-{3,3}     */
 
 /* Interface revision of this header.  It changes whenever an existing entry point's argument list or meaning changes (2: round 5 put
- * `colsum` into avc_render_points_bwd and moved the second-order row-0 term out of the weight-gradient products), so a caller built
+ * `colsum` into avc_render_points_bwd and moved the second-order row-0 term out of the weight-gradient products; 3: the rasteriser's
+ * batched forward with save and its backward, avc_rasterize_mesh_save / avc_rasterize_mesh_grad), so a caller built
  * against an older header can refuse the library instead of passing arguments in the wrong slots:
  *     if (avc_version() != AVC_ABI_VERSION) abort();       (avatarclip_amd/lib.py: load() does exactly this) */
-#define AVC_ABI_VERSION 2
+#define AVC_ABI_VERSION 3
 
 const char* avc_last_error(void);
 int avc_version(void);
@@ -300,6 +301,25 @@ int avc_rasterize_mesh(const float* v_world, int V, const int* idx, int F, const
 long avc_rasterize_scratch_bytes(int F, int image_size);
 int avc_rasterize_faces(const float* faces, const float* light, int F, int image_size, float near_, float far_,
                         float* image, void* scratch /* avc_rasterize_scratch_bytes, 0xFF-filled on entry; left so */, void* stream);
+
+/* The differentiable form of the same render, for AvatarAnimate's CLIP-guided optimisers (AvatarAnimate/models/render.py:10-39: the
+ * renders of the posed body are differentiated with respect to its vertices).  Backward = the approximate gradient of Kato, Ushiku and
+ * Harada, "Neural 3D Mesh Renderer" (CVPR 2018) section 3.3, neural_renderer's published rasteriser backward, restated (DESIGN.md
+ * section 8; tests/nr_grad_restatement.py).
+ * avc_rasterize_mesh_save: N renders in one call, render i = the world-space mesh v_world[i] [V,3] (one topology idx [F,3], fill_back
+ * copies included) seen by camera cam[i] [12] (as avc_rasterize_mesh) with face light light[i] [F].  Outputs: image [N,S,S] (the pooled
+ * grey image, no x flip: bit-identical to avc_rasterize_mesh with flip_x = 0, channels = 1), ndc [N,V,3], fidx int32 [N,2S,2S] = the
+ * winning face of every super-sampled pixel, z-buffer orientation (row 0 = bottom), -1 = background.  scratch: N x
+ * avc_rasterize_scratch_bytes(F, 2 S) bytes, 0xFF-filled on entry, left so. */
+int avc_rasterize_mesh_save(const float* v_world, int N, int V, const int* idx, int F, const float* cam, float width, const float* light, int S,
+                            float near_, float far_, float* ndc, float* image, int* fidx, void* scratch, void* stream);
+/* avc_rasterize_mesh_grad: grad_image [N,S,S] + the saved ndc / fidx (and light, idx) -> grad_ndc [N,V,3] (z = 0: the pseudo-gradient moves
+ * x and y only) and grad_light [N,F] (sum of the pixel gradients over each face's pixels).  eps: neural_renderer's DEFAULT_EPS (1e-4).
+ * vf_ptr [V+1] / vf_ent: the vertex -> (3 face + corner) CSR of idx (one per topology); face_grad: scratch of N x F x 6 floats.
+ * Deterministic (no float atomics). */
+int avc_rasterize_mesh_grad(const float* grad_image, const float* ndc, int N, int V, const int* idx, int F, const float* light, const int* fidx,
+                            int S, float eps, const int* vf_ptr, const int* vf_ent, float* face_grad, float* grad_ndc, float* grad_light,
+                            void* stream);
 
 #ifdef __cplusplus
 }
