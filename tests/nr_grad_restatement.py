@@ -91,9 +91,10 @@ def _expand(starts, lengths):
     return rep, k
 
 
-def pseudo_grad(ndc, faces, light, fidx, G, eps=1e-4, count=None):
+def pseudo_grad(ndc, faces, light, fidx, G, eps=1e-4, count=None, abs_sum=None):
     """the rules on a super-sampled pixel gradient G [n, n] (y up) -> grad_ndc [V, 3] (float64 sums of float32 terms; z = 0).
-    count: optional dict, gets 'out' and 'in' = the number of run pixels visited."""
+    count: optional dict, gets 'out' and 'in' = the number of run pixels visited.  abs_sum: optional float64 array [V, 3], gets the sum of
+    |term| over the terms of every vertex component (a scale for the rounding of any order of summation)."""
     nd = np.asarray(ndc, f32)
     faces = np.asarray(faces)
     lt = np.asarray(light, f32)
@@ -146,6 +147,8 @@ def pseudo_grad(ndc, faces, light, fidx, G, eps=1e-4, count=None):
                             d = np.where(d > 0, d + eps, d - eps).astype(f32)
                             term = (delta / d).astype(f32)
                             grad[face[vert], comp] -= term[m].astype(np.float64).sum()
+                            if abs_sum is not None:
+                                abs_sum[face[vert], comp] += np.abs(term[m]).astype(np.float64).sum()
 
                 # out runs
                 sel = np.nonzero(fidx[at(u0, i_in)] == f)[0]
@@ -189,7 +192,7 @@ def light_grad(fidx, G, F):
     return np.bincount(fidx[m], weights=np.asarray(G, np.float64)[m], minlength=F)
 
 
-def backward(ndc, faces, light, fidx, grad_image, eps=1e-4, count=None):
+def backward(ndc, faces, light, fidx, grad_image, eps=1e-4, count=None, abs_sum=None):
     """grad_image [S, S] -> (grad_ndc [V, 3], grad_light [F])"""
     G = G_map(grad_image)
-    return pseudo_grad(ndc, faces, light, fidx, G, eps, count), light_grad(np.asarray(fidx), G, len(faces))
+    return pseudo_grad(ndc, faces, light, fidx, G, eps, count, abs_sum), light_grad(np.asarray(fidx), G, len(faces))

@@ -1,6 +1,7 @@
-"""The rules of neural_renderer's approximate rasteriser backward (tests/nr_grad_restatement.py) on hand-built cases, the torch
-side of avatarclip_amd.mesh_render (light from the vertices, projection Jacobian, vertex -> face CSR), and the CLIP-guided generators of
-avatarclip_amd.animate with AnimateContext(renderer_gradient=True) on CPU stand-ins."""
+"""The rules of neural_renderer's approximate rasteriser backward (tests/nr_grad_restatement.py) on hand-built cases and,
+restated in float64, against the geometry of random triangles; the torch side of avatarclip_amd.mesh_render (light from the vertices, projection
+Jacobian, vertex -> face CSR), and the CLIP-guided generators of avatarclip_amd.animate with AnimateContext(renderer_gradient=True) on CPU
+stand-ins."""
 import numpy as np
 import pytest
 import torch
@@ -132,3 +133,87 @@ def test_vertex_face_csr():
         assert all(f2[e // 3, e % 3] == v for e in got) and list(got) == sorted(got)
     with pytest.raises(ValueError):
         M.vertex_face_csr(f2, 3)
+
+
+def _runs(P, fi, n):
+    """DESIGN.md section 8's visits for face 0 of pixel-space vertices P [3,2], restated in float64 (not the restatement's arithmetic) ->
+    (a, b, o, axis, u0, w_x, w, is the in run's pixel at w_in) for every run pixel"""
+    out = []
+    for e in range(3):
+        a, b, o = e, (e + 1) % 3, (e + 2) % 3
+        for axis in (0, 1):
+            ui, wi = (0, 1) if axis == 0 else (1, 0)
+            ua, wa, ub, wb, uo, wo = P[a, ui], P[a, wi], P[b, ui], P[b, wi], P[o, ui], P[o, wi]
+            d = (-1 if ua < ub else 1) if axis == 0 else (1 if ua < ub else -1)
+            at = (lambda u, w: (w, u)) if axis == 0 else (lambda u, w: (u, w))
+            for u0 in range(max(int(np.ceil(min(ua, ub))), 0), int(min(max(ua, ub), n - 1)) + 1):
+                wx = (wb - wa) / (ub - ua) * (u0 - ua) + wa
+                w_in = int(np.floor(wx) if d > 0 else np.ceil(wx))
+                w_out = w_in + d
+                if not (0 <= w_in < n and 0 <= w_out < n):
+                    continue
+                if fi[at(u0, w_in)] == 0:
+                    out += [(a, b, o, axis, u0, wx, w, False) for w in range(w_out, n if d > 0 else -1, d)]
+                wx2 = (wo - wa) / (uo - ua) * (u0 - ua) + wa if (u0 - ua) * (u0 - uo) < 0 else (wb - wo) / (ub - uo) * (u0 - uo) + wo
+                lim = int(np.ceil(wx2) if d > 0 else np.floor(wx2))
+                out += [(a, b, o, axis, u0, wx, w, w == w_in) for w in range(max(min(w_in, lim), 0), min(max(w_in, lim), n - 1) + 1)
+                        if fi[at(u0, w)] == 0]
+    return out
+
+
+def _edge_margin(T, k, x, y):
+    """signed distance in pixels of pixel centre (x, y) inside edge k (T[k] -> T[k + 1]) of the counter-clockwise triangle T [3,2]"""
+    p, q = T[k], T[(k + 1) % 3]
+    return ((q[0] - p[0]) * (y - p[1]) - (q[1] - p[1]) * (x - p[0])) / np.hypot(*(q - p))
+
+
+def test_the_displacement_rule_moves_the_edge_through_the_pixel():
+    """For every run pixel the rules visit on random front-facing triangles: moving vertex a (or b) along w by the rule's d (eps = 0, float64)
+    puts the line through it and the other vertex on the pixel centre of scan line u0.  For the in run's first pixel (at w_in), re-rasterising
+    (fp32) after 1.01 d drops the pixel from the face and after 0.99 d keeps it -- skipped where the pixel lies within one pixel of the other two
+    edges before or after the move (moving a vertex moves its other edge too) or where d = 0."""
+    n = 32
+    rs = np.random.RandomState(7)
+    lines = flips = 0
+    for _ in range(10):
+        while True:
+            ndc = np.zeros((3, 3), np.float32)
+            ndc[:, :2] = rs.uniform(-0.85, 0.85, (3, 2))
+            ndc[:, 2] = 2.0
+            if R.is_back(ndc):
+                ndc = ndc[[0, 2, 1]]
+            P = 0.5 * (ndc[:, :2].astype(np.float64) * n + n - 1)
+            area = 0.5 * ((P[1, 0] - P[0, 0]) * (P[2, 1] - P[0, 1]) - (P[1, 1] - P[0, 1]) * (P[2, 0] - P[0, 0]))
+            if area > 40:
+                break
+        faces = np.array([[0, 1, 2]])
+        fi = R.rasterize_index(ndc, faces, n)
+        for a, b, o, axis, u0, wx, w, first in _runs(P, fi, n):
+            ui, wi = (0, 1) if axis == 0 else (1, 0)
+            ua, wa, ub, wb = P[a, ui], P[a, wi], P[b, ui], P[b, wi]
+            dw = w - wx
+            if dw == 0:
+                continue
+            for vert, fixed, guard, d in ((a, b, ub != u0, (ub - ua) / (ub - u0) * dw * 2 / n), (b, a, ua != u0, (ub - ua) / (u0 - ua) * dw * 2 / n)):
+                if not guard:
+                    continue
+                Q = P.copy()
+                Q[vert, wi] += d * n / 2                               # d is in NDC: n / 2 pixels per unit
+                (uv, wv), (uf, wf) = (Q[vert, ui], Q[vert, wi]), (Q[fixed, ui], Q[fixed, wi])
+                cross = wv + (wf - wv) * (u0 - uv) / (uf - uv)
+                assert abs(cross - w) <= 1e-9 * max(1.0, abs(w)), (a, b, axis, u0, w, cross)
+                lines += 1
+                if not first:
+                    continue
+                x, y = (u0, w) if axis == 0 else (w, u0)
+                Q11 = P.copy()
+                Q11[vert, wi] += 1.01 * d * n / 2
+                if not all(_edge_margin(T, k, x, y) >= 1.0 for T in (P, Q11) for k in (b, o)):      # edge a -> b is edge a
+                    continue
+                for factor, kept in ((1.01, False), (0.99, True)):
+                    moved = ndc.copy()
+                    moved[vert, 1 - axis] = np.float32(ndc[vert, 1 - axis].astype(np.float64) + factor * d)
+                    assert (R.rasterize_index(moved, faces, n)[y, x] == 0) == kept, (a, b, axis, u0, w, vert, factor, d)
+                flips += 1
+    print("line crossings checked", lines, "in-run pixels re-rasterised", flips)
+    assert lines > 2000 and flips > 100
