@@ -71,6 +71,11 @@ _SIGS = {
     "avc_resize_norm_bwd": (c_int, [P, c_int, c_int, c_int, P, P, P, P]),
     "avc_gen_rays": (c_int, [P, P, P, c_int, c_int, c_float, c_float, c_float, c_int, c_int, c_int, P, P, P, P, P, P, P]),
     "avc_chess_background": (c_int, [P, c_int, c_int, c_int, P, P]),
+    "avc_nearest_point": (c_int, [P, c_int, P, c_int, P, P]),
+    "avc_mesh_components": (c_int, [P, c_int, c_int, P, P]),
+    "avc_mesh_largest_island": (c_int, [P, c_int, c_int, P, P, P, P, P, P]),
+    "avc_mesh_compact": (c_int, [P, P, P, c_int, c_int, P, P, P, P, P, P, P, P]),
+    "avc_skin_apply": (c_int, [P, P, P, c_int, c_int, c_int, P, P]),
 }
 _OPTIONAL = {}
 # experimental entry points of libavc_ring.so (include/avc_ring.h): bound when the loaded library has them

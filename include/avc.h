@@ -321,6 +321,30 @@ int avc_rasterize_mesh_grad(const float* grad_image, const float* ndc, int N, in
                             int S, float eps, const int* vf_ptr, const int* vf_ent, float* face_grad, float* grad_ndc, float* grad_light,
                             void* stream);
 
+/* ---- driving the avatar with a motion (AvatarGen/AppearanceGen/drive.py, generate_animation :308-376; avatarclip_amd/drive.py) ----
+ * M = 0 (or T = 0) is a no-op that returns 0.
+ * avc_nearest_point: find_nearest_ind (drive.py:235-240): idx[m] = argmin_k ((ref[k] - q[m]) ** 2).sum() for q [M,3], ref [K,3] float32,
+ * distances in fp64 with numpy's operation order (subtract, square, (dx^2 + dy^2) + dz^2, no FMA), ties to the lowest k: bit-identical
+ * to the reference's np.argmin.  Inputs are finite. */
+int avc_nearest_point(const float* q, int M, const float* ref, int K, int* idx, void* stream);
+/* cleanup_mesh (drive.py:172-210), the largest island of the triangle-edge graph, in three calls.  Triangles tris [F,3] int32 with a
+ * corner outside [0, NV) are ignored (the caller checks them).
+ * avc_mesh_components: label [NV] = the smallest vertex index of each vertex's connected component (a vertex in no triangle is its own).
+ * avc_mesh_largest_island: the component to keep -- the most vertices, a tie to the smallest label (the reference's BFS order with its
+ * strict `>`) -- as vflag [NV] and tflag [F] (1 = kept, int32); count [NV] int32 and best (one 64-bit word) are scratch.
+ * avc_mesh_compact: with vid / tid = the exclusive prefix sums of vflag / tflag (the caller's scan): v_out [vid[v]] = v [v] (float32 x 3),
+ * c_out [vid[v]] = colors [v] (one 32-bit RGBA word per vertex; colors may be NULL), t_out [tid[f]] = vid[tris[f]]: order kept. */
+int avc_mesh_components(const int* tris, int F, int NV, int* label, void* stream);
+int avc_mesh_largest_island(const int* tris, int F, int NV, const int* label, int* count, unsigned long long* best, int* vflag, int* tflag,
+                            void* stream);
+int avc_mesh_compact(const float* v, const unsigned* colors, const int* tris, int F, int NV, const int* vflag, const int* vid, const int* tflag,
+                     const int* tid, float* v_out, unsigned* c_out, int* t_out, void* stream);
+/* inv_lbs / lbs (drive.py:242-265) with one transform per TEMPLATE vertex: out [T,M,3] with out[t,m] = xf[t, idx[m]] (p[m], 1), where
+ * xf [T,K,12] float32 = rows 0..2 of the 4 x 4 per-template transforms (the inverses for the unposing, T = 1), idx [M] int32 (from
+ * avc_nearest_point), p [M,3].  xf and out 16-byte aligned.  Contract: every idx in [0, K); an index outside writes NaN for that vertex and
+ * reads nothing (avatarclip_amd/drive.py checks idx before the call). */
+int avc_skin_apply(const float* xf, const int* idx, const float* p, int M, int K, int T, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
