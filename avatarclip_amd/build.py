@@ -15,7 +15,7 @@ RING_LIB = os.path.join(HERE, "libavc_ring.so")
 SOURCES = ["avc_core.hip", "avc_mlp_fwd.hip", "avc_mlp_bwd.hip", "avc_wgrad.hip", "avc_rays.hip", "avc_vit.hip", "avc_vit_attn.hip", "avc_vit_gemm.hip", "avc_mcubes.hip", "avc_raster.hip", "avc_raster_grad.hip", "avc_params.hip", "avc_glue.hip", "avc_drive.hip"]
 HEADERS = ["avc_common.h", "avc_stage.h", "avc_mlp.h", "avc_bwd_body.h", "avc_wgrad_body.h", "avc_offsets_gen.h", "avc_raster.h", os.path.join("..", "..", "include", "avc.h"),
            os.path.join("..", "..", "include", "avc_ring.h")]
-FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-comment"] + os.environ.get("AVC_EXTRA_FLAGS", "").split()
+FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-comment"]
 # avc_mlp_fwd.hip holds the one kernel built for ONE wavefront per SIMD on the 512-entry unified register file (mlp_sdf2_kernel, 256-thread
 # workgroups): hipcc then picks the AGPR form of the MFMAs (accumulators in the accumulation half, one v_accvgpr_read per element in front of
 # every epilogue).  The VGPR form keeps the accumulators where the epilogues read them; the kernel puts the ACTIVATIONS into AGPRs itself.

@@ -14,40 +14,15 @@
 // abar_m (x) h_in) -- and passes them to a consumer workgroup of the same XCD through an L2-resident ring.
 #pragma once
 #include "avc_mlp.h"
-#ifndef BWD_G
-#define BWD_G 4   // tiles per staged group (LDS = 2 * G * 16 KiB + table: one 8-wave workgroup per CU)
-#endif
-#ifndef BWD_WPB
-#define BWD_WPB 8   // wavefronts per workgroup: every staged weight tile is shared by 256 points (LDS-DMA fill rate is the scarce resource)
-#endif
-// cache policy of the tile loads: NT = streamed past the caches.  Measured per 4 Mi points (profiles/r03_ab_kernels.txt):
-//   AVC_BWD_E_NT    the h tiles the second-order sweep reads (they are read AGAIN by the reverse sweep ~6 layer steps later):
-//                   normal policy 10.21 ms vs nt 10.43 -> 0
-//   AVC_BWD_RR_NT   the tiles this kernel wrote itself (normal-policy stores) and reads back (gbar_h, ybar[1:]): nt loads 10.43 vs
-//                   normal 10.59 (both switches off: 11.12) -> 1
-#ifndef AVC_BWD_E_NT
-#define AVC_BWD_E_NT 0
-#endif
-#ifndef AVC_BWD_RR_NT
-#define AVC_BWD_RR_NT 1
-#endif
-// Round 5 (the kernel's self-re-reads, 70 tiles per block).  Timing ablations -- results are garbage --
-//   AVC_ABL_BWD_NOEH    the second-order sweep does not load its h tiles (an opaque constant instead): what ANY scheme that removes the
-//                       first of the two h reads (31 tiles) could gain at most
-//   AVC_ABL_BWD_NORR    the reverse sweep does not re-read the tiles this kernel wrote itself (gbar_h 31, ybar[1:] 8 tiles)
-//   AVC_ABL_BWD_RECOMP  NOEH + the price of recomputing h inside the second-order sweep from the staged W_l fragments, priced LOW: a
-//                       second MFMA chain per tile on the same A fragments (one LDS read feeds two MFMAs) + the 16 softplus per lane
-//                       and tile, but NOT the second input array (64 VGPRs) nor the f16 weight set a real version needs
+constexpr int BWD_G = 4;     // tiles per staged group (LDS = 2 * G * 16 KiB + table: one 8-wave workgroup per CU)
+constexpr int BWD_WPB = 8;   // wavefronts per workgroup: every staged weight tile is shared by 256 points (LDS-DMA fill rate is the scarce resource)
+// Cache policy of the tile loads (NT = streamed past the caches), measured per 4 Mi points (profiles/r03_ab_kernels.txt):
+//   the h tiles the second-order sweep reads (they are read AGAIN by the reverse sweep ~6 layer steps later): normal policy 10.21 ms
+//   vs nt 10.43; the tiles this kernel wrote itself (normal-policy stores) and reads back (gbar_h, ybar[1:]): nt loads 10.43 vs normal 10.59.
+// The kernel's self-re-reads (70 tiles per block) were priced in round 5 (profiles/r05_ab_kernels.txt); recomputing h in the
+// second-order sweep instead of reading it did not pay.
 // (gbar_hs -- the last tiles the second-order sweep produces, the first the reverse sweep consumes -- ALWAYS stays in registers across
 //  the turn: it has no panel since round 5, see col_sums below; keeping h_s as well spilled 78 registers and lost 5 %)
-template <typename V>
-__device__ __forceinline__ FragPair<V> abl_const_pair() {
-  FragPair<V> d;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) { d.a0[j] = (typename MF<V>::S)0.75f; d.a1[j] = (typename MF<V>::S)1.25f; }
-  asm volatile("" : "+v"(d.a0), "+v"(d.a1));
-  return d;
-}
 
 template <typename P> __device__ __forceinline__ P launder(P p) {
   asm volatile("" : "+s"(p));
@@ -131,18 +106,10 @@ __device__ __forceinline__ float transpose_sum(const float (&v)[NV], int lane) {
 // read + write: the slot has a single writer, this wavefront.
 template <class N, int NV>
 __device__ __forceinline__ void col_sums(cs_slot_t slot, int lane, int base, const float (&v)[NV]) {
-#ifdef AVC_ABL_CS_NODPP
-  const float total = v[0];
-#else
   const float total = transpose_sum<NV>(v, lane);
-#endif
   const bool writer = (lane & 31) < NV;
   cs_slot_t dst = writer ? slot + base + (lane & (NV - 1)) : slot + PanelLayout<N>::CS_FLOATS + (lane & 63);
-#ifdef AVC_ABL_CS_NOADD
-  asm volatile("" :: "v"(total), "v"(dst));
-#else
   *dst = *dst + total;
-#endif
 }
 template <class N>
 __device__ __forceinline__ cs_slot_t cs_init(char* lds_base, int wv, int lane) {
@@ -158,11 +125,9 @@ __device__ __forceinline__ void cs_flush(cs_slot_t slot, float* out, long row, i
 }
 
 // The inputs the FIRST MFMA chain and the first epilogues of a block wait for: delta_o (from d_rgb and the forward's colours) and the
-// ReLU masks.  AVC_BWD_PIPE_IN=1: the persistent kernel requests them for its NEXT block under the last layer of the current one
-// (loop-carried, 20 VGPRs) instead of at the top of the block, where all eight wavefronts sit out one exposed HBM round trip.
-#ifndef AVC_BWD_PIPE_IN
-#define AVC_BWD_PIPE_IN 1   // (profiles/r05_ab_kernels.txt: 9.81 -> 9.48 ms per 4 Mi points)
-#endif
+// ReLU masks.  The persistent kernel requests them for its NEXT block under the last layer of the current one (loop-carried, 20 VGPRs)
+// instead of at the top of the block, where all eight wavefronts sit out one exposed HBM round trip
+// (profiles/r05_ab_kernels.txt: 9.81 -> 9.48 ms per 4 Mi points).
 template <class N> struct BlkIn { b8 dof; unsigned m1[N::HT], m2[N::HT]; float dn[3], dsdf; };   // (+ the cotangents d_normal, d_sdf: used mid-block, behind barriers no load can be hoisted over)
 template <class N>
 __device__ __forceinline__ void load_blk_in(const BwdArgs& a, long blk, long nblk, int lane, BlkIn<N>& bi) {
@@ -253,14 +218,14 @@ __device__ __forceinline__ void bwd_sweeps(StageT<BWD_G>& sg, const BwdArgs& a, 
     b8 dl[N::HK];
     b8 d1[N::HK];
     if constexpr (N::NCMID == 1) {
-      layer_s<b8, 1, N::HT>(sg, Wb, o.v[OFF_CHT], nxt<N, OFF_CM0T>(sg, Wb, o), dof, AVC_RELU_BWD(dl, m2, L::G_D2));
-      layer_s<b8, N::HK, N::HT>(sg, Wb, o.v[OFF_CM0T], nxt<N, OFF_C0T>(sg, Wb, o), dl, AVC_RELU_BWD(d1, m1, L::G_D1));
+      layer_s1<b8, 1, N::HT>(sg, Wb, o.v[OFF_CHT], nxt<N, OFF_CM0T>(sg, Wb, o), dof, AVC_RELU_BWD(dl, m2, L::G_D2));
+      layer_s1<b8, N::HK, N::HT>(sg, Wb, o.v[OFF_CM0T], nxt<N, OFF_C0T>(sg, Wb, o), dl, AVC_RELU_BWD(d1, m1, L::G_D1));
     } else {
-      layer_s<b8, 1, N::HT>(sg, Wb, o.v[OFF_CHT], nxt<N, OFF_C0T>(sg, Wb, o), dof, AVC_RELU_BWD(d1, m1, L::G_D1));
+      layer_s1<b8, 1, N::HT>(sg, Wb, o.v[OFF_CHT], nxt<N, OFF_C0T>(sg, Wb, o), dof, AVC_RELU_BWD(d1, m1, L::G_D1));
     }
     // d r0 = C0^T delta1: HT feature tiles (ybar[1:], kept for the reverse sweep), then the [x,n] tile (rows 3,4,5 = d n)
     float dn_acc[3] = {0.f, 0.f, 0.f};
-    layer_s<b8, N::HK, N::HT + 1>(sg, Wb, o.v[OFF_C0T], nxt<N, OFF_W0G>(sg, Wb, o), d1, AVC_EPI(
+    layer_s1<b8, N::HK, N::HT + 1>(sg, Wb, o.v[OFF_C0T], nxt<N, OFF_W0G>(sg, Wb, o), d1, AVC_EPI(
       if (t < N::HT) {
         b8 f0, f1;
         _Pragma("unroll") for (int j = 0; j < 8; ++j) { f0[j] = (__bf16)acc[j]; f1[j] = (__bf16)acc[8 + j]; }
@@ -297,11 +262,7 @@ __device__ __forceinline__ void bwd_sweeps(StageT<BWD_G>& sg, const BwdArgs& a, 
   auto load_dfeat = [&]() __attribute__((always_inline)) {
 #pragma unroll
     for (int t = 0; t < N::HT; ++t) {
-#ifdef AVC_ABL_BWD_NORR
-      const FragPair<b8> d = abl_const_pair<b8>();
-#else
-      const FragPair<b8> d = tile_load<(AVC_BWD_RR_NT != 0), b8>(tiles, L::G_DFEAT + t);
-#endif
+      const FragPair<b8> d = tile_load<true, b8>(tiles, L::G_DFEAT + t);
       dfeat[2 * t] = d.a0;
       dfeat[2 * t + 1] = d.a1;
     }
@@ -329,11 +290,7 @@ __device__ __forceinline__ void bwd_sweeps(StageT<BWD_G>& sg, const BwdArgs& a, 
     tile_store<false>(tiles, L::G_GB0, gb0[0], gb0[1]);
     tile_store<false>(tiles, L::G_GB0 + 1, gb0[2], zero_frag<b8>());
     // gbar_a = W gbar_h(in); gbar_h(out) = gbar_a * sigma(h_out)
-#if defined(AVC_ABL_BWD_NOEH) || defined(AVC_ABL_BWD_RECOMP)
-#define AVC_E_LOADH(PH) abl_const_pair<h8>()
-#else
-#define AVC_E_LOADH(PH) tile_load<(AVC_BWD_E_NT != 0), h8>(ftiles, (PH) + t)
-#endif
+#define AVC_E_LOADH(PH) tile_load<false, h8>(ftiles, (PH) + t)
 #define AVC_SECOND(OUT, PH, PT)                                                                              \
   AVC_PRE(return AVC_E_LOADH(PH);),                                                                          \
   AVC_EPID(FragPair<h8>, _Pragma("unroll") for (int j = 0; j < 8; ++j) {                                     \
@@ -353,28 +310,24 @@ __device__ __forceinline__ void bwd_sweeps(StageT<BWD_G>& sg, const BwdArgs& a, 
           pin2(OUT[2 * t], OUT[2 * t + 1]);                                                                  \
           col_sums<N, 16>(cs, lane, (t * 2 + h) * 16, v);)
     b8 gb1[N::HK];
-    layer_sqd<b8, 3, N::HT>(sg, Wb, o.v[OFF_W0G], nxt<N, OFF_WM0>(sg, Wb, o), gb0, AVC_SECOND(gb1, L::P_H1, L::G_GBH1));
+    layer_sq1<b8, 3, N::HT>(sg, Wb, o.v[OFF_W0G], nxt<N, OFF_WM0>(sg, Wb, o), gb0, AVC_SECOND(gb1, L::P_H1, L::G_GBH1));
     b8 gbm[N::HK];
     if constexpr (N::NMID == 2) {
-      layer_sqd<b8, N::HK, N::HT>(sg, Wb, o.v[OFF_WM0], nxt<N, OFF_WM1>(sg, Wb, o), gb1, AVC_SECOND(gbm, L::P_HM, L::G_GBHM));
+      layer_sq1<b8, N::HK, N::HT>(sg, Wb, o.v[OFF_WM0], nxt<N, OFF_WM1>(sg, Wb, o), gb1, AVC_SECOND(gbm, L::P_HM, L::G_GBHM));
       b8 gbm1[N::HK];
-      layer_sqd<b8, N::HK, N::HT>(sg, Wb, o.v[OFF_WM1], nxt<N, OFF_WS>(sg, Wb, o), gbm,
+      layer_sq1<b8, N::HK, N::HT>(sg, Wb, o.v[OFF_WM1], nxt<N, OFF_WS>(sg, Wb, o), gbm,
                                   AVC_SECOND(gbm1, L::P_HM + N::HT, L::G_GBHM + N::HT));
-      layer_sqd<b8, N::HK, N::ST>(sg, Wb, o.v[OFF_WS], nxt<N, OFF_WLT>(sg, Wb, o), gbm1, AVC_SECOND_S(gbs, L::P_HS));
+      layer_sq1<b8, N::HK, N::ST>(sg, Wb, o.v[OFF_WS], nxt<N, OFF_WLT>(sg, Wb, o), gbm1, AVC_SECOND_S(gbs, L::P_HS));
     } else {
-      layer_sqd<b8, N::HK, N::HT>(sg, Wb, o.v[OFF_WM0], nxt<N, OFF_WS>(sg, Wb, o), gb1, AVC_SECOND(gbm, L::P_HM, L::G_GBHM));
-      layer_sqd<b8, N::HK, N::ST>(sg, Wb, o.v[OFF_WS], nxt<N, OFF_WLT>(sg, Wb, o), gbm, AVC_SECOND_S(gbs, L::P_HS));
+      layer_sq1<b8, N::HK, N::HT>(sg, Wb, o.v[OFF_WM0], nxt<N, OFF_WS>(sg, Wb, o), gb1, AVC_SECOND(gbm, L::P_HM, L::G_GBHM));
+      layer_sq1<b8, N::HK, N::ST>(sg, Wb, o.v[OFF_WS], nxt<N, OFF_WLT>(sg, Wb, o), gbm, AVC_SECOND_S(gbs, L::P_HS));
     }
   }
   // ------------------------------------------------------------------ phase F: reverse sweep (ii) (bf16)
   {
     b8 as_[N::SK];
     load_dfeat();
-#ifdef AVC_ABL_BWD_NORR
-#define AVC_F_LOADB(PB) abl_const_pair<b8>()
-#else
-#define AVC_F_LOADB(PB) tile_load<(AVC_BWD_RR_NT != 0), b8>(tiles, (PB) + t)
-#endif
+#define AVC_F_LOADB(PB) tile_load<true, b8>(tiles, (PB) + t)
 #define AVC_LOAD3(PH, PB, PG)                                                                               \
   AVC_PRE(PF3 d; { const FragPair<h8> a_ = tile_load<true, h8>(ftiles, (PH) + t); d.h0 = a_.a0; d.h1 = a_.a1; } \
           { const FragPair<b8> a_ = AVC_F_LOADB(PB); d.b0 = a_.a0; d.b1 = a_.a1; } \
@@ -385,7 +338,7 @@ __device__ __forceinline__ void bwd_sweeps(StageT<BWD_G>& sg, const BwdArgs& a, 
           d.b0 = gbs[2 * t]; d.b1 = gbs[2 * t + 1];                                                          \
           { const FragPair<h8> a_ = tile_load<true, h8>(ftiles, (PG) + t); d.g0 = a_.a0; d.g1 = a_.a1; } return d;)
     // ubar[:SKIP]/sqrt2 = (W_last[1:,:]^T dfeat + W_last[0,:] d_sdf)/sqrt2 ; 1/sqrt2 is folded into both packs
-    layer_sq<b8, N::HK, N::ST>(sg, Wb, o.v[OFF_WLT], nxt<N, OFF_WST>(sg, Wb, o), dfeat,
+    layer_sq1<b8, N::HK, N::ST>(sg, Wb, o.v[OFF_WLT], nxt<N, OFF_WST>(sg, Wb, o), dfeat,
       AVC_LOAD3_S(L::P_HS, L::P_GAS), AVC_EPID(PF3,
       float wa[16];
       load16(T + o.v[OFF_WL0_ACC], t, h, wa);
@@ -413,18 +366,18 @@ __device__ __forceinline__ void bwd_sweeps(StageT<BWD_G>& sg, const BwdArgs& a, 
     // ... and, in the persistent kernel, the next block's delta_o and masks (issued after the first group barrier of the last layer)
 #define AVC_F_LASTHOOK AVC_HOOK(if constexpr (PIPE) load_blk_in<N>(a, blk0_next + wv, nblk, lane, *bip);)
     if constexpr (N::NMID == 2) {
-      layer_sq<b8, N::SK, N::HT>(sg, Wb, o.v[OFF_WST], nxt<N, OFF_WM1T>(sg, Wb, o), as_,
+      layer_sq1<b8, N::SK, N::HT>(sg, Wb, o.v[OFF_WST], nxt<N, OFF_WM1T>(sg, Wb, o), as_,
                                  AVC_REVERSE(am, L::P_HM + N::HT, L::G_GBHM + N::HT, L::P_GAM + N::HT, L::G_ABM + N::HT, R::on));
       if constexpr (R::on) ring.template handoff<N>(1, am, blk0, lane, wv);
-      layer_sq<b8, N::HK, N::HT>(sg, Wb, o.v[OFF_WM1T], nxt<N, OFF_WM0T>(sg, Wb, o), am,
+      layer_sq1<b8, N::HK, N::HT>(sg, Wb, o.v[OFF_WM1T], nxt<N, OFF_WM0T>(sg, Wb, o), am,
                                  AVC_REVERSE(am0, L::P_HM, L::G_GBHM, L::P_GAM, L::G_ABM, R::on));
       if constexpr (R::on) ring.template handoff<N>(0, am0, blk0, lane, wv);
-      layer_sq<b8, N::HK, N::HT>(sg, Wb, o.v[OFF_WM0T], first, am0, AVC_REVERSE(am, L::P_H1, L::G_GBH1, L::P_GA1, L::G_AB1, false), AVC_F_LASTHOOK);
+      layer_sq1<b8, N::HK, N::HT>(sg, Wb, o.v[OFF_WM0T], first, am0, AVC_REVERSE(am, L::P_H1, L::G_GBH1, L::P_GA1, L::G_AB1, false), AVC_F_LASTHOOK);
     } else {
-      layer_sq<b8, N::SK, N::HT>(sg, Wb, o.v[OFF_WST], nxt<N, OFF_WM0T>(sg, Wb, o), as_,
+      layer_sq1<b8, N::SK, N::HT>(sg, Wb, o.v[OFF_WST], nxt<N, OFF_WM0T>(sg, Wb, o), as_,
                                  AVC_REVERSE(am, L::P_HM, L::G_GBHM, L::P_GAM, L::G_ABM, R::on));
       if constexpr (R::on) ring.template handoff<N>(0, am, blk0, lane, wv);
-      layer_sq<b8, N::HK, N::HT>(sg, Wb, o.v[OFF_WM0T], first, am, AVC_REVERSE(am0, L::P_H1, L::G_GBH1, L::P_GA1, L::G_AB1, false), AVC_F_LASTHOOK);
+      layer_sq1<b8, N::HK, N::HT>(sg, Wb, o.v[OFF_WM0T], first, am, AVC_REVERSE(am0, L::P_H1, L::G_GBH1, L::P_GA1, L::G_AB1, false), AVC_F_LASTHOOK);
     }
   }
 #undef AVC_RELU_BWD

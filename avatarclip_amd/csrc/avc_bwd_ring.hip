@@ -35,19 +35,10 @@
 #define RC_XCD_LINES (3 + RING_NTY_MAX)
 #define RC_SLOT0 (RC_XCD + 8 * RC_XCD_LINES * RC_LINE)   // per (xcd, type, slot): one line {arrive, freed, meta}
 #define RC_WORDS (RC_SLOT0 + 8 * RING_NTY_MAX * RING_NS_MAX * RC_LINE)
-#ifndef RING_SPIN_LIMIT
-#define RING_SPIN_LIMIT (1 << 21)                   // polls (~0.3 us each with the sleep): ~0.6 s
-#endif
-// timing / counter experiments only (the products are garbage): 1 = the consumer takes its forward-type operand from the ring slot too
-// (the abar tiles a second time) instead of from the F region in HBM -- a consumer that never waits for HBM; 2 = the producer
-// additionally writes a second copy of its tiles into the slot (what handing BOTH operands through the ring would cost it)
-#ifndef RING_EXP_B
-#define RING_EXP_B 0
-#endif
-#define RING_UNIT_TILES(HT) ((RING_EXP_B == 2 ? 2 : 1) * (HT))   // tiles per wavefront and hand-off unit
-#ifndef RING_DMA_AUX
-#define RING_DMA_AUX 16                             // sc1: device scope -- the copy is served by the XCD's L2, never by this CU's L1
-#endif
+constexpr unsigned RING_SPIN_LIMIT = 1 << 21;       // polls (~0.3 us each with the sleep): ~0.6 s
+constexpr int RING_DMA_AUX = 16;                    // sc1: device scope -- the copy is served by the XCD's L2, never by this CU's L1
+// (a hand-off unit holds HT tiles per wavefront; handing BOTH operands of a product through the ring was priced in
+// profiles/r04_ring_handoff.md)
 
 struct RingParams {
   unsigned* ctl;          // RC_WORDS u32, zeroed by the launcher
@@ -116,10 +107,9 @@ struct RingProd {
     }
     __syncthreads();
     const unsigned slot = __builtin_amdgcn_readfirstlane(s_w[0]);
-    char* dst = rp.ring + ((((long)xcd * rp.ntypes + type) * rp.nslots + slot) * BWD_WPB + wv) * (long)(RING_UNIT_TILES(N2::HT) * 2048);
+    char* dst = rp.ring + ((((long)xcd * rp.ntypes + type) * rp.nslots + slot) * BWD_WPB + wv) * (long)(N2::HT * 2048);
     const PanelPtr pp = panel_ptr(dst, lane);
     tiles_store<true, N2::HT>(pp, 0, f);             // plain stores: the lines stay in this XCD's write-back L2
-    if (RING_EXP_B == 2) tiles_store<true, N2::HT>(pp, N2::HT, f);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // ... and are there now
     if (lane == 0) __hip_atomic_fetch_add(slot_line(rp, xcd, type, slot), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (threadIdx.x == 0) t_hand += wall_clock64() - t0;
@@ -146,7 +136,7 @@ __device__ __forceinline__ void ring_consumer(char* lds, const RingParams& rp, c
   const unsigned ns = (unsigned)rp.nslots;
   const char* const fbase = a.fpanels + (long)rp.pb[type] * 2048;
   const long fstride = (long)L::P_TILES * 2048;
-  constexpr int UT = RING_UNIT_TILES(TA);
+  constexpr int UT = TA;   // tiles per wavefront and hand-off unit
   const char* const rbase = rp.ring + (((long)xcd * rp.ntypes + type) * rp.nslots) * (long)(BWD_WPB * UT * 2048);
   facc acc[NI * NK];
 #pragma unroll
@@ -188,9 +178,8 @@ __device__ __forceinline__ void ring_consumer(char* lds, const RingParams& rp, c
       for (int c = wv; c < nchunk; c += 8) {
         const int tix = c >> 1;
         char* dst = lds + s * slot_bytes + c * 1024;
-        if (tix < TA || RING_EXP_B != 0) {
-          const int rt = tix < TA ? tix : (RING_EXP_B == 2 ? tix : tix - TA);
-          const char* g = ra + ((long)j * UT + rt) * 2048 + (src_lo + (c & 1) * 16) * 16;
+        if (tix < TA) {
+          const char* g = ra + ((long)j * UT + tix) * 2048 + (src_lo + (c & 1) * 16) * 16;
           __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g, (__attribute__((address_space(3))) void*)dst, 16, 0, RING_DMA_AUX);
         } else {
           const char* g = fbase + (blk0 + j) * fstride + (long)(tix - TA) * 2048 + (src_lo + (c & 1) * 16) * 16;
@@ -278,6 +267,7 @@ __global__ __launch_bounds__(64 * BWD_WPB) void mlp_bwd_ring_kernel(BwdArgs a, R
   extern __shared__ __attribute__((aligned(16))) char lds[];
   __shared__ unsigned s_w[6];   // [0] hand-off slot, [1] abort seen, [2] role ticket / first group, [3] unused, [4], [5] next group (double buffered)
   typedef StageT<BWD_G> ST;
+  static_assert(BWD_WPB >= 4 && BWD_WPB % 4 == 0, "stage_issue's turns need a multiple of 4 wavefronts per workgroup");
   constexpr AvcOffsets o = Off<N>::value;
   const int xcd = xcc_id();
   if (threadIdx.x == 0) {
@@ -328,7 +318,7 @@ __global__ __launch_bounds__(64 * BWD_WPB) void mlp_bwd_ring_kernel(BwdArgs a, R
 extern "C" long avc_bwd_ring_ctl_bytes(void) { return (long)RC_WORDS * 4; }
 extern "C" long avc_bwd_ring_payload_bytes(int net, int ntypes, int nslots) {
   const int ht = net == AVC_NET_FULL ? NetFull::HT : NetSmall::HT;
-  return 8L * ntypes * nslots * BWD_WPB * RING_UNIT_TILES(ht) * 2048;
+  return 8L * ntypes * nslots * BWD_WPB * ht * 2048;
 }
 extern "C" int avc_bwd_ring_types(int net) { return net == AVC_NET_FULL ? NetFull::NMID : NetSmall::NMID; }
 

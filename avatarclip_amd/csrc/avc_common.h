@@ -100,16 +100,8 @@ template <typename T> __device__ __forceinline__ AVC_GLOBAL T* as_global(T* p) {
 
 // Streaming traffic (parked activations, weight-gradient panels): written once, read once or a few times much later, far larger
 // than the 4 MB L2 of an XCD.  Non-temporal accesses keep it from evicting the packed weights every workgroup re-reads.
-#ifndef AVC_NO_NT_STORE
 #define AVC_NT_STORE(v, p) __builtin_nontemporal_store((v), (p))
-#else
-#define AVC_NT_STORE(v, p) (*(p) = (v))
-#endif
-#ifndef AVC_NO_NT_LOAD
 #define AVC_NT_LOAD(p) __builtin_nontemporal_load((p))
-#else
-#define AVC_NT_LOAD(p) (*(p))
-#endif
 
 // packed per-tile fp32 table [tile][half][16] -> this lane's 16 values
 __device__ __forceinline__ void load16(const float* __restrict__ tab, int t, int h, float (&out)[16]) {
@@ -158,71 +150,24 @@ __device__ __forceinline__ void load8(const float* __restrict__ tab, int s, int 
 // canonicalisation (the bias add used to provide it for free); v_med3_f32(t, 0, 3e38) needs none.  (NOT inline asm: the hazard
 // recogniser does not look inside an asm, and a VALU read of an MFMA result without the wait states it inserts returns the
 // previous contents of the first result registers -- seen as 12 wrong columns in the last tile of a layer.)
-#ifndef AVC_SOFTPLUS_DIRECT
-#define AVC_SOFTPLUS_DIRECT 1
-#endif
 __device__ __forceinline__ float relu_raw(float t) { return __builtin_amdgcn_fmed3f(t, 0.f, 3.0e38f); }   // (a finite bound: +inf folds back to fmaxnum)
 __device__ __forceinline__ float softplus2(float t) {
   // H = S * Softplus_beta100(t / S)  (nn.Softplus(beta=100), fields.py:68) in base-2 units; raw v_exp_f32 / v_log_f32
-#ifdef AVC_ABL_CHEAPACT   // timing ablation only (what the transcendentals cost)
-  return fmaxf(t, 0.f);
-#endif
-#if AVC_SOFTPLUS_DIRECT
   // H = log2(1 + 2^t) as written -- v_exp, v_add, v_log -- plus ONE v_med3 that repairs the only range where that fails: 2^t
   // overflows for t >= 128, the logarithm returns +inf, and the median of (+inf, t, 128) is t (= H to fp32 precision there); below,
-  // t <= L <= max(t, 0) + 1 <= 128 makes L the median.  2 plain + 2 transcendental instructions per element; the split form below
-  // (max(t, 0) + log2(1 + 2^-|t|)) needs 3 + 2, and plain VALU issue is what these kernels are short of.
+  // t <= L <= max(t, 0) + 1 <= 128 makes L the median.  2 plain + 2 transcendental instructions per element; the split form
+  // max(t, 0) + log2(1 + 2^-|t|) needs 3 + 2, and plain VALU issue is what these kernels are short of.
   // Very negative t: 2^t underflows to 0, L = 0 (true value 2^t log2 e < 2^-126).  Absolute error vs the split form <= 1 ulp of fp32.
   const float L = __builtin_amdgcn_logf(1.f + __builtin_amdgcn_exp2f(t));
   return __builtin_amdgcn_fmed3f(L, t, 128.f);
-#else
-  const float e = __builtin_amdgcn_exp2f(-fabsf(t));
-  return relu_raw(t) + __builtin_amdgcn_logf(1.f + e);
-#endif
 }
-// softplus2 of a whole accumulator tile.  AVC_SOFTPLUS_PK=1 (experiment): the "1 + 2^t" adds on register PAIRS
-// (v_pk_add_f32) -- 8 instead of 16 plain adds per tile; MI355X_MICROARCH.md prices a packed-f32 op beside MFMAs at ~13 cycles MORE than
-// the two scalar ops it replaces, which is what profiles/r05_ab_kernels.txt measures.
-#ifndef AVC_SOFTPLUS_PK
-#define AVC_SOFTPLUS_PK 0
-#endif
-typedef float f2v __attribute__((ext_vector_type(2)));
+// softplus2 of a whole accumulator tile.  (The "1 + 2^t" adds on register pairs, v_pk_add_f32, measured slower: a packed-f32 op beside
+// MFMAs costs more than the two scalar ops it replaces, profiles/r05_ab_kernels.txt.)
 template <typename A>
 __device__ __forceinline__ void softplus2_tile(const A& acc, float (&a)[16]) {
-#if AVC_SOFTPLUS_PK && AVC_SOFTPLUS_DIRECT && !defined(AVC_ABL_CHEAPACT)
-#pragma unroll
-  for (int r = 0; r < 16; r += 2) {
-    f2v e = {__builtin_amdgcn_exp2f(acc[r]), __builtin_amdgcn_exp2f(acc[r + 1])};
-    const f2v one = {1.f, 1.f};
-    e = e + one;
-    asm("" : "+v"(e));   // keep the pair together: the add stays ONE packed instruction
-    a[r] = __builtin_amdgcn_fmed3f(__builtin_amdgcn_logf(e[0]), acc[r], 128.f);
-    a[r + 1] = __builtin_amdgcn_fmed3f(__builtin_amdgcn_logf(e[1]), acc[r + 1], 128.f);
-  }
-#else
 #pragma unroll
   for (int r = 0; r < 16; ++r) a[r] = softplus2(acc[r]);
-#endif
 }
-// The same activation evaluated AFTER the f16 conversion the next layer's operand needs anyway (experiment, AVC_SDF_F16_ACT; VERDICT r3
-// item 6): v_cvt_pk_f16_f32, v_exp_f16, v_pk_add_f16, v_log_f16 and the overflow repair as v_pk_max_f16 / v_pk_min_f16 -- H = min(log2(1 +
-// 2^t), max(t, 16)): 2^t overflows f16 from t = 16 on, the logarithm then returns +inf and max(t, 16) = t is the minimum; below, L <= 16 <=
-// max(t, 16).  2.0 plain VALU instructions per element instead of 2.5; the price is a second rounding (of t) in front of the operand's.
-typedef _Float16 h2v __attribute__((ext_vector_type(2)));
-template <typename A>
-__device__ __forceinline__ void softplus_frags_f16(const A& acc, h8& f0, h8& f1) {
-#pragma unroll
-  for (int j = 0; j < 8; ++j) { f0[j] = (_Float16)acc[j]; f1[j] = (_Float16)acc[8 + j]; }
-  const h8 one = {1, 1, 1, 1, 1, 1, 1, 1}, cap = {16, 16, 16, 16, 16, 16, 16, 16};
-  h8 l0 = __builtin_elementwise_log2(__builtin_elementwise_exp2(f0) + one);
-  h8 l1 = __builtin_elementwise_log2(__builtin_elementwise_exp2(f1) + one);
-  f0 = __builtin_elementwise_min(l0, __builtin_elementwise_max(f0, cap));
-  f1 = __builtin_elementwise_min(l1, __builtin_elementwise_max(f1, cap));
-  asm volatile("" : "+v"(f0), "+v"(f1));
-}
-#ifndef AVC_SDF_F16_ACT
-#define AVC_SDF_F16_ACT 0
-#endif
 // sigma(beta a) recovered from H = S * softplus(a):  1 - 2^-H
 __device__ __forceinline__ float sig_from_h(float H) { return 1.f - __builtin_amdgcn_exp2f(-H); }
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + __expf(-x)); }

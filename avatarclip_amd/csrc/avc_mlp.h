@@ -27,25 +27,6 @@ template <class N> static inline bool offsets_match(const int* offs) {
   return true;
 }
 
-// Static issue priority per wavefront (s_setprio once, before the main loop).  The wavefronts w, w + 4 (, w + 8) of a workgroup share a
-// SIMD and run the same instruction sequence between the same barriers; between equals the arbiter prefers the OLDER wave, i.e. the
-// later-dispatched ones lose every contested VALU slot.  AVC_WAVE_PRIO: 0 = leave it to age, 1 = the younger half of the workgroup
-// at priority 1, 2 = priority w / 4, 3 = the older half at priority 1.  (Measured: profiles/r03_ab_kernels.txt.)
-#ifndef AVC_WAVE_PRIO
-#define AVC_WAVE_PRIO 0
-#endif
-__device__ __forceinline__ void avc_static_wave_priority() {
-#if AVC_WAVE_PRIO == 1
-  if ((threadIdx.x >> 6) >= (blockDim.x >> 7)) __builtin_amdgcn_s_setprio(1);
-#elif AVC_WAVE_PRIO == 2
-  const int q = threadIdx.x >> 8;
-  if (q == 1) __builtin_amdgcn_s_setprio(1);
-  if (q >= 2) __builtin_amdgcn_s_setprio(2);
-#elif AVC_WAVE_PRIO == 3
-  if ((threadIdx.x >> 6) < (blockDim.x >> 7)) __builtin_amdgcn_s_setprio(1);
-#endif
-}
-
 struct PointSrc {
   const float* pts;      // [N,3] or nullptr -> ray mode
   const float* rays_o;   // [R,3]
@@ -105,26 +86,10 @@ __device__ __forceinline__ Next no_next() { Next n; n.ptr = nullptr; n.chunks = 
 // ---- are issued before the epilogue of tile t-1, so the VALU / transcendental / store work of one tile hides under the
 // ---- matrix pipe of the next (same basic block, no barrier between).
 // The two wavefronts of a SIMD (waves w and w+4 of the workgroup) leave every group barrier together and would run their MFMA
-// chains at the same time and their VALU epilogues at the same time (matrix pipe idle during the epilogues).  Holding the
-// second wave back by about half a tile step lets one wave's epilogue run under the other's MFMA chain.
-#ifdef AVC_ABL_NOSYNC   // timing ablation only
-#define AVC_SYNC() do {} while (0)
-#elif defined(AVC_EXP_SYNC)   // timing experiment only (results are garbage): group barrier that leaves AVC_EXP_SYNC VMEM ops in flight
-#define AVC_STR2(x) #x
-#define AVC_STR(x) AVC_STR2(x)
-#define AVC_SYNC() do { asm volatile("s_waitcnt vmcnt(" AVC_STR(AVC_EXP_SYNC) ") lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_s_barrier(); } while (0)
-#else
+// chains at the same time and their VALU epilogues at the same time (matrix pipe idle during the epilogues).  (Holding the
+// second wave back by about half a tile step with s_sleep, and a static s_setprio per wavefront, were measured and did not pay:
+// profiles/r03_ab_kernels.txt.)
 #define AVC_SYNC() __syncthreads()
-#endif
-#ifndef AVC_DEPHASE
-#define AVC_DEPHASE 0   // s_sleep units (64 cycles); 0 = off
-#endif
-template <class ST>
-__device__ __forceinline__ void dephase(const ST& st) {
-  if (AVC_DEPHASE > 0) {
-    if (st.wave >= (st.nw >> 1)) __builtin_amdgcn_s_sleep(AVC_DEPHASE);
-  }
-}
 #define AVC_EPI(...) [&](int t, const facc& acc) __attribute__((always_inline)) { __VA_ARGS__ }
 // Optional hook run once per layer right AFTER the barrier of its first weight group: the place for streaming stores of the
 // previous layer's output tiles (still live as this layer's input).  hipcc drains vmcnt(0) before every group barrier while an
@@ -132,38 +97,27 @@ __device__ __forceinline__ void dephase(const ST& st) {
 // workgroup for an HBM write round trip; issued right after one it has a group of MFMA work (~2 us) to complete under.
 struct NoHook { __device__ __forceinline__ void operator()() const {} };
 #define AVC_HOOK(...) [&]() __attribute__((always_inline)) { __VA_ARGS__ }
-// a hook that spreads its stores over the layer's weight groups: called after EVERY group barrier with (g, number of groups) and
-// stores the g-th share of its tiles (tiles_store_part) -- bursts of 4 instead of 8 tile stores per barrier interval
+// a hook that spreads its stores over the layer's tile steps: called with (t, number of tiles) and stores the t-th share of its
+// tiles (tiles_store_part)
 #define AVC_HOOKG(...) [&](int grp_, int ngrp_) __attribute__((always_inline)) { __VA_ARGS__ }
-// AVC_STORE_PER_TILE=1 (round 5): a spreading hook is called once per output-TILE step with (t, NT) instead of once per weight group
-// with (g, NG): its tile stores go out one tile (2 KiB per wavefront, 16 KiB per workgroup) at a time, each under ~500 cycles of
-// MFMA work, instead of in bursts of 4 tiles behind a barrier (64 KiB per workgroup against a store path of 64 B/clk: the waves then sit
-// on VMEM back-pressure).  One-shot hooks (AVC_HOOK) still run once, after the first barrier.
-#ifndef AVC_STORE_PER_TILE
-#define AVC_STORE_PER_TILE 1   // (profiles/r05_ab_kernels.txt: training forward 7.51 -> 7.45 ms, plain forward 5.88 -> 5.82 ms per 4 Mi points)
-#endif
+// A spreading hook is called once per output-TILE step with (t, NT), not once per weight group: its tile stores go out one tile (2 KiB
+// per wavefront, 16 KiB per workgroup) at a time, each under ~500 cycles of MFMA work, instead of in bursts of 4 tiles behind a barrier
+// (64 KiB per workgroup against a store path of 64 B/clk: the waves then sit on VMEM back-pressure).  profiles/r05_ab_kernels.txt:
+// training forward 7.51 -> 7.45 ms, plain forward 5.88 -> 5.82 ms per 4 Mi points.  One-shot hooks (AVC_HOOK) run once, after the
+// first barrier.
 template <typename Hook>
-__device__ __forceinline__ void hook_call(Hook&& hook, int g, int ng) {
-  if constexpr (std::is_invocable_v<Hook, int, int>) { if (!AVC_STORE_PER_TILE) hook(g, ng); }
-  else if (g == 0) hook();
+__device__ __forceinline__ void hook_call(Hook&& hook, int g) {
+  if constexpr (!std::is_invocable_v<Hook, int, int>) { if (g == 0) hook(); }
 }
 template <typename Hook>
 __device__ __forceinline__ void hook_tile(Hook&& hook, int t, int nt) {
-  if constexpr (std::is_invocable_v<Hook, int, int>) { if (AVC_STORE_PER_TILE) hook(t, nt); }
+  if constexpr (std::is_invocable_v<Hook, int, int>) hook(t, nt);
 }
 
-#ifndef AVC_PAIR
-#define AVC_PAIR 0   // 1: two output tiles per MFMA stream (independent accumulators), 0: one dependent chain per tile
-#endif
-#ifndef AVC_PAIR_SQ
-#define AVC_PAIR_SQ AVC_PAIR   // the same for the layers whose epilogues read panel tiles back (layer_sq: normal sweep of the forward)
-#endif
-#ifndef AVC_PAIR_L2
-#define AVC_PAIR_L2 AVC_PAIR   // ... and for the layers with a split K dimension (layer2_s: feature layer, first colour layer)
-#endif
 // PAIRED = two output tiles per MFMA stream.  Measured per 4 Mi points (profiles/r03_ab_kernels.txt): forward 6.16 -> 6.01 ms and
 // training forward 8.25 -> 7.84 ms with it (and 26 / 36 spilled registers become 0 / 12); the SDF-only kernel loses 6 % (its 168
-// registers leave no room for the second accumulator: 16 -> 28 spills) and the backward kernel 3 %: those keep one chain.
+// registers leave no room for the second accumulator: 16 -> 28 spills) and the backward kernel 3 %: those keep one chain
+// (layer_s1, layer_sq1); the forward kernels pair everywhere (layer_s, layer_sq, layer2_s).
 template <bool PAIRED, typename V, int KS, int NT, class ST, typename Epi, typename Hook = NoHook, class Bias = NoBias>
 __device__ __forceinline__ void layer_sp(ST& st, const V* __restrict__ blob, int offw, const Next& after, const V (&in)[KS],
                                          Epi&& epi, Hook&& hook = NoHook{}, const Bias& bias = NoBias{}) {
@@ -182,8 +136,7 @@ __device__ __forceinline__ void layer_sp(ST& st, const V* __restrict__ blob, int
     } else {
       stage_issue(st, after, st.par ^ 1);
     }
-    hook_call(hook, g, NG);
-    dephase(st);
+    hook_call(hook, g);
 #pragma unroll
     for (int j = 0; j < G; j += (PAIRED ? 2 : 1)) {
       const int t = g * G + j;
@@ -214,7 +167,7 @@ __device__ __forceinline__ void layer_sp(ST& st, const V* __restrict__ blob, int
 template <typename V, int KS, int NT, class ST, typename Epi, typename Hook = NoHook, class Bias = NoBias>
 __device__ __forceinline__ void layer_s(ST& st, const V* __restrict__ blob, int offw, const Next& after, const V (&in)[KS],
                                         Epi&& epi, Hook&& hook = NoHook{}, const Bias& bias = NoBias{}) {
-  layer_sp<(AVC_PAIR != 0), V, KS, NT>(st, blob, offw, after, in, epi, hook, bias);
+  layer_sp<true, V, KS, NT>(st, blob, offw, after, in, epi, hook, bias);
 }
 template <typename V, int KS, int NT, class ST, typename Epi, typename Hook = NoHook, class Bias = NoBias>
 __device__ __forceinline__ void layer_s1(ST& st, const V* __restrict__ blob, int offw, const Next& after, const V (&in)[KS],
@@ -225,20 +178,17 @@ __device__ __forceinline__ void layer_s1(ST& st, const V* __restrict__ blob, int
 // ---- (panel tiles read back by the backward sweeps), epi(t, acc, data) consumes them after the chain of tile t+1.  The
 // ---- backward kernel keeps only ~16 KiB of reads in flight per CU when every epilogue loads and immediately waits; one
 // ---- chain (~600 cycles) of head start costs no extra live set beyond the loaded registers themselves.
-#ifndef AVC_DEEP_PF1
-#define AVC_DEEP_PF1 0
-#endif
 #define AVC_PRE(...) [&](int t) __attribute__((always_inline)) { __VA_ARGS__ }
 #define AVC_EPID(DT, ...) [&](int t, const facc& acc, const DT& d) __attribute__((always_inline)) { __VA_ARGS__ }
-// DEEP = false: pre(t-1) goes out before the chain of tile t (one chain of head start, one load set live);
-// DEEP = true:  pre(t) goes out before the chain of tile t (two chains + one epilogue of head start, two sets live) --
-//               measured slower for the three-array loads of the reverse sweep (register pressure), see DESIGN.md 5.
-template <bool AVC_PRE_DEEP, bool PAIRED, bool DUAL, typename V, int KS, int NT, class ST, typename Pre, typename Epi, typename Hook>
+// pre(t-1) goes out before the chain of tile t (one chain of head start, one load set live).  (pre(t) before the chain of tile t -- two
+// chains + one epilogue of head start, two sets live -- measured slower for the three-array loads of the reverse sweep: register
+// pressure)
+template <bool PAIRED, typename V, int KS, int NT, class ST, typename Pre, typename Epi, typename Hook>
 __device__ __forceinline__ void layer_sq_(ST& st, const V* __restrict__ blob, int offw, const Next& after, const V (&in)[KS],
                                          Pre&& pre, Epi&& epi, Hook&& hook) {
   constexpr int G = ST::template group<KS>();
   constexpr int NG = (NT + G - 1) / G;
-  if constexpr (PAIRED && !AVC_PRE_DEEP) {
+  if constexpr (PAIRED) {
     // two output tiles per MFMA stream: the loads of the previous pair's epilogues go out before the chains of the current pair
     facc prev0, prev1;
     decltype(pre(0)) d0{}, d1{};
@@ -254,7 +204,7 @@ __device__ __forceinline__ void layer_sq_(ST& st, const V* __restrict__ blob, in
       } else {
         stage_issue(st, after, st.par ^ 1);
       }
-      hook_call(hook, g, NG);
+      hook_call(hook, g);
 #pragma unroll
       for (int j = 0; j < G; j += 2) {
         const int t = g * G + j;
@@ -290,17 +240,8 @@ __device__ __forceinline__ void layer_sq_(ST& st, const V* __restrict__ blob, in
     __builtin_amdgcn_sched_barrier(0);
     return;
   }
-  facc prev, prev2;
-  decltype(pre(0)) dprev{}, dcur{};
-  // DUAL (timing ablation AVC_ABL_BWD_RECOMP): every tile runs a second chain on the same A fragments and its epilogue pays 16 softplus
-  auto fold2 = [&](const facc& a, const facc& a2) __attribute__((always_inline)) {
-    facc r = a;
-    if constexpr (DUAL) {
-#pragma unroll
-      for (int q = 0; q < 16; ++q) r[q] += 1e-38f * softplus2(a2[q]);
-    }
-    return r;
-  };
+  facc prev;
+  decltype(pre(0)) dprev{};
 #pragma unroll
   for (int g = 0; g < NG; ++g) {
     AVC_SYNC();
@@ -312,55 +253,37 @@ __device__ __forceinline__ void layer_sq_(ST& st, const V* __restrict__ blob, in
     } else {
       stage_issue(st, after, st.par ^ 1);
     }
-    hook_call(hook, g, NG);
+    hook_call(hook, g);
 #pragma unroll
     for (int j = 0; j < G; ++j) {
       const int t = g * G + j;
       if (t < NT) {
         hook_tile(hook, t, NT);
-        if (AVC_PRE_DEEP) {
-          dcur = pre(t);
-          __builtin_amdgcn_sched_barrier(0);   // the loads go out before the chain
-        } else if (t > 0) {
+        if (t > 0) {
           dprev = pre(t - 1);
-          __builtin_amdgcn_sched_barrier(0);
+          __builtin_amdgcn_sched_barrier(0);   // the loads go out before the chain
         }
-        facc acc, acc2;
-        if constexpr (DUAL) {
-          const V* a = reinterpret_cast<const V*>(st.lds + st.par * ST::BUF_BYTES + j * KS * 1024) + st.lane;
-#pragma unroll
-          for (int r = 0; r < 16; ++r) { acc[r] = 0.f; acc2[r] = 1.f; }
-          asm volatile("" : "+v"(acc2));
-          acc = mma_chain_lds_dual<V, KS>(a, in, acc, acc2);
-        } else {
-          acc = tile_mma<V, KS>(st, j, in);
-        }
-        if (t > 0) { epi(t - 1, fold2(prev, prev2), dprev); interleave_mfma_valu<KS>(); }
+        facc acc = tile_mma<V, KS>(st, j, in);
+        if (t > 0) { epi(t - 1, prev, dprev); interleave_mfma_valu<KS>(); }
         prev = acc;
-        if constexpr (DUAL) prev2 = acc2;
-        if (AVC_PRE_DEEP) dprev = dcur;
         __builtin_amdgcn_sched_barrier(0);
       }
     }
     st.par ^= 1;
   }
-  if (!AVC_PRE_DEEP) dprev = pre(NT - 1);
-  epi(NT - 1, fold2(prev, prev2), dprev);
+  dprev = pre(NT - 1);
+  epi(NT - 1, prev, dprev);
   __builtin_amdgcn_sched_barrier(0);
 }
 template <typename V, int KS, int NT, class ST, typename Pre, typename Epi, typename Hook = NoHook>
 __device__ __forceinline__ void layer_sq(ST& st, const V* __restrict__ blob, int offw, const Next& after, const V (&in)[KS],
                                          Pre&& pre, Epi&& epi, Hook&& hook = NoHook{}) {
-  layer_sq_<false, (AVC_PAIR_SQ != 0), false, V, KS, NT>(st, blob, offw, after, in, pre, epi, hook);
+  layer_sq_<true, V, KS, NT>(st, blob, offw, after, in, pre, epi, hook);
 }
 template <typename V, int KS, int NT, class ST, typename Pre, typename Epi, typename Hook = NoHook>
-__device__ __forceinline__ void layer_sqd(ST& st, const V* __restrict__ blob, int offw, const Next& after, const V (&in)[KS],
+__device__ __forceinline__ void layer_sq1(ST& st, const V* __restrict__ blob, int offw, const Next& after, const V (&in)[KS],
                                           Pre&& pre, Epi&& epi, Hook&& hook = NoHook{}) {
-#ifdef AVC_ABL_BWD_RECOMP
-  layer_sq_<AVC_DEEP_PF1 != 0, false, true, V, KS, NT>(st, blob, offw, after, in, pre, epi, hook);
-#else
-  layer_sq_<AVC_DEEP_PF1 != 0, (AVC_PAIR_SQ != 0), false, V, KS, NT>(st, blob, offw, after, in, pre, epi, hook);
-#endif
+  layer_sq_<false, V, KS, NT>(st, blob, offw, after, in, pre, epi, hook);   // always one accumulator chain
 }
 template <typename V, int KA, int KB, int NT, class ST, typename Epi, typename Hook = NoHook, class Bias = NoBias>
 __device__ __forceinline__ void layer2_s(ST& st, const V* __restrict__ blob, int offw, const Next& after, const V (&ina)[KA],
@@ -368,7 +291,6 @@ __device__ __forceinline__ void layer2_s(ST& st, const V* __restrict__ blob, int
   constexpr int KS = KA + KB;
   constexpr int G = ST::template group<KS>();
   constexpr int NG = (NT + G - 1) / G;
-  constexpr bool PAIRED = AVC_PAIR_L2 != 0;
   facc prev0, prev1;
   int tp = -1, np = 0;
 #pragma unroll
@@ -382,13 +304,12 @@ __device__ __forceinline__ void layer2_s(ST& st, const V* __restrict__ blob, int
     } else {
       stage_issue(st, after, st.par ^ 1);
     }
-    hook_call(hook, g, NG);
-    dephase(st);
+    hook_call(hook, g);
 #pragma unroll
-    for (int j = 0; j < G; j += (PAIRED ? 2 : 1)) {
+    for (int j = 0; j < G; j += 2) {
       const int t = g * G + j;
       if (t < NT) {
-        const bool two = PAIRED && (j + 1 < G) && (t + 1 < NT);
+        const bool two = (j + 1 < G) && (t + 1 < NT);
         hook_tile(hook, t, NT);
         if (two) hook_tile(hook, t + 1, NT);
         facc a0, a1;
@@ -497,12 +418,7 @@ template <typename V> __device__ __forceinline__ AVC_GLOBAL V* tile_addr(const P
 template <bool KEEP, typename V>
 __device__ __forceinline__ void tile_store(const PanelPtr& pp, int tile, const V& f0, const V& f1) {
   AVC_GLOBAL V* p = tile_addr<V>(pp, tile);
-#ifdef AVC_KEEP_NT   // timing experiment: the re-read tiles streamed past the caches as well
-  constexpr bool keep = false;
-#else
-  constexpr bool keep = KEEP;
-#endif
-  if (keep) {
+  if (KEEP) {
     p[0] = f0;
     p[64] = f1;
   } else {
@@ -554,32 +470,28 @@ __device__ __forceinline__ float sdf_only(ST& sg, const h8* __restrict__ Wf, TP 
       h8 pef[3];
       pe_to_frags_f16(pe, x, h, pef);
       layer_s1<h8, 3, N::HT>(sg, Wf, o.v[OFF_W0], nxt<N, OFF_WM0>(sg, Wf, o), pef, AVC_EPI(
-        if constexpr (AVC_SDF_F16_ACT != 0) { softplus_frags_f16(acc, h1[2 * t], h1[2 * t + 1]); } else {
         float a[16];
         softplus2_tile(acc, a);
-        acc_to_frags(a, h1[2 * t], h1[2 * t + 1]); }
+        acc_to_frags(a, h1[2 * t], h1[2 * t + 1]);
       ), NoHook{}, TabBias{T + o.v[OFF_B0], h});
     }
     if constexpr (N::NMID == 2) {
       h8 hm0[N::HK];
       layer_s1<h8, N::HK, N::HT>(sg, Wf, o.v[OFF_WM0], nxt<N, OFF_WM1>(sg, Wf, o), h1, AVC_EPI(
-        if constexpr (AVC_SDF_F16_ACT != 0) { softplus_frags_f16(acc, hm0[2 * t], hm0[2 * t + 1]); } else {
         float a[16];
         softplus2_tile(acc, a);
-        acc_to_frags(a, hm0[2 * t], hm0[2 * t + 1]); }
+        acc_to_frags(a, hm0[2 * t], hm0[2 * t + 1]);
       ), NoHook{}, TabBias{T + o.v[OFF_BM0], h});
       layer_s1<h8, N::HK, N::HT>(sg, Wf, o.v[OFF_WM1], nxt<N, OFF_WS>(sg, Wf, o), hm0, AVC_EPI(
-        if constexpr (AVC_SDF_F16_ACT != 0) { softplus_frags_f16(acc, hlast[2 * t], hlast[2 * t + 1]); } else {
         float a[16];
         softplus2_tile(acc, a);
-        acc_to_frags(a, hlast[2 * t], hlast[2 * t + 1]); }
+        acc_to_frags(a, hlast[2 * t], hlast[2 * t + 1]);
       ), NoHook{}, TabBias{T + o.v[OFF_BM1], h});
     } else {
       layer_s1<h8, N::HK, N::HT>(sg, Wf, o.v[OFF_WM0], nxt<N, OFF_WS>(sg, Wf, o), h1, AVC_EPI(
-        if constexpr (AVC_SDF_F16_ACT != 0) { softplus_frags_f16(acc, hlast[2 * t], hlast[2 * t + 1]); } else {
         float a[16];
         softplus2_tile(acc, a);
-        acc_to_frags(a, hlast[2 * t], hlast[2 * t + 1]); }
+        acc_to_frags(a, hlast[2 * t], hlast[2 * t + 1]);
       ), NoHook{}, TabBias{T + o.v[OFF_BM0], h});
     }
   }
@@ -599,18 +511,11 @@ __device__ __forceinline__ float sdf_only(ST& sg, const h8* __restrict__ Wf, TP 
 // 512-entry unified file (MFMA takes its B operands from either half).
 // ---------------------------------------------------------------------------------------------------------------
 #define AVC_EPI2(...) [&](int t, int q, const facc& acc) __attribute__((always_inline)) { __VA_ARGS__ }
-#ifndef AVC_LDS_AHEAD_M2
-#define AVC_LDS_AHEAD_M2 8   // A fragments in flight ahead of the MFMA pairs
-#endif
+constexpr int AVC_LDS_AHEAD_M2 = 8;   // A fragments in flight ahead of the MFMA pairs
 // the epilogues of two groups (2 x 16 elements: exp, add, log, med3 + 8 conversions = ~150 instructions, 64 of them transcendental)
 // dealt over the 2 KS MFMAs of the next tile: with ONE wavefront per SIMD about five single-issue instructions fit the 32-cycle shadow of
 // an MFMA (MI355X_MICROARCH.md, per-instruction constants), which is what a 256-wide layer offers (32 MFMAs per tile step)
-#ifndef AVC_M2_TRANS_PER_MFMA
-#define AVC_M2_TRANS_PER_MFMA 2
-#endif
-#ifndef AVC_M2_VALU_PER_MFMA
-#define AVC_M2_VALU_PER_MFMA 3
-#endif
+constexpr int AVC_M2_TRANS_PER_MFMA = 2, AVC_M2_VALU_PER_MFMA = 3;
 template <int NM>
 __device__ __forceinline__ void interleave_m2() {
   constexpr int scale = NM >= 32 ? 1 : (32 + NM - 1) / NM;   // short chains (layer 0: 6 MFMAs) take the whole epilogue between them

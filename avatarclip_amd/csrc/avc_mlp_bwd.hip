@@ -21,7 +21,7 @@ __global__ __launch_bounds__(64 * BWD_WPB) void mlp_bwd_kernel(BwdArgs a) {
   extern __shared__ __attribute__((aligned(16))) char lds[];
   typedef StageT<BWD_G> ST;
   constexpr AvcOffsets o = Off<N>::value;
-  avc_static_wave_priority();
+  static_assert(BWD_WPB >= 4 && BWD_WPB % 4 == 0, "stage_issue's turns need a multiple of 4 wavefronts per workgroup");
   const int lane0 = threadIdx.x & 63;
   const int wv = threadIdx.x >> 6;
   const long nblk = (a.npts + 31) >> 5;
@@ -33,15 +33,10 @@ __global__ __launch_bounds__(64 * BWD_WPB) void mlp_bwd_kernel(BwdArgs a) {
   __syncthreads();
   NoRing ring;
   // every wavefront of a workgroup runs the same number of iterations (workgroup-uniform loop bound)
-#if AVC_BWD_PIPE_IN
   BlkIn<N> bi;     // the block's first inputs, requested one block ahead (csrc/avc_bwd_body.h)
   load_blk_in<N>(a, (long)blockIdx.x * BWD_WPB + wv, nblk, lane0, bi);
   for (long blk0 = (long)blockIdx.x * BWD_WPB; blk0 < nblk; blk0 += (long)gridDim.x * BWD_WPB)
     bwd_sweeps<N, true>(sg, a, Tl, blk0, nblk, lane0, wv, ring, cs, &bi, blk0 + (long)gridDim.x * BWD_WPB);
-#else
-  for (long blk0 = (long)blockIdx.x * BWD_WPB; blk0 < nblk; blk0 += (long)gridDim.x * BWD_WPB)
-    bwd_sweeps<N>(sg, a, Tl, blk0, nblk, lane0, wv, ring, cs);
-#endif
   cs_flush<N>(cs, a.colsum, (long)blockIdx.x * BWD_WPB + wv, lane0);
 }
 

@@ -2,55 +2,18 @@
 //   avc_sdf_forward       SDF only (row 0 of the last layer) -- the no-grad evaluations of the hierarchical sampler
 //                         (renderer.py:337-338,187) and of extract_fields (renderer.py:10-25)
 //   avc_render_points_fwd sdf + normal (d sdf/dx) + 6 colour channels per sample point (renderer.py:221-232)
-// two output tiles per MFMA stream (independent accumulator chains) in the layers of THIS file: forward 6.21 -> 6.02 ms, training
-// forward 8.20 -> 7.90 ms per 4 Mi points; the backward kernel loses 4 % with it (profiles/r03_ab_kernels.txt) and keeps one chain
-#ifndef AVC_PAIR
-#define AVC_PAIR 1
-#endif
+// The layers of THIS file run two output tiles per MFMA stream (independent accumulator chains; layer_s, layer_sq, layer2_s of avc_mlp.h):
+// forward 6.21 -> 6.02 ms, training forward 8.20 -> 7.90 ms per 4 Mi points; the backward kernel loses 4 % with it and keeps one chain
+// (profiles/r03_ab_kernels.txt).
 #include "avc_mlp.h"
-#ifndef FWD_WPB
-#define FWD_WPB 8   // one 8-wave workgroup per CU shares every staged weight tile (LDS-DMA fill rate is the scarce resource)
-#endif
-#ifndef SDF_WPB
-#define SDF_WPB 12   // wavefronts per workgroup of the SDF-only kernel: the only kernel of the engine that fits 168 VGPRs (16 spilled), i.e. 3 waves per SIMD and 384 points per staged weight tile (8 -> 12: -6 %)
-#endif
-#ifndef FWD_G
-#define FWD_G 4
-#endif
-#ifndef AVC_SPREAD_STORES
-#define AVC_SPREAD_STORES 1   // 1: the tile stores of a layer's input are dealt to ALL weight-group intervals of the layer, 0: all after the first barrier
-#endif
-#if AVC_SPREAD_STORES
+constexpr int FWD_WPB = 8;    // one 8-wave workgroup per CU shares every staged weight tile (LDS-DMA fill rate is the scarce resource)
+constexpr int SDF_WPB = 12;   // wavefronts per workgroup of the SDF-only kernel: the only kernel of the engine that fits 168 VGPRs (16 spilled), i.e. 3 waves per SIMD and 384 points per staged weight tile (8 -> 12: -6 %)
+constexpr int FWD_G = 4;
+// the tile stores of a layer's input are dealt to ALL tile steps of the layer, not issued in one burst after its first barrier
 #define AVC_STORE_HOOK(KEEP, NT, PT, ARR) AVC_HOOKG(tiles_store_part<KEEP, NT>(tiles, PT, ARR, grp_, ngrp_);)
-#else
-#define AVC_STORE_HOOK(KEEP, NT, PT, ARR) AVC_HOOK(tiles_store<KEEP, NT>(tiles, PT, ARR);)
-#endif
-// timing ablations of the training forward (results are garbage): which of its extra stores cost what
-#ifdef AVC_ABL_NOMASK
-constexpr bool ABL_NOMASK = true;
-#else
-constexpr bool ABL_NOMASK = false;
-#endif
-#ifdef AVC_ABL_NORSTORE
-constexpr bool ABL_NORSTORE = true;
-#else
-constexpr bool ABL_NORSTORE = false;
-#endif
-#ifdef AVC_ABL_NOGASTORE
-constexpr bool ABL_NOGASTORE = true;
-#else
-constexpr bool ABL_NOGASTORE = false;
-#endif
-#ifdef AVC_ABL_NOMISC
-constexpr bool ABL_NOMISC = true;
-#else
-constexpr bool ABL_NOMISC = false;
-#endif
 #include "../../include/avc.h"
 #include <stdlib.h>
-#ifndef AVC_SDF_PPW_DEFAULT
-#define AVC_SDF_PPW_DEFAULT 32   // points per wavefront of avc_sdf_forward: 32 (mlp_sdf_kernel) | 64 (mlp_sdf2_kernel)
-#endif
+constexpr int AVC_SDF_PPW_DEFAULT = 32;   // points per wavefront of avc_sdf_forward: 32 (mlp_sdf_kernel) | 64 (mlp_sdf2_kernel)
 
 template <class N>
 __global__ __launch_bounds__(64 * SDF_WPB) void mlp_sdf_kernel(PointSrc ps, long npts, const h8* __restrict__ Wf,
@@ -60,7 +23,7 @@ __global__ __launch_bounds__(64 * SDF_WPB) void mlp_sdf_kernel(PointSrc ps, long
   constexpr AvcOffsets o = Off<N>::value;
   extern __shared__ __attribute__((aligned(16))) char lds[];
   typedef StageT<FWD_G> ST;
-  avc_static_wave_priority();
+  static_assert(SDF_WPB >= 4 && SDF_WPB % 4 == 0, "stage_issue's turns need a multiple of 4 wavefronts per workgroup");
   const int lane = threadIdx.x & 63;
   const int h = lane >> 5;
   const int p = lane & 31;
@@ -88,9 +51,7 @@ __global__ __launch_bounds__(64 * SDF_WPB) void mlp_sdf_kernel(PointSrc ps, long
 
 // ---- the same with two 32-point groups per wavefront (sdf_only2, avc_mlp.h): 4-wave workgroups, one wavefront per SIMD on the
 // ---- 512-entry unified register file; every staged weight tile serves 256 points and every LDS A fragment two MFMAs
-#ifndef SDF2_WPB
-#define SDF2_WPB 4
-#endif
+constexpr int SDF2_WPB = 4;
 template <class N>
 __global__ __launch_bounds__(64 * SDF2_WPB) void mlp_sdf2_kernel(PointSrc ps, long npts, const h8* __restrict__ Wf,
                                                                  const float* __restrict__ T, float* __restrict__ sdf_out,
@@ -98,6 +59,7 @@ __global__ __launch_bounds__(64 * SDF2_WPB) void mlp_sdf2_kernel(PointSrc ps, lo
   constexpr AvcOffsets o = Off<N>::value;
   extern __shared__ __attribute__((aligned(16))) char lds[];
   typedef StageT<FWD_G> ST;
+  static_assert(SDF2_WPB >= 4 && SDF2_WPB % 4 == 0, "stage_issue's turns need a multiple of 4 wavefronts per workgroup");
   const int lane = threadIdx.x & 63;
   const int h = lane >> 5;
   const int p = lane & 31;
@@ -139,12 +101,6 @@ __global__ __launch_bounds__(64 * SDF2_WPB) void mlp_sdf2_kernel(PointSrc ps, lo
 //                  (non-temporal) and ride under a kernel that is bound by its matrix / vector work.
 // Persistent workgroups.  Plain (temporal) accesses for the tiles that are re-read within the same block.
 // ---------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ FragPair<h8> fwd_abl_pair(int t) {   // (AVC_ABL_FWD_NORR: an opaque constant in place of a tile read back)
-  FragPair<h8> d;
-  _Pragma("unroll") for (int j = 0; j < 8; ++j) { d.a0[j] = (_Float16)(0.25f + 0.01f * t); d.a1[j] = (_Float16)(0.5f - 0.01f * t); }
-  asm volatile("" : "+v"(d.a0), "+v"(d.a1));
-  return d;
-}
 template <typename P> __device__ __forceinline__ P launder_ptr(P p) {
   asm volatile("" : "+s"(p));
   return p;
@@ -160,7 +116,7 @@ __global__ __launch_bounds__(64 * FWD_WPB) void mlp_render_kernel(PointSrc ps, l
   typedef typename std::conditional<TRAIN, PanelLayout<N>, ScratchLayout<N>>::type L;
   extern __shared__ __attribute__((aligned(16))) char lds[];
   typedef StageT<FWD_G> ST;
-  avc_static_wave_priority();
+  static_assert(FWD_WPB >= 4 && FWD_WPB % 4 == 0, "stage_issue's turns need a multiple of 4 wavefronts per workgroup");
   const int lane0 = threadIdx.x & 63;
   const int wv = threadIdx.x >> 6;
   const long nblk = (npts + 31) >> 5;
@@ -260,7 +216,7 @@ __global__ __launch_bounds__(64 * FWD_WPB) void mlp_render_kernel(PointSrc ps, l
         acc_to_frags(a, f0, f1);
         tile_store<true>(tiles, L::P_FEAT + t, f0, f1);
       ), AVC_HOOK(
-        if constexpr (TRAIN && !ABL_NOMISC) {
+        if constexpr (TRAIN) {
           tiles_store<false, N::ST>(tiles, L::P_HS, hs);
           tiles_store<false, N::ST>(tiles, L::P_GAS, g_s);
         }), AVC_F_BIAS(OFF_BL));
@@ -268,23 +224,14 @@ __global__ __launch_bounds__(64 * FWD_WPB) void mlp_render_kernel(PointSrc ps, l
     // ---------------------------------------------------------------- normal sweep: g_h(prev) = W^T g_a ; g_a(prev) = g_h sigma(h_prev)
     float n[3];
     {
-#ifdef AVC_ABL_FWD_NORR   // timing ablation only (garbage results): the normal sweep WITHOUT its re-reads of the parked h tiles = the upper bound of
-                          // any scheme that keeps h_1 .. h_s resident through the sweep
-#define AVC_F_HLOAD(PH) fwd_abl_pair(t)
-#else
 #define AVC_F_HLOAD(PH) tile_load<false, h8>(tiles, (PH) + t)
-#endif
 #define AVC_F_NSTEP(OUT, PH)                                                                              \
   AVC_PRE(return AVC_F_HLOAD(PH);),                                                                         \
   AVC_EPID(FragPair<h8>, _Pragma("unroll") for (int j = 0; j < 8; ++j) {                                    \
             OUT[2 * t][j] = (_Float16)(acc[j] * sig_from_h((float)d.a0[j]));                                \
             OUT[2 * t + 1][j] = (_Float16)(acc[8 + j] * sig_from_h((float)d.a1[j])); }                      \
           pin2(OUT[2 * t], OUT[2 * t + 1]);)
-#if AVC_SPREAD_STORES
-#define AVC_F_GSTORE(PG, G) AVC_HOOKG(if constexpr (TRAIN && !ABL_NOGASTORE) tiles_store_part<false, N::HT>(tiles, PG, G, grp_, ngrp_);)
-#else
-#define AVC_F_GSTORE(PG, G) AVC_HOOK(if constexpr (TRAIN && !ABL_NOGASTORE) tiles_store<false, N::HT>(tiles, PG, G);)
-#endif
+#define AVC_F_GSTORE(PG, G) AVC_HOOKG(if constexpr (TRAIN) tiles_store_part<false, N::HT>(tiles, PG, G, grp_, ngrp_);)
       h8 g[N::HK];
       h8 g2[N::HK];
       if constexpr (N::NMID == 2) {
@@ -336,14 +283,9 @@ __global__ __launch_bounds__(64 * FWD_WPB) void mlp_render_kernel(PointSrc ps, l
       // masks of the backward pass -- both from the hook of the next layer
 #define AVC_F_RELU(OUT, ML)                                                                   \
   AVC_EPI(const unsigned bits = relu_frags<TRAIN>(acc, OUT[2 * t], OUT[2 * t + 1]);            \
-          if constexpr (TRAIN && !ABL_NOMASK) mk[((ML) * N::HT + t) * 64] = (unsigned short)bits;)
-#if AVC_SPREAD_STORES
+          if constexpr (TRAIN) mk[((ML) * N::HT + t) * 64] = (unsigned short)bits;)
 #define AVC_F_RSTORE(PT, R)                                                                   \
-  AVC_HOOKG(if constexpr (TRAIN && !ABL_NORSTORE) tiles_store_part<false, N::HT>(tiles, PT, R, grp_, ngrp_);)
-#else
-#define AVC_F_RSTORE(PT, R)                                                                   \
-  AVC_HOOK(if constexpr (TRAIN && !ABL_NORSTORE) tiles_store<false, N::HT>(tiles, PT, R);)
-#endif
+  AVC_HOOKG(if constexpr (TRAIN) tiles_store_part<false, N::HT>(tiles, PT, R, grp_, ngrp_);)
       h8 r1[N::HK];
       h8 r2[N::HK];
       if constexpr (N::NCMID == 1) {

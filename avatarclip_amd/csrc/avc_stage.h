@@ -36,7 +36,7 @@ struct StageT {
   int wave;    // wave index in the workgroup (SGPR)
   int lane;
   int nw;      // waves per workgroup
-  int turn;    // which of the wavefronts of a SIMD issues the next group's DMA (AVC_DMA_TURNS)
+  int turn;    // which of the wavefronts of a SIMD issues the next group's DMA 
 };
 
 template <int G>
@@ -55,26 +55,19 @@ __device__ __forceinline__ StageT<G> stage_init(char* lds) {
 // the group barrier, in front of its first MFMA: a global_load_lds costs the issuing wave 60-185 cycles (MI355X_MICROARCH.md, "LDS-DMA
 // piece issue cost"), all wavefronts of a SIMD pay it at the same moment and nobody feeds the matrix pipe meanwhile -- with the DMA
 // removed the SDF kernel runs 19.5 % faster, with the barriers removed 3 % (profiles/r06_ab_kernels.txt: most of the "waits" of DESIGN.md
-// section 5).  AVC_DMA_TURNS=1: of the wavefronts that share a SIMD (w, w + 4, w + 8) only ONE issues per group -- the four of a turn,
+// section 5).  So of the wavefronts that share a SIMD (w, w + 4, w + 8) only ONE issues per group -- the four of a turn,
 // one per SIMD, copy the whole group -- and the turn rotates with every group; the others go straight to their MFMA chains and have the
 // SIMD to themselves while the issuing wave is busy, which then catches up while they wait at the next barrier.  No new control flow:
 // the chunk loop stays where it was, only its first index and stride change (a wave out of turn starts at `chunks`).
-#ifndef AVC_DMA_TURNS
-#define AVC_DMA_TURNS 1
-#endif
-#ifndef AVC_DMA_ROT
-#define AVC_DMA_ROT 0
-#endif
+// rotate = true needs blockDim.x / 64 to be a multiple of 4 and at least 4 (with fewer wavefronts only part of the group would be
+// staged): every kernel that rotates says so with a static_assert on its workgroup size.
+// (Workgroups walking the chunks from different starting points made no difference: profiles/r06_ab_kernels.txt.)
 template <class ST>
 __device__ __forceinline__ void stage_issue(ST& st, const Next& nx, int buf, bool rotate = true) {
   if (!nx.ptr) return;
-#ifdef AVC_ABL_NODMA   // timing ablation only (results are garbage)
-  return;
-#endif
   const char* g = reinterpret_cast<const char*>(nx.ptr);
   char* dst = st.lds + buf * ST::BUF_BYTES;
   int first = st.wave, stride = st.nw;
-#if AVC_DMA_TURNS
   if (rotate) {
     const int nsub = st.nw >> 2;                  // wavefronts per SIMD
     first = ((st.wave >> 2) == st.turn) ? (st.wave & 3) : nx.chunks;
@@ -82,25 +75,9 @@ __device__ __forceinline__ void stage_issue(ST& st, const Next& nx, int buf, boo
     const int nt = st.turn + 1;
     st.turn = nt >= nsub ? 0 : nt;
   }
-#endif
-#ifdef AVC_ABL_HALFDMA   // timing ablation only (garbage results): every second chunk -- is the cost proportional to the bytes?
-  stride *= 2;
-#endif
-  for (int c = first; c < nx.chunks; c += stride) {
-#if AVC_DMA_ROT          // experiment: workgroups walk the group's chunks from different starting points (same data, same LDS image)
-    int cs = c + (int)(blockIdx.x * 5u) % nx.chunks;
-    cs = cs >= nx.chunks ? cs - nx.chunks : cs;
-#else
-    const int cs = c;
-#endif
-#ifdef AVC_ABL_DMA_SAMESRC   // timing ablation only (garbage results): every chunk from the SAME 1 KiB of the blob -- L2 / fabric side or LDS / issue side?
-    const int src = 0;
-#else
-    const int src = cs;
-#endif
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(g + src * 1024 + st.lane * 16),
-                                     (__attribute__((address_space(3))) void*)(dst + cs * 1024), 16, 0, 0);
-  }
+  for (int c = first; c < nx.chunks; c += stride)
+    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(g + c * 1024 + st.lane * 16),
+                                     (__attribute__((address_space(3))) void*)(dst + c * 1024), 16, 0, 0);
 }
 
 
@@ -118,24 +95,16 @@ __device__ __forceinline__ void pin4(V& a, V& b, V& c, V& d) { asm("" : "+v"(a),
 // ~150 VALU instructions with the matrix pipe idle; both wavefronts of a SIMD run in lockstep between the group barriers,
 // so MFMA time and VALU time ADD (measured: forward kernel = MFMA 32 us + VALU 32 us + LDS 31 us + DMA 24 us per round).
 // One MFMA followed by a slice of VALU work, KS times, lets the epilogue run in the shadow of the chain.
-#ifndef AVC_VALU_PER_MFMA
-#define AVC_VALU_PER_MFMA 10
-#endif
-#ifndef AVC_TRANS_PER_MFMA
-#define AVC_TRANS_PER_MFMA 0   // > 0: ask for that many transcendentals right behind every MFMA (they issue under the matrix pipe for free up to ~2 per MFMA: profiles/r02_ubench2.txt), the plain VALU slice after them
-#endif
+constexpr int AVC_VALU_PER_MFMA = 10;
 template <int KS>
 __device__ __forceinline__ void interleave_mfma_valu() {
 #pragma unroll
   for (int k = 0; k < KS; ++k) {
     __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                   // 1 MFMA
-    if (AVC_TRANS_PER_MFMA > 0) __builtin_amdgcn_sched_group_barrier(0x400, AVC_TRANS_PER_MFMA, 0);   // transcendentals
     __builtin_amdgcn_sched_group_barrier(0x002, AVC_VALU_PER_MFMA, 0);   // then a slice of VALU
   }
 }
-#ifndef AVC_LDS_AHEAD
-#define AVC_LDS_AHEAD 8   // A fragments in flight ahead of the MFMA chain (x4 VGPRs each)
-#endif
+constexpr int AVC_LDS_AHEAD = 8;   // A fragments in flight ahead of the MFMA chain (x4 VGPRs each)
 template <typename V, int KS>
 __device__ __forceinline__ facc mma_chain_lds(const V* __restrict__ a_lds /* lane's chunk of k-step 0 */, const V (&in)[KS], facc acc) {
   // rolling prefetch: AVC_LDS_AHEAD fragments are requested up front, every group of 4 MFMAs is preceded by the requests
@@ -156,27 +125,6 @@ __device__ __forceinline__ facc mma_chain_lds(const V* __restrict__ a_lds /* lan
 }
 
 
-// timing ablation (AVC_ABL_BWD_RECOMP, csrc/avc_bwd_body.h): a second accumulator chain on the SAME A fragments -- one LDS read feeds
-// two MFMAs -- which is what recomputing h_l inside the second-order sweep would add to its MFMA stream at the very least
-template <typename V, int KS>
-__device__ __forceinline__ facc mma_chain_lds_dual(const V* __restrict__ a_lds, const V (&in)[KS], facc acc, facc& acc2) {
-  V a[KS];
-#pragma unroll
-  for (int s = 0; s < KS && s < AVC_LDS_AHEAD; ++s) a[s] = a_lds[s * 64];
-#pragma unroll
-  for (int s = 0; s < KS; s += 4) {
-    if (s + 3 < KS) pin4(a[s], a[s + 1], a[s + 2], a[s + 3]);
-#pragma unroll
-    for (int k = s + AVC_LDS_AHEAD; k < s + AVC_LDS_AHEAD + 4 && k < KS; ++k) a[k] = a_lds[k * 64];
-#pragma unroll
-    for (int k = s; k < s + 4 && k < KS; ++k) {
-      acc = MF<V>::mma(a[k], in[k], acc);
-      acc2 = MF<V>::mma(a[k], in[k], acc2);
-    }
-  }
-  return acc;
-}
-
 // where the accumulator of an output tile starts: zero, or the tile's bias row from the fp32 table in LDS (see tile_mma below)
 struct NoBias { static constexpr bool on = false; };
 struct TabBias { static constexpr bool on = true; lds_tab_t tab; int h; };
@@ -185,9 +133,7 @@ struct TabBias { static constexpr bool on = true; lds_tab_t tab; int h; };
 // ---- operand).  A filler issued between two MFMAs on the SAME accumulator breaks the back-to-back accumulate path of the
 // ---- matrix pipe (~+43 cycles, MI355X_MICROARCH.md "per-instruction cycle constants"), which is why a single dependent chain
 // ---- cannot hide the epilogue of the previous tile; between MFMAs on different accumulators a filler costs its issue slot.
-#ifndef AVC_LDS_AHEAD2
-#define AVC_LDS_AHEAD2 4   // A fragments in flight per tile of the pair
-#endif
+constexpr int AVC_LDS_AHEAD2 = 4;   // A fragments in flight per tile of the pair
 // the MFMAs of two tiles over one input array: a0 / a1 = this lane's chunk of k-step 0 of either tile
 template <typename V, int KS>
 __device__ __forceinline__ void pair_chain(const V* __restrict__ a0, const V* __restrict__ a1, const V (&in)[KS], facc& acc0, facc& acc1) {

@@ -139,9 +139,7 @@ __global__ __launch_bounds__(64 * VIT_WAVES) void vit_linear_kernel(const b8* __
 // MFMAs, 1 KiB of operands per MFMA; the two wavefronts that share a row / column pair meet in the CU's L1), the whole K range per
 // wavefront (no split-K, no LDS), fragments prefetched VIT_GEMM_AHEAD k-steps ahead.  Both operands arrive pre-packed in fragment
 // order, so every load is one coalesced 16 B per lane.
-#ifndef VIT_GEMM_AHEAD
-#define VIT_GEMM_AHEAD 3
-#endif
+constexpr int VIT_GEMM_AHEAD = 3;
 __global__ __launch_bounds__(256) void vit_gemm_kernel(const b8* __restrict__ Xs, const b8* __restrict__ Wp, const float* __restrict__ bias,
                                                        const float* __restrict__ res, float* __restrict__ Y, float* __restrict__ Ypre,
                                                        int M, int N, int K, int act) {
@@ -209,12 +207,10 @@ __global__ __launch_bounds__(256) void vit_gemm_kernel(const b8* __restrict__ Xs
   }
 }
 
-// batched calls: the LDS-staged GEMM of avc_vit_gemm.hip (128 x 128 blocks)
+// batched calls: the LDS-staged GEMM of avc_vit_gemm.hip (128 x 128 blocks; 12.7 ms per encoder pass against 20.3 for the direct-from-L1
+// kernel above, profiles/r03_score_bench.txt), which returns false for the shapes it does not cover
 bool avc_vit_gemm_lds(const void* xs, const void* wp, const float* bias, const float* res, float* y, float* y_pre, void* ys, int M, int N,
                       int K, int act, int mt_packed, void* stream);
-#ifndef VIT_GEMM_LDS
-#define VIT_GEMM_LDS 1   // 0: the direct-from-L1 128 x 128 kernel above (the A/B of profiles/r03_score_bench.txt)
-#endif
 
 extern "C" long avc_vit_workspace_bytes(int M, int K) {
   const long mt = ((M + 127) / 128) * 4;   // whole groups of 4 row tiles (the rows past M are packed as zeros)
@@ -253,13 +249,10 @@ static int vit_linear_impl(const float* x, const float* x_gelu_pre, const void* 
   if (avc_first_use_on_device(attr_seen)) {
     (void)hipFuncSetAttribute((const void*)vit_linear_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, VIT_WAVES * 4 * 4096);
   }
-#ifndef VIT_BATCHED_GEMM
-#define VIT_BATCHED_GEMM 1   // 0: batched calls through the split-K latency kernel with 4 row tiles per workgroup (13.5 k images/s at B = 512)
-#endif
-  if (batched && VIT_BATCHED_GEMM && VIT_GEMM_LDS && avc_vit_gemm_lds(xs, wp, bias, residual, y, y_pre, nullptr, M, N, K, act, mt_packed, stream)) {
-  } else if (batched && VIT_BATCHED_GEMM && (N & 127) == 0) {
+  if (batched && avc_vit_gemm_lds(xs, wp, bias, residual, y, y_pre, nullptr, M, N, K, act, mt_packed, stream)) {
+  } else if (batched && (N & 127) == 0) {
     hipLaunchKernelGGL(vit_gemm_kernel, dim3(N / 128, mt_packed / 4), dim3(256), 0, s, xs, wp, bias, residual, y, y_pre, M, N, K, act);
-  } else if (batched) {
+  } else if (batched) {   // the split-K latency kernel with 4 row tiles per workgroup (13.5 k images/s at B = 512)
     hipLaunchKernelGGL((vit_linear_kernel<4>), grid, block, lds, s, xs, wp, bias, residual, y, y_pre, M, N, K, act);
   } else {
     vit_launch_small(grid, lds, s, xs, wp, bias, residual, y, y_pre, M, N, K, act, nullptr, nullptr);
@@ -469,81 +462,12 @@ extern "C" int avc_vit_ln_bwd(const float* dy, const float* x, const float* gamm
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// attention: qkv [B,T,3*W] (q | k | v, head hd at column hd*64), out [B,T,W].  One 4-wave workgroup per (b, head).
+// attention: qkv [B,T,3*W] (q | k | v, head hd at column hd*64), out [B,T,W].  The image tower's kernels are the matrix-core ones of
+// avc_vit_attn.hip; the fp32 VALU kernels they replaced in round 3 (profiles/r03_ab_kernels.txt) are gone.
 // ---------------------------------------------------------------------------------------------------------
 #define AT_T 50
 #define AT_D 64
 #define AT_LD 65   // +1 padding: thread i reads row i -> conflict-free
-
-// AT_PARTS wavefronts per (b, head): wave `part` owns the keys j = part (mod AT_PARTS) for the scores and the AT_COLS output
-// columns AT_COLS part .. for P V; every LDS read of K / V is a broadcast (a wave shares j), P rows are stride-51 (conflict-free).
-// Only B x heads = 24 workgroups exist per call, so the kernels are latency chains: 8 wavefronts instead of 4 halve every
-// per-thread loop (forward 26 -> see profiles/r03_ab_kernels.txt, backward 56 ->).
-#ifndef AT_PARTS
-#define AT_PARTS 8
-#endif
-#define AT_COLS (AT_D / AT_PARTS)
-__device__ __forceinline__ float at_max_parts(const float (*r)[64], int i) {
-  float m = r[0][i];
-#pragma unroll
-  for (int p = 1; p < AT_PARTS; ++p) m = fmaxf(m, r[p][i]);
-  return m;
-}
-__device__ __forceinline__ float at_sum_parts(const float (*r)[64], int i) {
-  float m = r[0][i];
-#pragma unroll
-  for (int p = 1; p < AT_PARTS; ++p) m += r[p][i];
-  return m;
-}
-__global__ __launch_bounds__(64 * AT_PARTS) void vit_attn_fwd_kernel(const float* __restrict__ qkv, float* __restrict__ out, int Wd,
-                                                                     int heads, float scale) {
-  __shared__ float Ks[AT_T][AT_LD], Vs[AT_T][AT_LD], Ps[AT_T][AT_T + 1], red[2][AT_PARTS][64];
-  const int b = blockIdx.x / heads, hd = blockIdx.x % heads;
-  const int i = threadIdx.x & 63, part = threadIdx.x >> 6;
-  const float* base = qkv + (long)b * AT_T * 3 * Wd + hd * AT_D;
-  for (int e = threadIdx.x; e < AT_T * AT_D; e += 64 * AT_PARTS) {
-    const int r = e / AT_D, c = e % AT_D;
-    Ks[r][c] = base[(long)r * 3 * Wd + Wd + c];
-    Vs[r][c] = base[(long)r * 3 * Wd + 2 * Wd + c];
-  }
-  __syncthreads();
-  const bool live = i < AT_T;
-  float mx = -1e30f;
-  if (live) {
-    float q[AT_D];
-#pragma unroll
-    for (int c = 0; c < AT_D; ++c) q[c] = base[(long)i * 3 * Wd + c] * scale;
-    for (int j = part; j < AT_T; j += AT_PARTS) {
-      float s = 0.f;
-#pragma unroll
-      for (int c = 0; c < AT_D; ++c) s += q[c] * Ks[j][c];
-      Ps[i][j] = s;
-      mx = fmaxf(mx, s);
-    }
-  }
-  red[0][part][i] = mx;
-  __syncthreads();
-  float sum = 0.f;
-  if (live) {
-    mx = at_max_parts(red[0], i);
-    for (int j = part; j < AT_T; j += AT_PARTS) { const float e = __expf(Ps[i][j] - mx); Ps[i][j] = e; sum += e; }
-  }
-  red[1][part][i] = sum;
-  __syncthreads();
-  if (!live) return;
-  const float inv = 1.f / at_sum_parts(red[1], i);
-  float o[AT_COLS];
-#pragma unroll
-  for (int c = 0; c < AT_COLS; ++c) o[c] = 0.f;
-  for (int j = 0; j < AT_T; ++j) {
-    const float pj = Ps[i][j] * inv;
-#pragma unroll
-    for (int c = 0; c < AT_COLS; ++c) o[c] += pj * Vs[j][AT_COLS * part + c];
-  }
-  float* op = out + ((long)b * AT_T + i) * Wd + hd * AT_D + AT_COLS * part;
-#pragma unroll
-  for (int c = 0; c < AT_COLS; ++c) op[c] = o[c];
-}
 
 // Text tower (clip/model.py encode_text: 77 tokens, 8 heads of 64, causal mask): forward only -- prompts are encoded once per
 // run (main.py:273-288).  One workgroup per (sequence, head), thread i = query row i, K/V rows in LDS, online softmax.
@@ -585,92 +509,7 @@ __global__ __launch_bounds__(TA_TMAX) void text_attn_fwd_kernel(const float* __r
   for (int c = 0; c < AT_D; ++c) op[c] = o[c] * inv;
 }
 
-__global__ __launch_bounds__(64 * AT_PARTS) void vit_attn_bwd_kernel(const float* __restrict__ qkv, const float* __restrict__ dout,
-                                                                     float* __restrict__ dqkv, int Wd, int heads, float scale) {
-  extern __shared__ __attribute__((aligned(16))) float sm[];
-  float (*Ks)[AT_LD] = reinterpret_cast<float (*)[AT_LD]>(sm);
-  float (*Vs)[AT_LD] = Ks + AT_T;
-  float (*Qs)[AT_LD] = Vs + AT_T;
-  float (*Ds)[AT_LD] = Qs + AT_T;                       // dO
-  float (*Ps)[AT_T + 1] = reinterpret_cast<float (*)[AT_T + 1]>(Ds + AT_T);   // P
-  float (*Ss)[AT_T + 1] = Ps + AT_T;                    // dS (already scaled)
-  float (*red)[AT_PARTS][64] = reinterpret_cast<float (*)[AT_PARTS][64]>(Ss + AT_T);   // [3][parts][64]: max, sum, sum p d
-  const int b = blockIdx.x / heads, hd = blockIdx.x % heads;
-  const int i = threadIdx.x & 63, part = threadIdx.x >> 6;
-  const bool live = i < AT_T;
-  const float* base = qkv + (long)b * AT_T * 3 * Wd + hd * AT_D;
-  const float* dob = dout + (long)b * AT_T * Wd + hd * AT_D;
-  for (int e = threadIdx.x; e < AT_T * AT_D; e += 64 * AT_PARTS) {
-    const int r = e / AT_D, c = e % AT_D;
-    Qs[r][c] = base[(long)r * 3 * Wd + c];
-    Ks[r][c] = base[(long)r * 3 * Wd + Wd + c];
-    Vs[r][c] = base[(long)r * 3 * Wd + 2 * Wd + c];
-    Ds[r][c] = dob[(long)r * Wd + c];
-  }
-  __syncthreads();
-  // scores and dP = dO V^T for the keys of this wave
-  float mx = -1e30f;
-  if (live) {
-    for (int j = part; j < AT_T; j += AT_PARTS) {
-      float s = 0.f, d = 0.f;
-#pragma unroll
-      for (int c = 0; c < AT_D; ++c) { s += Qs[i][c] * Ks[j][c]; d += Ds[i][c] * Vs[j][c]; }
-      s *= scale;
-      Ps[i][j] = s;
-      Ss[i][j] = d;
-      mx = fmaxf(mx, s);
-    }
-  }
-  red[0][part][i] = mx;
-  __syncthreads();
-  float sum = 0.f;
-  if (live) {
-    mx = at_max_parts(red[0], i);
-    for (int j = part; j < AT_T; j += AT_PARTS) { const float e = __expf(Ps[i][j] - mx); Ps[i][j] = e; sum += e; }
-  }
-  red[1][part][i] = sum;
-  __syncthreads();
-  float dsum = 0.f;
-  if (live) {
-    const float inv = 1.f / at_sum_parts(red[1], i);
-    for (int j = part; j < AT_T; j += AT_PARTS) {
-      const float pj = Ps[i][j] * inv;
-      Ps[i][j] = pj;
-      dsum += pj * Ss[i][j];
-    }
-  }
-  red[2][part][i] = dsum;
-  __syncthreads();
-  if (live) {
-    dsum = at_sum_parts(red[2], i);
-    for (int j = part; j < AT_T; j += AT_PARTS) Ss[i][j] = Ps[i][j] * (Ss[i][j] - dsum) * scale;
-  }
-  __syncthreads();
-  if (!live) return;
-  // dQ row i, dK / dV row j = i: this wave's AT_COLS columns
-  const int c0 = AT_COLS * part;
-  float dq[AT_COLS], dk[AT_COLS], dv[AT_COLS];
-#pragma unroll
-  for (int c = 0; c < AT_COLS; ++c) { dq[c] = 0.f; dk[c] = 0.f; dv[c] = 0.f; }
-  for (int r = 0; r < AT_T; ++r) {
-    const float ds_q = Ss[i][r];
-    const float ds_k = Ss[r][i], pr = Ps[r][i];
-#pragma unroll
-    for (int c = 0; c < AT_COLS; ++c) {
-      dq[c] += ds_q * Ks[r][c0 + c];
-      dk[c] += ds_k * Qs[r][c0 + c];
-      dv[c] += pr * Ds[r][c0 + c];
-    }
-  }
-  float* dqp = dqkv + ((long)b * AT_T + i) * 3 * Wd + hd * AT_D + c0;
-#pragma unroll
-  for (int c = 0; c < AT_COLS; ++c) { dqp[c] = dq[c]; dqp[Wd + c] = dk[c]; dqp[2 * Wd + c] = dv[c]; }
-}
-
-// matrix-core attention (avc_vit_attn.hip); VIT_ATTN_MFMA=0 keeps the fp32 VALU kernels above (the A/B of profiles/r03_ab_kernels.txt)
-#ifndef VIT_ATTN_MFMA
-#define VIT_ATTN_MFMA 1
-#endif
+// matrix-core attention (avc_vit_attn.hip; against the fp32 VALU kernels it replaced: profiles/r03_ab_kernels.txt)
 int avc_attn_fwd_mfma(const float* qkv, float* out, int B, int width, int heads, void* stream);
 int avc_attn_bwd_mfma(const float* qkv, const float* dout, float* dqkv, int B, int width, int heads, void* stream);
 int avc_attn_fwd_mfma_packed(const float* qkv, void* out_packed, int B, int width, int heads, void* stream);
@@ -687,9 +526,7 @@ extern "C" int avc_vit_attention_fwd_packed(const float* qkv, void* out_packed, 
 
 extern "C" int avc_vit_attention_fwd(const float* qkv, float* out, int B, int T, int width, int heads, void* stream) {
   if (T != AT_T || width != heads * AT_D) { avc_set_error("avc_vit_attention: built for 50 tokens, head dim 64"); return 1; }
-  if (VIT_ATTN_MFMA) return avc_attn_fwd_mfma(qkv, out, B, width, heads, stream);
-  hipLaunchKernelGGL(vit_attn_fwd_kernel, dim3(B * heads), dim3(64 * AT_PARTS), 0, (hipStream_t)stream, qkv, out, width, heads, 0.125f);
-  return avc_check_launch("avc_vit_attention_fwd");
+  return avc_attn_fwd_mfma(qkv, out, B, width, heads, stream);
 }
 extern "C" int avc_text_attention_fwd(const float* qkv, float* out, int B, int T, int width, int heads, int causal, void* stream) {
   if (T < 1 || T > TA_TMAX || width != heads * AT_D) { avc_set_error("avc_text_attention_fwd: 1 <= T <= 128, head dim 64"); return 1; }
@@ -706,13 +543,5 @@ extern "C" int avc_text_attention_fwd(const float* qkv, float* out, int B, int T
 extern "C" int avc_vit_attention_bwd(const float* qkv, const float* dout, float* dqkv, int B, int T, int width, int heads,
                                      void* stream) {
   if (T != AT_T || width != heads * AT_D) { avc_set_error("avc_vit_attention: built for 50 tokens, head dim 64"); return 1; }
-  if (VIT_ATTN_MFMA) return avc_attn_bwd_mfma(qkv, dout, dqkv, B, width, heads, stream);
-  const size_t lds = (4 * AT_T * AT_LD + 2 * AT_T * (AT_T + 1) + 3 * AT_PARTS * 64) * sizeof(float);
-  static unsigned long long attr_seen = 0;
-  if (avc_first_use_on_device(attr_seen)) {
-    hipFuncSetAttribute((const void*)vit_attn_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  }
-  hipLaunchKernelGGL(vit_attn_bwd_kernel, dim3(B * heads), dim3(64 * AT_PARTS), lds, (hipStream_t)stream, qkv, dout, dqkv, width, heads,
-                     0.125f);
-  return avc_check_launch("avc_vit_attention_bwd");
+  return avc_attn_bwd_mfma(qkv, dout, dqkv, B, width, heads, stream);
 }

@@ -17,19 +17,10 @@
 #include "avc_common.h"
 #include "../../include/avc.h"
 
-#ifndef G2_TM
-#define G2_TM 2          // 32-row MFMA tiles per wavefront (the workgroup is 2 x 2 wavefronts: 128 x 128 outputs)
-#define G2_TN 2
-#define G2_KB 2          // 16-deep k-steps per ring slot
-#define G2_STAGES 3      // ring slots: 3 x 16 KiB
-#define G2_OCC 3         // workgroups per CU the register budget is held to
-#endif
-// Workgroups are dealt round-robin to the 8 XCDs (each with its own L2).  G2_XCD_REMAP = 1 renumbers them so that every XCD works on
-// a CONTIGUOUS range of output blocks in row-major order: the column blocks of one row block of X then share one L2 instead of
-// pulling that row block into all eight (12.8 -> 12.6 ms).
-#ifndef G2_XCD_REMAP
-#define G2_XCD_REMAP 1
-#endif
+constexpr int G2_TM = 2, G2_TN = 2;   // 32-row MFMA tiles per wavefront (the workgroup is 2 x 2 wavefronts: 128 x 128 outputs)
+constexpr int G2_KB = 2;              // 16-deep k-steps per ring slot
+constexpr int G2_STAGES = 3;          // ring slots: 3 x 16 KiB
+constexpr int G2_OCC = 3;             // workgroups per CU the register budget is held to
 
 typedef __attribute__((address_space(3))) char g2_lds_char;
 
@@ -53,14 +44,13 @@ __global__ __launch_bounds__(256, OCC) void vit_gemm_lds_kernel(const b8* __rest
   const int n = lane & 31, h = lane >> 5;
   const int wm = wv & 1, wn = wv >> 1;
   const int KS = K >> 4, NIT = KS / KB;
-#if G2_XCD_REMAP
+  // Workgroups are dealt round-robin to the 8 XCDs (each with its own L2).  They are renumbered so that every XCD works on a CONTIGUOUS
+  // range of output blocks in row-major order: the column blocks of one row block of X then share one L2 instead of pulling that row
+  // block into all eight (12.8 -> 12.6 ms, profiles/r03_score_bench.txt).
   const int ncol = gridDim.x, total = gridDim.x * gridDim.y, L = blockIdx.x + ncol * blockIdx.y;
   const int xcd = L & 7, q8 = total >> 3, r8 = total & 7;
   const int T = xcd * q8 + (xcd < r8 ? xcd : r8) + (L >> 3);
   const long mt_base = (long)(T / ncol) * AT, nt_base = (long)(T % ncol) * BT;
-#else
-  const long mt_base = (long)blockIdx.y * AT, nt_base = (long)blockIdx.x * BT;
-#endif
 
   // chunk c of a slot: fragment (tile = c / KB, k-step = c % KB); tiles 0 .. AT-1 are rows of X, the rest columns of W
   auto issue = [&](int it, int slot) {

@@ -5,15 +5,11 @@
 #define WG_TB_MAX 9
 #define WG_TILES_MAX 18
 #define WG_BUF_BYTES (WG_TILES_MAX * 2048)
-#ifndef WG_DEPTH
-#define WG_DEPTH 4   // blocks in the LDS ring: one being contracted, WG_DEPTH - 1 copies in flight
-#endif
+constexpr int WG_DEPTH = 4;   // blocks in the LDS ring: one being contracted, WG_DEPTH - 1 copies in flight
 // cache policy of the panel -> LDS copies (aux operand of global_load_lds): 2 = nt -- every tile is read exactly once by exactly one
 // workgroup.  (Measured at 4 Mi points, profiles/r03_ab_kernels.txt: nt 10.15 ms vs default 10.22; a ring as deep as the LDS allows per
 // pair -- 8 slots for the 9/10-tile products, 5 for the 15/16-tile ones -- 10.22 vs 10.23: the kernel does not lack bytes in flight.)
-#ifndef WG_DMA_AUX
-#define WG_DMA_AUX 2
-#endif
+constexpr int WG_DMA_AUX = 2;
 
 // the two operand regions (csrc/avc_mlp.h: PanelLayout): [0] = F region (forward-type, f16), [1] = G region (gradient-type, bf16)
 struct WgRegions { const char* base[2]; long stride[2]; };   // byte address of block 0 of the slab, bytes per block

@@ -1,5 +1,6 @@
 """Average duration of the CLIP attention kernels (forward, backward) at B images (development aid): python scripts/attn_time.py [B ...]
-A/B against the VALU kernels: AVC_LIB_NAME=libavc_attnvalu.so (scripts/build_variant.sh attnvalu -DVIT_ATTN_MFMA=0)."""
+A/B against another commit: AVC_LIB_NAME=libavc_ref.so (scripts/build_ref.sh).  The A/B against the fp32 VALU kernels of round 3 is
+profiles/r03_ab_kernels.txt."""
 import os, sys
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
