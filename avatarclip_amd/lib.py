@@ -10,7 +10,7 @@ from . import build as _build
 _lib = None
 ABI_VERSION = 3          # AVC_ABI_VERSION of include/avc.h this binding was written against
 
-c_int, c_long, c_float, c_void_p = ctypes.c_int, ctypes.c_long, ctypes.c_float, ctypes.c_void_p
+c_int, c_long, c_float, c_double, c_void_p = ctypes.c_int, ctypes.c_long, ctypes.c_float, ctypes.c_double, ctypes.c_void_p
 P = c_void_p
 
 _SIGS = {
@@ -76,6 +76,15 @@ _SIGS = {
     "avc_mesh_largest_island": (c_int, [P, c_int, c_int, P, P, P, P, P, P]),
     "avc_mesh_compact": (c_int, [P, P, P, c_int, c_int, P, P, P, P, P, P, P, P]),
     "avc_skin_apply": (c_int, [P, P, P, c_int, c_int, c_int, P, P]),
+    "avc_rig_cell_keys": (c_int, [P, c_int, c_double, c_double, c_double, c_double, c_int, P, P]),
+    "avc_rig_cluster_heads": (c_int, [P, c_int, P, P]),
+    "avc_rig_cluster_average": (c_int, [P, c_int, P, P, c_int, P, c_int, P, P, P, P]),
+    "avc_rig_tri_keys": (c_int, [P, c_int, c_int, P, c_int, P, P, P]),
+    "avc_rig_tri_unique": (c_int, [P, P, c_int, P, P]),
+    "avc_rig_tri_compact": (c_int, [P, c_int, P, P, c_int, P, P]),
+    "avc_skin_sort_template": (c_int, [P, c_int, c_int, P, P, P, P]),
+    "avc_skin_pack": (c_int, [P, P, P, c_int, P, c_int, c_int, P, P, P, P]),
+    "avc_rot_to_quat": (c_int, [P, c_long, P, P]),
 }
 _OPTIONAL = {}
 # experimental entry points of libavc_ring.so (include/avc_ring.h): bound when the loaded library has them

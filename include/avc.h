@@ -345,6 +345,49 @@ int avc_mesh_compact(const float* v, const unsigned* colors, const int* tris, in
  * reads nothing (avatarclip_amd/drive.py checks idx before the call). */
 int avc_skin_apply(const float* xf, const int* idx, const float* p, int M, int K, int T, float* out, void* stream);
 
+/* ---- rigging the avatar (Avatar2FBX/export_fbx.py:49-109, utils/ply_utils.py; avatarclip_amd/rig.py, csrc/avc_rig.hip) ----
+ * Empty inputs are no-ops that return 0.  No float atomics: every result is bit-identical from run to run.
+ *
+ * simplify_mesh (ply_utils.py:16-19, open3d's simplify_vertex_clustering with contraction Average) in three calls around the caller's
+ * sort and scan.
+ * avc_rig_cell_keys: keyed [N] = (cell key << 32 | vertex index), cell = floor((v - origin) / voxel_size) per axis in fp64 (these two
+ * operations, in this order), 10 bits per axis: voxel_divisor in [1, AVC_RIG_MAX_DIVISOR] (indices lie in [0, voxel_divisor + 1]).
+ * avc_rig_cluster_heads: sorted = keyed in ascending order; first_flag [N] = 1 for the first (lowest) vertex of every cell, else 0.
+ * avc_rig_cluster_average: first_rank = the exclusive prefix sum of first_flag (the caller's scan; M = its total): the cell whose first
+ * vertex is v becomes output vertex first_rank[v], so the outputs are in the order the cells are first met walking the input.  v_out [M,3]
+ * = the fp64 mean of the cell's vertices, summed in increasing input index, rounded to float32; c_out [M,3] float32 = the fp64 mean of
+ * c / 255 likewise (colors: csize = 3 or 4 bytes per vertex, the first three used; NULL: no colours); vmap [N] = each vertex's output. */
+#define AVC_RIG_MAX_DIVISOR 1022
+int avc_rig_cell_keys(const float* v, int N, double ox, double oy, double oz, double voxel_size, int voxel_divisor, long long* keyed,
+                      void* stream);
+int avc_rig_cluster_heads(const long long* sorted, int N, int* first_flag, void* stream);
+int avc_rig_cluster_average(const long long* sorted, int N, const float* v, const unsigned char* colors, int csize, const int* first_rank,
+                            int M, float* v_out, float* c_out, int* vmap, void* stream);
+/* The triangles of the clustered mesh (open3d's rules: a triangle with two corners in one cell is dropped, the others are rotated so
+ * that their smallest index comes first, exact duplicates are removed, opposite orientations both stay).
+ * avc_rig_tri_keys: tri_out [F,3] = the mapped, rotated triangle; key [F] = a << 42 | b << 21 | c, or AVC_RIG_TRI_DROP for a dropped one
+ * (also one naming a vertex outside [0, N)).  M <= AVC_RIG_MAX_KEYED_VERTICES = 2^21, else an error: three indices must fit 63 bits.
+ * avc_rig_tri_unique: sorted_key / order = the keys sorted STABLY and the permutation that sorts them (int64): tflag [F] = 1 for the
+ * first input occurrence of every surviving triangle.
+ * avc_rig_tri_compact: tid = the exclusive prefix sum of tflag, F_out its total: t_out [tid[f]] = tri_out [f], input order kept. */
+#define AVC_RIG_MAX_KEYED_VERTICES (1 << 21)
+#define AVC_RIG_TRI_DROP 0x7FFFFFFFFFFFFFFFLL
+int avc_rig_tri_keys(const int* tris, int F, int N, const int* vmap, int M, int* tri_out, long long* key, void* stream);
+int avc_rig_tri_unique(const long long* sorted_key, const long long* order, int F, int* tflag, void* stream);
+int avc_rig_tri_compact(const int* tri_in, int F, const int* tflag, const int* tid, int F_out, int* t_out, void* stream);
+/* The skin (export_fbx.py:73 the gather of the nearest template vertex's blend weights, :88 the permute to [24, M]) and its packing
+ * into glTF's JOINTS_n / WEIGHTS_n.  weights [K,24] float32 = SMPL's lbs_weights.
+ * avc_skin_sort_template: per template vertex its non-zero weights sorted by weight descending, then joint ascending: tj [K,24] uint8
+ * and tw [K,24] float32 (unused slots: joint 0, weight 0), count [K].  keep > 0: only the `keep` largest, divided by their float32 sum.
+ * avc_skin_pack: joints [sets,M,4] uint8 and wout [sets,M,4] float32 = the first 4 * sets entries of the list of nearest[m]; blend_weights
+ * [24,M] (may be NULL) = weights[nearest[m], j].  sets <= 6.  A nearest index outside [0, K) writes zeros and reads nothing. */
+int avc_skin_sort_template(const float* weights, int K, int keep, unsigned char* tj, float* tw, int* count, void* stream);
+int avc_skin_pack(const float* weights, const unsigned char* tj, const float* tw, int K, const int* nearest, int M, int sets,
+                  unsigned char* joints, float* wout, float* blend_weights, void* stream);
+/* The animation tracks (the reference's TODO "Add animation", fbx_utils.py:320): R [n,3,3] float32 rotation matrices -> q [n,4] unit
+ * quaternions (x, y, z, w) with w >= 0, Shepperd's method in fp64, rounded to float32.  q 16-byte aligned. */
+int avc_rot_to_quat(const float* R, long n, float* q, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
