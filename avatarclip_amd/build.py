@@ -7,20 +7,9 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, os.environ.get("AVC_LIB_NAME", "libavc.so"))
-# csrc/avc_bwd_ring.hip (the role-specialised backward of round 4, measured slower: profiles/r04_ring_handoff.md) is NOT part of
-# libavc.so; `build(ring=True)` / `python -m avatarclip_amd.build --ring` / AVC_WITH_RING=1 links it, with everything else, into
-# libavc_ring.so (include/avc_ring.h), which AVC_LIB_NAME=libavc_ring.so AVC_BWD_RING=1 selects.
-RING_SOURCE = "avc_bwd_ring.hip"
-RING_LIB = os.path.join(HERE, "libavc_ring.so")
 SOURCES = ["avc_core.hip", "avc_mlp_fwd.hip", "avc_mlp_bwd.hip", "avc_wgrad.hip", "avc_rays.hip", "avc_vit.hip", "avc_vit_attn.hip", "avc_vit_gemm.hip", "avc_mcubes.hip", "avc_raster.hip", "avc_raster_grad.hip", "avc_params.hip", "avc_glue.hip", "avc_drive.hip", "avc_rig.hip"]
-HEADERS = ["avc_common.h", "avc_stage.h", "avc_mlp.h", "avc_bwd_body.h", "avc_wgrad_body.h", "avc_offsets_gen.h", "avc_raster.h", os.path.join("..", "..", "include", "avc.h"),
-           os.path.join("..", "..", "include", "avc_ring.h")]
+HEADERS = ["avc_common.h", "avc_stage.h", "avc_mlp.h", "avc_bwd_body.h", "avc_offsets_gen.h", "avc_raster.h", os.path.join("..", "..", "include", "avc.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-comment"]
-# avc_mlp_fwd.hip holds the one kernel built for ONE wavefront per SIMD on the 512-entry unified register file (mlp_sdf2_kernel, 256-thread
-# workgroups): hipcc then picks the AGPR form of the MFMAs (accumulators in the accumulation half, one v_accvgpr_read per element in front of
-# every epilogue).  The VGPR form keeps the accumulators where the epilogues read them; the kernel puts the ACTIVATIONS into AGPRs itself.
-# Every other kernel of that file has 512+ threads per workgroup and uses no AGPRs either way (identical code with and without the flag).
-SOURCE_FLAGS = {"avc_mlp_fwd.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]}
 
 
 def _hipcc():
@@ -46,13 +35,10 @@ def _gen_offsets():
     mod.main()
 
 
-def build(force: bool = False, verbose: bool = False, ring: bool = False) -> str:
-    """libavc.so (or $AVC_LIB_NAME); ring=True: libavc_ring.so = the same objects + csrc/avc_bwd_ring.hip"""
+def build(force: bool = False, verbose: bool = False) -> str:
+    """libavc.so (or $AVC_LIB_NAME)"""
     _gen_offsets()
-    # AVC_LIB_NAME=libavc_ring.so makes LIB the ring library's path: a plain build() must then not relink it without its ring object
-    ring = ring or os.environ.get("AVC_WITH_RING", "0") == "1" or os.path.basename(LIB) == os.path.basename(RING_LIB)
-    target = RING_LIB if ring else LIB
-    srcs = [s for s in SOURCES + ([RING_SOURCE] if ring else []) if os.path.exists(os.path.join(CSRC, s))]
+    srcs = [s for s in SOURCES if os.path.exists(os.path.join(CSRC, s))]
     hdrs = [os.path.join(CSRC, h) for h in HEADERS]
     objs, jobs = [], []
     for s in srcs:
@@ -60,7 +46,7 @@ def build(force: bool = False, verbose: bool = False, ring: bool = False) -> str
         obj = os.path.join(CSRC, s.replace(".hip", os.environ.get("AVC_OBJ_SUFFIX", "") + ".o"))
         objs.append(obj)
         if force or _stale(obj, [src] + hdrs):
-            jobs.append([_hipcc()] + FLAGS + SOURCE_FLAGS.get(s, []) + ["-c", src, "-o", obj])
+            jobs.append([_hipcc()] + FLAGS + ["-c", src, "-o", obj])
 
     def run(cmd):
         if verbose:
@@ -72,12 +58,12 @@ def build(force: bool = False, verbose: bool = False, ring: bool = False) -> str
     if jobs:
         with ThreadPoolExecutor(max_workers=min(len(jobs), os.cpu_count() or 4)) as ex:
             list(ex.map(run, jobs))
-    if jobs or force or _stale(target, objs):
-        tmp = "%s.%d.tmp" % (target, os.getpid())       # concurrent builders: nobody ever maps a half-written library
+    if jobs or force or _stale(LIB, objs):
+        tmp = "%s.%d.tmp" % (LIB, os.getpid())       # concurrent builders: nobody ever maps a half-written library
         run([_hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-o", tmp] + objs)
-        os.replace(tmp, target)
-    return target
+        os.replace(tmp, LIB)
+    return LIB
 
 
 if __name__ == "__main__":
-    print(build(force="--force" in sys.argv, verbose=True, ring="--ring" in sys.argv))
+    print(build(force="--force" in sys.argv, verbose=True))

@@ -1,6 +1,6 @@
-// The three sweeps of the point-MLP backward for one workgroup iteration (8 wavefronts x 32 points), shared by the plain backward
-// kernel (avc_mlp_bwd.hip) and the role-specialised one (avc_bwd_ring.hip).  Mathematics: SURVEY.md A.1/A.2 (fields.py:96-107
-// double backward; autograd at main.py:537), proven against torch.autograd in tests/test_analytic.py (oracle/analytic.py).
+// The three sweeps of the point-MLP backward for one workgroup iteration (8 wavefronts x 32 points): the body of the backward
+// kernel (avc_mlp_bwd.hip).  Mathematics: SURVEY.md A.1/A.2 (fields.py:96-107 double backward; autograd at main.py:537), proven
+// against torch.autograd in tests/test_analytic.py (oracle/analytic.py).
 //
 // NOTHING of the forward pass is recomputed: the forward kernel (avc_render_points_fwd_train) left h_l, g_a,l, the ReLU masks and
 // the colours in the block's operand panels (csrc/avc_mlp.h: PanelLayout, F region).  The sweeps -- colour backward (phase D),
@@ -8,10 +8,6 @@
 // argument / g_a / gbar_h back from the panels as fragments (no transposition) and write the gradient-type operands of the
 // weight-gradient products (gbar_h, abar, delta, ybar) to the G region of the current slab.  The second-order term abar' is not
 // stored: the reverse sweep rebuilds it from the gbar_h, g_a and h tiles (abar' = gbar_h g_a beta (1-s)/s).
-//
-// `Ring` policy: NoRing = every gradient-type tile goes to the G region.  A ring policy (avc_bwd_ring.hip) takes the abar tiles of
-// the middle SDF layers instead -- they are pure hand-off tiles (written here, read only by the weight-gradient product
-// abar_m (x) h_in) -- and passes them to a consumer workgroup of the same XCD through an L2-resident ring.
 #pragma once
 #include "avc_mlp.h"
 constexpr int BWD_G = 4;     // tiles per staged group (LDS = 2 * G * 16 KiB + table: one 8-wave workgroup per CU)
@@ -157,17 +153,11 @@ __device__ __forceinline__ void load_blk_in(const BwdArgs& a, long blk, long nbl
   bi.dsdf = a.d_sdf[i] * vmask;
 }
 
-struct NoRing {
-  static constexpr bool on = false;
-  template <class N> __device__ __forceinline__ void handoff(int, const b8 (&)[N::HK], long, int, int) const {}
-};
-
 // one workgroup iteration: blocks blk0 .. blk0 + BWD_WPB - 1 (wave wv owns block blk0 + wv)
-// PIPE: `bi` holds this block's inputs on entry and the inputs of block blk0_next + wv on return (plain backward kernel only: the
-// role-specialised kernel claims its blocks dynamically and does not know the next one)
-template <class N, bool PIPE = false, class R>
+// `bi` holds this block's inputs on entry and the inputs of block blk0_next + wv on return
+template <class N>
 __device__ __forceinline__ void bwd_sweeps(StageT<BWD_G>& sg, const BwdArgs& a, lds_tab_t Tl, long blk0, long nblk, int lane0,
-                                           int wv, R& ring, cs_slot_t cs, BlkIn<N>* bip = nullptr, long blk0_next = 0) {
+                                           int wv, cs_slot_t cs, BlkIn<N>& bi, long blk0_next) {
   typedef PanelLayout<N> L;
   constexpr AvcOffsets o = Off<N>::value;
   const PointSrc& ps = a.ps;
@@ -197,9 +187,6 @@ __device__ __forceinline__ void bwd_sweeps(StageT<BWD_G>& sg, const BwdArgs& a, 
   float nbar[3];
   float dsdf_in;
   {
-    BlkIn<N> bi_local;
-    if constexpr (!PIPE) load_blk_in<N>(a, blk, nblk, lane, bi_local);
-    BlkIn<N>& bi = PIPE ? *bip : bi_local;
     b8 dof[1];
     dof[0] = bi.dof;
     tile_store<false>(tiles, L::G_DO, dof[0], zero_frag<b8>());
@@ -350,34 +337,30 @@ __device__ __forceinline__ void bwd_sweeps(StageT<BWD_G>& sg, const BwdArgs& a, 
       pin2(as_[2 * t], as_[2 * t + 1]);
       tile_store<false>(tiles, L::G_ABS + t, as_[2 * t], as_[2 * t + 1]);
     ));
-    // hbar(prev) = W^T abar(cur); abar(prev) = abar'(prev) + hbar * sigma(h_prev).  RINGED: the tile does not go to the G region
-    // (the ring policy hands the whole activation to a consumer workgroup after the layer)
-#define AVC_REVERSE(OUT, PH, PB, PG, PT, RINGED)                                                            \
+    // hbar(prev) = W^T abar(cur); abar(prev) = abar'(prev) + hbar * sigma(h_prev)
+#define AVC_REVERSE(OUT, PH, PB, PG, PT)                                                                    \
   AVC_LOAD3(PH, PB, PG),                                                                                     \
   AVC_EPID(PF3, _Pragma("unroll") for (int j = 0; j < 8; ++j) {                                              \
             const float s0 = sig_from_h((float)d.h0[j]), s1 = sig_from_h((float)d.h1[j]);                    \
             OUT[2 * t][j] = (__bf16)(second_term((float)d.b0[j], (float)d.g0[j], s0) + acc[j] * s0);         \
             OUT[2 * t + 1][j] = (__bf16)(second_term((float)d.b1[j], (float)d.g1[j], s1) + acc[8 + j] * s1); } \
           pin2(OUT[2 * t], OUT[2 * t + 1]);                                                                  \
-          if constexpr (!(RINGED)) tile_store<false>(tiles, (PT) + t, OUT[2 * t], OUT[2 * t + 1]);)
+          tile_store<false>(tiles, (PT) + t, OUT[2 * t], OUT[2 * t + 1]);)
     b8 am[N::HK];
     b8 am0[N::HK];
     const Next first = nxt<N, OFF_CHT>(sg, a.Wb0, o);   // prefetch the first tile of the next block iteration
-    // ... and, in the persistent kernel, the next block's delta_o and masks (issued after the first group barrier of the last layer)
-#define AVC_F_LASTHOOK AVC_HOOK(if constexpr (PIPE) load_blk_in<N>(a, blk0_next + wv, nblk, lane, *bip);)
+    // ... and the next block's delta_o and masks (issued after the first group barrier of the last layer)
+#define AVC_F_LASTHOOK AVC_HOOK(load_blk_in<N>(a, blk0_next + wv, nblk, lane, bi);)
     if constexpr (N::NMID == 2) {
       layer_sq1<b8, N::SK, N::HT>(sg, Wb, o.v[OFF_WST], nxt<N, OFF_WM1T>(sg, Wb, o), as_,
-                                 AVC_REVERSE(am, L::P_HM + N::HT, L::G_GBHM + N::HT, L::P_GAM + N::HT, L::G_ABM + N::HT, R::on));
-      if constexpr (R::on) ring.template handoff<N>(1, am, blk0, lane, wv);
+                                 AVC_REVERSE(am, L::P_HM + N::HT, L::G_GBHM + N::HT, L::P_GAM + N::HT, L::G_ABM + N::HT));
       layer_sq1<b8, N::HK, N::HT>(sg, Wb, o.v[OFF_WM1T], nxt<N, OFF_WM0T>(sg, Wb, o), am,
-                                 AVC_REVERSE(am0, L::P_HM, L::G_GBHM, L::P_GAM, L::G_ABM, R::on));
-      if constexpr (R::on) ring.template handoff<N>(0, am0, blk0, lane, wv);
-      layer_sq1<b8, N::HK, N::HT>(sg, Wb, o.v[OFF_WM0T], first, am0, AVC_REVERSE(am, L::P_H1, L::G_GBH1, L::P_GA1, L::G_AB1, false), AVC_F_LASTHOOK);
+                                 AVC_REVERSE(am0, L::P_HM, L::G_GBHM, L::P_GAM, L::G_ABM));
+      layer_sq1<b8, N::HK, N::HT>(sg, Wb, o.v[OFF_WM0T], first, am0, AVC_REVERSE(am, L::P_H1, L::G_GBH1, L::P_GA1, L::G_AB1), AVC_F_LASTHOOK);
     } else {
       layer_sq1<b8, N::SK, N::HT>(sg, Wb, o.v[OFF_WST], nxt<N, OFF_WM0T>(sg, Wb, o), as_,
-                                 AVC_REVERSE(am, L::P_HM, L::G_GBHM, L::P_GAM, L::G_ABM, R::on));
-      if constexpr (R::on) ring.template handoff<N>(0, am, blk0, lane, wv);
-      layer_sq1<b8, N::HK, N::HT>(sg, Wb, o.v[OFF_WM0T], first, am, AVC_REVERSE(am0, L::P_H1, L::G_GBH1, L::P_GA1, L::G_AB1, false), AVC_F_LASTHOOK);
+                                 AVC_REVERSE(am, L::P_HM, L::G_GBHM, L::P_GAM, L::G_ABM));
+      layer_sq1<b8, N::HK, N::HT>(sg, Wb, o.v[OFF_WM0T], first, am, AVC_REVERSE(am0, L::P_H1, L::G_GBH1, L::P_GA1, L::G_AB1), AVC_F_LASTHOOK);
     }
   }
 #undef AVC_RELU_BWD

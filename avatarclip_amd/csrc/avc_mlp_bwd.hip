@@ -31,12 +31,11 @@ __global__ __launch_bounds__(64 * BWD_WPB) void mlp_bwd_kernel(BwdArgs a) {
   const lds_tab_t Tl = tab_to_lds(lds + ST::LDS_BYTES, a.T0, o.v[OFF_TAB_END]);
   const cs_slot_t cs = cs_init<N>(lds + ST::LDS_BYTES + AVC_TAB_LDS_BYTES, wv, lane0);   // this wavefront's column-sum slot (csrc/avc_bwd_body.h)
   __syncthreads();
-  NoRing ring;
   // every wavefront of a workgroup runs the same number of iterations (workgroup-uniform loop bound)
   BlkIn<N> bi;     // the block's first inputs, requested one block ahead (csrc/avc_bwd_body.h)
   load_blk_in<N>(a, (long)blockIdx.x * BWD_WPB + wv, nblk, lane0, bi);
   for (long blk0 = (long)blockIdx.x * BWD_WPB; blk0 < nblk; blk0 += (long)gridDim.x * BWD_WPB)
-    bwd_sweeps<N, true>(sg, a, Tl, blk0, nblk, lane0, wv, ring, cs, &bi, blk0 + (long)gridDim.x * BWD_WPB);
+    bwd_sweeps<N>(sg, a, Tl, blk0, nblk, lane0, wv, cs, bi, blk0 + (long)gridDim.x * BWD_WPB);
   cs_flush<N>(cs, a.colsum, (long)blockIdx.x * BWD_WPB + wv, lane0);
 }
 

@@ -12,8 +12,6 @@ constexpr int FWD_G = 4;
 // the tile stores of a layer's input are dealt to ALL tile steps of the layer, not issued in one burst after its first barrier
 #define AVC_STORE_HOOK(KEEP, NT, PT, ARR) AVC_HOOKG(tiles_store_part<KEEP, NT>(tiles, PT, ARR, grp_, ngrp_);)
 #include "../../include/avc.h"
-#include <stdlib.h>
-constexpr int AVC_SDF_PPW_DEFAULT = 32;   // points per wavefront of avc_sdf_forward: 32 (mlp_sdf_kernel) | 64 (mlp_sdf2_kernel)
 
 template <class N>
 __global__ __launch_bounds__(64 * SDF_WPB) void mlp_sdf_kernel(PointSrc ps, long npts, const h8* __restrict__ Wf,
@@ -48,44 +46,6 @@ __global__ __launch_bounds__(64 * SDF_WPB) void mlp_sdf_kernel(PointSrc ps, long
   if (valid && h == 0) sdf_out[oi] = sdfv;
 }
 
-
-// ---- the same with two 32-point groups per wavefront (sdf_only2, avc_mlp.h): 4-wave workgroups, one wavefront per SIMD on the
-// ---- 512-entry unified register file; every staged weight tile serves 256 points and every LDS A fragment two MFMAs
-constexpr int SDF2_WPB = 4;
-template <class N>
-__global__ __launch_bounds__(64 * SDF2_WPB) void mlp_sdf2_kernel(PointSrc ps, long npts, const h8* __restrict__ Wf,
-                                                                 const float* __restrict__ T, float* __restrict__ sdf_out,
-                                                                 const int* __restrict__ slot, int ld_out) {
-  constexpr AvcOffsets o = Off<N>::value;
-  extern __shared__ __attribute__((aligned(16))) char lds[];
-  typedef StageT<FWD_G> ST;
-  static_assert(SDF2_WPB >= 4 && SDF2_WPB % 4 == 0, "stage_issue's turns need a multiple of 4 wavefronts per workgroup");
-  const int lane = threadIdx.x & 63;
-  const int h = lane >> 5;
-  const int p = lane & 31;
-  const long blk = 2 * ((long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6));   // this wavefront's blocks: blk, blk + 1
-  ST sg = stage_init<ST::G>(lds);
-  stage_issue(sg, nxt<N, OFF_W0>(sg, Wf, o), 0);
-  const lds_tab_t Tl = tab_to_lds(lds + ST::LDS_BYTES, T, o.v[OFF_TAB_END]);
-  __syncthreads();
-  float x[2][3];
-  long oi[2];
-  bool valid[2];
-#pragma unroll
-  for (int q = 0; q < 2; ++q) {
-    long i = (blk + q) * 32 + p;
-    valid[q] = i < npts;
-    if (!valid[q]) i = npts - 1;
-    fetch_point(ps, i, x[q]);
-    oi[q] = i;
-    if (slot) oi[q] = (i / ps.S) * ld_out + slot[i];
-  }
-  float sdfv[2];
-  sdf_only2<N>(sg, Wf, Tl, o, h, x, sdfv);
-#pragma unroll
-  for (int q = 0; q < 2; ++q)
-    if (valid[q] && h == 0) sdf_out[oi[q]] = sdfv[q];
-}
 
 // ---------------------------------------------------------------------------------------------------------------
 // avc_render_points_fwd / avc_render_points_fwd_train: sdf + normal + colour.  The normal sweep needs sigma(h_l) of every
@@ -366,19 +326,6 @@ static int launch_sdf(int net, PointSrc ps, long npts, const void* wf, const flo
   if (avc_first_use_on_device(attr_seen)) {
     hipFuncSetAttribute((const void*)mlp_sdf_kernel<NetFull>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
     hipFuncSetAttribute((const void*)mlp_sdf_kernel<NetSmall>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-    hipFuncSetAttribute((const void*)mlp_sdf2_kernel<NetFull>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-    hipFuncSetAttribute((const void*)mlp_sdf2_kernel<NetSmall>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-  }
-  // AVC_SDF_POINTS_PER_WAVE=64: the two-group kernel (A/B partner: profiles/r06_ab_kernels.txt); read once per process
-  static const int ppw = [] { const char* e = getenv("AVC_SDF_POINTS_PER_WAVE"); return e ? atoi(e) : AVC_SDF_PPW_DEFAULT; }();
-  if (ppw == 64) {
-    const int grid2 = grid_for(npts, 2 * SDF2_WPB, 0x7fffffff);
-    if (net == AVC_NET_FULL)
-      hipLaunchKernelGGL((mlp_sdf2_kernel<NetFull>), dim3(grid2), dim3(64 * SDF2_WPB), lds_bytes, s, ps, npts, (const h8*)wf, tab, sdf_out, slot, ld_out);
-    else if (net == AVC_NET_SMALL)
-      hipLaunchKernelGGL((mlp_sdf2_kernel<NetSmall>), dim3(grid2), dim3(64 * SDF2_WPB), lds_bytes, s, ps, npts, (const h8*)wf, tab, sdf_out, slot, ld_out);
-    else { avc_set_error("unknown net id"); return 1; }
-    return avc_check_launch("avc_sdf_forward");
   }
   const int wpb = SDF_WPB;   // wavefronts per workgroup
   const int grid = grid_for(npts, wpb, 0x7fffffff);

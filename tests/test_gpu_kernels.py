@@ -347,7 +347,7 @@ def test_head_fusions_equal_their_torch_statements(monkeypatch):
         monkeypatch.setattr(E, "FUSED_PACK", False)
         b = E.Packed(dl, flat)
         assert torch.equal(a.w_f16, b.w_f16) and torch.equal(a.w_bf16, b.w_bf16) and torch.equal(a.tab, b.tab)
-    from tests.ring_cases import _nets
+    from tests.engine_cases import _nets
     ren = _nets(True, dev)
     g = torch.Generator().manual_seed(2)
     R = 777
@@ -412,12 +412,12 @@ def test_grouped_upsample_kernel_equals_one_ray_per_wavefront(n, m, monkeypatch)
 @gpu
 @pytest.mark.parametrize("small,R,S,slab_blocks", [(True, 257, 48, None), (False, 4096, 64, None), (False, 4096, 64, 2048)])
 def test_fused_split_sums_and_unpacking_equal_the_torch_statement(small, R, S, slab_blocks, monkeypatch):
-    """(libavc.so's own case: it had moved into the libavc_ring.so subprocess in round 5.)  avc_weight_grad_reduce + avc_weight_grad_unpack (one launch per slab + one at the end) against the torch statement of the same
+    """avc_weight_grad_reduce + avc_weight_grad_unpack (one launch per slab + one at the end) against the torch statement of the same
     arithmetic (two reductions + two adds per slab, gather, scale, two index_adds): same products, fp32 sums in a different order;
     with several slabs the accumulate path is exercised."""
     from avatarclip_amd.engine import Engine
     dev = torch.device("cuda")
-    from tests.ring_cases import _inputs, _nets
+    from tests.engine_cases import _inputs, _nets
     ren = _nets(small, dev)
     eng = ren.engine
     if slab_blocks is not None:
@@ -439,27 +439,47 @@ def test_fused_split_sums_and_unpacking_equal_the_torch_statement(small, R, S, s
 
 
 @gpu
-def test_sdf_kernel_with_64_points_per_wavefront_equals_the_default_kernel(tmp_path):
-    """mlp_sdf2_kernel (round 6, csrc/avc_mlp.h: two 32-point groups per wavefront, one wavefront per SIMD, activations in AGPRs;
-    AVC_SDF_POINTS_PER_WAVE=64, measured 12 % slower and therefore off: profiles/r06_ab_kernels.txt) computes every point with the same
-    instruction sequence as mlp_sdf_kernel -- the values must be EQUAL BIT FOR BIT, for both nets, ragged sizes, the scatter form and the
-    point form.  The default kernel is pinned against the oracle by test_sdf_and_point_forward.  (The launcher reads the switch once
-    per process: two child processes.)"""
-    import os
-    import subprocess
-    import sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    outs = {}
-    for ppw in ("32", "64"):
-        path = str(tmp_path / ("sdf_%s.pt" % ppw))
-        r = subprocess.run([sys.executable, os.path.join(root, "tests", "sdf_ppw_child.py"), path], env=dict(os.environ, AVC_SDF_POINTS_PER_WAVE=ppw),
-                           capture_output=True, text=True, timeout=600, cwd=root)
-        assert r.returncode == 0, r.stderr[-2000:]
-        outs[ppw] = torch.load(path)
-    assert set(outs["32"]) == set(outs["64"]) and len(outs["32"]) == 24
-    for k, a in outs["32"].items():
+def test_sdf_kernel_forms_agree_at_ragged_sizes_and_tails_change_no_value():
+    """mlp_sdf_kernel (one wavefront per 32 points, 8-wave workgroup iterations of 256) on both nets at ragged sizes -- no multiple of 32 or
+    of 256 points, a single point -- in its three forms: rays, rays scattered through `slot` (cat_z_vals) and explicit points.  The scatter
+    form runs the arithmetic of the ray form and only stores elsewhere: bit for bit, and it writes nothing else.  The point form gets x
+    computed outside the kernel: atol 5e-4, the figure of test_sdf_and_point_forward, which pins the values against the oracle.  A point's
+    value does not depend on what shares its launch: padding the points to a whole workgroup iteration changes no bit of the first R * S."""
+    from tests.engine_cases import _nets
+    dev = torch.device("cuda")
+    out = {}
+    for small in (True, False):
+        ren = _nets(small, dev, seed=3)
+        with torch.no_grad():
+            for p in ren.sdf_network.parameters():
+                p.add_(torch.randn(p.shape, generator=torch.Generator().manual_seed(p.numel())).to(dev) * 0.02)
+        eng = ren.engine
+        pk = eng.pack(ren.flat_params())
+        for R, S in ((4099, 32), (333, 7), (1, 1), (65, 64)):
+            key = "%d_%d_%d" % (small, R, S)
+            g = torch.Generator().manual_seed(R * 100 + S)
+            ro = (torch.randn(R, 3, generator=g) * 0.2).to(dev)
+            rd = torch.nn.functional.normalize(torch.randn(R, 3, generator=g), dim=-1).to(dev)
+            z = torch.sort(torch.rand(R, S, generator=g) * 2, dim=-1)[0].contiguous().to(dev)
+            rays = out["rays_" + key] = eng.sdf_rays(pk, ro, rd, z).cpu()
+            slot = torch.stack([torch.randperm(S + 3, generator=g)[:S] for _ in range(R)]).int().to(dev)
+            dst = torch.zeros(R, S + 3, device=dev)
+            eng.sdf_rays(pk, ro, rd, z, sdf_out=dst, slot=slot, ld_out=S + 3)
+            dst = out["slot_" + key] = dst.cpu()
+            pts = (ro[:, None, :] + rd[:, None, :] * z[..., None]).reshape(-1, 3)
+            at_pts = out["pts_" + key] = eng.sdf_pts(pk, pts).cpu()
+            assert torch.equal(torch.gather(dst, 1, slot.cpu().long()), rays), key
+            assert int((dst != 0).sum()) <= R * S, key                       # the 3 columns per ray no slot names stay as they were
+            assert torch.allclose(at_pts.reshape(R, S), rays, atol=5e-4), (key, (at_pts.reshape(R, S) - rays).abs().max().item())
+            n = R * S
+            pad = (torch.randn((n + 255) // 256 * 256 - n, 3, generator=g) * 0.5).to(dev)
+            assert pad.shape[0] > 0
+            padded = eng.sdf_pts(pk, torch.cat([pts, pad])).cpu()
+            assert torch.equal(padded[:n], at_pts), (key, (padded[:n] - at_pts).abs().max().item())
+            assert torch.isfinite(padded).all(), key
+    assert len(out) == 24
+    for k, a in out.items():
         assert torch.isfinite(a).all() and a.abs().max() > 0, k
-        assert torch.equal(a, outs["64"][k]), (k, (a - outs["64"][k]).abs().max().item())
 
 
 @gpu

@@ -163,12 +163,9 @@ def test_c_abi_exports_every_declared_symbol():
         assert hasattr(lib, n), n
     lib.avc_version.restype = ctypes.c_int
     assert lib.avc_version() >= 1
-    # the experimental header: its entry points live in libavc_ring.so ONLY (the product library does not carry the experiment)
-    ring_names = declared("avc_ring.h")
-    assert len(ring_names) == 4 and not any(hasattr(lib, n) for n in ring_names)
-    ring = ctypes.CDLL(build.build(ring=True))
-    for n in names + ring_names:
-        assert hasattr(ring, n), n
+    # the entry points of the retired role-specialised backward (profiles/r04_ring_handoff.md) are gone from the library
+    for n in ("avc_bwd_ring_ctl_bytes", "avc_bwd_ring_payload_bytes", "avc_bwd_ring_types", "avc_render_points_bwd_ring"):
+        assert not hasattr(lib, n), n
 
 
 def test_gaussian_blur_matches_depthwise_convolution():
