@@ -189,6 +189,7 @@ class Runner:
             self.file_backup()
         self.perceptor = None
         self.prior_renderer = None
+        self._side_stream = None      # the second HIP stream of the silhouette mode's view (make_view_on_side_stream), made on first use
 
     def seed_data_rngs(self):
         """View-sharded data parallelism: the weights are identical on every rank (broadcast), the DATA must not be.  The
@@ -220,6 +221,33 @@ class Runner:
         if self.val_mesh_freq > 0 and self.iter_step % self.val_mesh_freq == 0:
             self.validate_mesh()
 
+    def _after_step(self, loss, clip_stage):
+        """main.py:240-253 / 549-563: report, checkpoint, validation, next learning rate"""
+        if self.iter_step % self.report_freq == 0 and self.rank == 0:
+            if clip_stage:
+                print(self.base_exp_dir)
+            print("iter:{:8>d} loss = {} lr={}".format(self.iter_step, loss.item(), self.optimizer.param_groups[0]["lr"]))
+        if self.iter_step % self.save_freq == 0 and self.rank == 0:
+            self.save_checkpoint()
+        self._validation_hooks(clip_stage)
+        self.update_learning_rate()
+
+    def _optimizer_step(self, loss):
+        """main.py:226-230 / 536-540: backward, one RCCL all-reduce of the flat gradient bucket (K17), the Adam step"""
+        self.optimizer.zero_grad(set_to_none=self.grad_bucket is None)
+        loss.backward()
+        if self.grad_bucket is not None:
+            self.grad_bucket.allreduce_mean()
+        self.optimizer.step()
+        self.iter_step += 1
+
+    def _white_background(self):
+        return torch.ones([1, 3], device=self.device)
+
+    def _loss_mask(self, mask):
+        """main.py:196-199 / 407-410"""
+        return (mask > 0.5).float() if self.mask_weight > 0.0 else torch.ones_like(mask)
+
     # ------------------------------------------------------------------ NeuS-init stage (main.py:180-256)
     def train(self):
         self._open_writer()
@@ -228,13 +256,7 @@ class Runner:
         image_perm = self.get_image_perm()
         for _ in range(res_step):
             data = self.dataset.gen_random_rays_at(image_perm[self.iter_step % len(image_perm)], self.batch_size)
-            loss = self.train_iteration(data)
-            if self.iter_step % self.report_freq == 0 and self.rank == 0:
-                print("iter:{:8>d} loss = {} lr={}".format(self.iter_step, loss.item(), self.optimizer.param_groups[0]["lr"]))
-            if self.iter_step % self.save_freq == 0 and self.rank == 0:
-                self.save_checkpoint()
-            self._validation_hooks(clip_stage=False)
-            self.update_learning_rate()
+            self._after_step(self.train_iteration(data), clip_stage=False)
             if self.iter_step % len(image_perm) == 0:
                 image_perm = self.get_image_perm()
         if self.writer is not None:
@@ -243,8 +265,8 @@ class Runner:
     def train_iteration(self, data):
         rays_o, rays_d, true_rgb, mask = data[:, :3], data[:, 3:6], data[:, 6:9], data[:, 9:10]
         near, far = self.dataset.near_far_from_sphere(rays_o, rays_d)
-        background_rgb = torch.ones([1, 3], device=self.device) if self.use_white_bkgd else None
-        mask = (mask > 0.5).float() if self.mask_weight > 0.0 else torch.ones_like(mask)
+        background_rgb = self._white_background() if self.use_white_bkgd else None
+        mask = self._loss_mask(mask)
         mask_sum = mask.sum() + 1e-5
         render_out = self.renderer.render(rays_o, rays_d, near, far, background_rgb=background_rgb,
                                           cos_anneal_ratio=self.get_cos_anneal_ratio())
@@ -252,12 +274,7 @@ class Runner:
         color_fine_loss = F.l1_loss(color_error, torch.zeros_like(color_error), reduction="sum") / mask_sum
         mask_loss = F.binary_cross_entropy(render_out["weight_sum"].clip(1e-3, 1.0 - 1e-3), mask)
         loss = color_fine_loss + render_out["gradient_error"] * self.igr_weight + mask_loss * self.mask_weight
-        self.optimizer.zero_grad(set_to_none=self.grad_bucket is None)
-        loss.backward()
-        if self.grad_bucket is not None:
-            self.grad_bucket.allreduce_mean()
-        self.optimizer.step()
-        self.iter_step += 1
+        self._optimizer_step(loss)
         if self.writer is not None:   # main.py:216,230-238
             with torch.no_grad():
                 psnr = 20.0 * torch.log10(1.0 / (((render_out["color_fine"] - true_rgb) ** 2 * mask).sum() / (mask_sum * 3.0)).sqrt())
@@ -351,14 +368,7 @@ class Runner:
         for iter_i in range(res_step):
             if iter_i == 30010:  # main.py:346-347
                 break
-            loss = self.train_clip_iteration(iter_i)
-            if self.iter_step % self.report_freq == 0 and self.rank == 0:
-                print(self.base_exp_dir)
-                print("iter:{:8>d} loss = {} lr={}".format(self.iter_step, loss.item(), self.optimizer.param_groups[0]["lr"]))
-            if self.iter_step % self.save_freq == 0 and self.rank == 0:
-                self.save_checkpoint()
-            self._validation_hooks(clip_stage=True)
-            self.update_learning_rate()
+            self._after_step(self.train_clip_iteration(iter_i), clip_stage=True)
         if self.writer is not None:
             self.writer.flush()
 
@@ -377,49 +387,52 @@ class Runner:
     # tests (tests/test_glue_golden.py runs the glue on fixtures produced by the reference's own lines):
     #   make_view (main.py:348-385) -> draw_background (:387-415) -> renderer.render (:417-420)
     #   -> shade_and_scatter (:422-487) -> assemble_loss (:489-534) -> backward / all-reduce / Adam (:536-538)
-    def make_view(self, iter_i, camera=None):
-        dev = self.device
-        eye, at, theta, phi, is_front = camera if camera is not None else self.sample_camera(iter_i)
-        pose = h2d.upload(lookat(eye, at, np.array([0, 1, 0])), dev)
-        prior = self.prior_renderer(eye, at)
-        true_rgb = torch.as_tensor(prior, dtype=torch.float32, device=dev)
-        if dev.type == "cuda" and os.environ.get("AVC_FUSED_HEAD", "1") != "0":
-            # rays + near / far + the prior resampled to the ray grid in one launch (dataset.rays_fused) instead of ~45
-            dilated_mask = sel_idx = None
-            if self.use_silhouettes:
-                grid = self.dataset.silhouette_grid(self.max_ray_num, true_rgb[..., 0])
-                if grid is not None:
-                    W, dilated_mask, sel_idx = grid
-                    H = W
-                else:
-                    raise RuntimeError("the prior render of this view is empty: no silhouette to sample rays in (dataset.py:262-263)")
-            else:
-                W, H = int(self.dataset.W // self.full_frame_resolution_level), int(self.dataset.H // self.full_frame_resolution_level)
-            rays_o, rays_d, near, far, true_rgb, mask = self.dataset.rays_fused(pose, W, H, sel_idx, true_rgb.reshape(true_rgb.shape[0], true_rgb.shape[1], 3))
-            ray_of_pixel = None
-            if sel_idx is not None:
-                ray_of_pixel = torch.full((H * W,), -1, dtype=torch.int32, device=dev)
-                ray_of_pixel[sel_idx] = torch.arange(sel_idx.numel(), dtype=torch.int32, device=dev)
-            return types.SimpleNamespace(eye=eye, at=at, theta=theta, phi=phi, is_front=is_front, pose=pose, H=H, W=W,
-                                         rays_o=rays_o, rays_d=rays_d, near=near, far=far, true_rgb=true_rgb, mask=mask,
-                                         dilated_mask=dilated_mask, sel_idx=sel_idx, ray_of_pixel=ray_of_pixel, mask_binary=True)
-        ori_mask = (true_rgb != 0).float()[..., 0]
+    def _fused_head(self):
+        """AVC_FUSED_HEAD, read per call (tests/test_gpu_glue.py flips it on one Runner): the view's rays and the chess-board
+        background out of one launch each; 0 (or no GPU) = the torch statements"""
+        return self.device.type == "cuda" and os.environ.get("AVC_FUSED_HEAD", "1") != "0"
+
+    def _view_head_fused(self, pose, prior):
+        """rays + near / far + the prior resampled to the ray grid in one launch (dataset.rays_fused) instead of ~45"""
+        dilated_mask = sel_idx = None
+        if self.use_silhouettes:
+            grid = self.dataset.silhouette_grid(self.max_ray_num, prior[..., 0])
+            if grid is None:
+                raise RuntimeError("the prior render of this view is empty: no silhouette to sample rays in (dataset.py:262-263)")
+            W, dilated_mask, sel_idx = grid
+            H = W
+        else:
+            W, H = int(self.dataset.W // self.full_frame_resolution_level), int(self.dataset.H // self.full_frame_resolution_level)
+        rays_o, rays_d, near, far, true_rgb, mask = self.dataset.rays_fused(pose, W, H, sel_idx, prior.reshape(prior.shape[0], prior.shape[1], 3))
+        return H, W, rays_o, rays_d, near, far, true_rgb, mask, dilated_mask, sel_idx
+
+    def _view_head_torch(self, pose, prior):
+        """main.py:360-380 as torch statements: the parity reference of the fused head, and the CPU path"""
         dilated_mask = sel_idx = None
         if self.use_silhouettes:
             self.dataset.last_sel_idx = None
-            rays_o, rays_d, W, dilated_mask = self.dataset.gen_rays_silhouettes(pose, self.max_ray_num, ori_mask)
-            sel_idx = getattr(self.dataset, "last_sel_idx", None)
+            rays_o, rays_d, W, dilated_mask = self.dataset.gen_rays_silhouettes(pose, self.max_ray_num, (prior != 0).float()[..., 0])
+            sel_idx = self.dataset.last_sel_idx
             H = W
             rays_o, rays_d = rays_o.float(), rays_d.float()
         else:
             rays_o, rays_d = self.dataset.gen_rays_pose(pose, self.full_frame_resolution_level)
             H, W = rays_o.shape[0], rays_o.shape[1]
             rays_o, rays_d = rays_o.reshape(H * W, 3).float(), rays_d.reshape(H * W, 3).float()
-        Hp, Wp = true_rgb.shape[0], true_rgb.shape[1]
-        true_rgb = F.interpolate(true_rgb.reshape(Hp, Wp, 3).permute(2, 0, 1).unsqueeze(0), size=(H, W)) \
+        Hp, Wp = prior.shape[0], prior.shape[1]
+        true_rgb = F.interpolate(prior.reshape(Hp, Wp, 3).permute(2, 0, 1).unsqueeze(0), size=(H, W)) \
             .squeeze(0).permute(1, 2, 0).reshape(-1, 3)                                        # main.py:376-377 (nearest)
         mask = (true_rgb != 0).float()[..., :1]
         near, far = self.dataset.near_far_from_sphere(rays_o, rays_d)
+        return H, W, rays_o, rays_d, near, far, true_rgb, mask, dilated_mask, sel_idx
+
+    def make_view(self, iter_i, camera=None):
+        dev = self.device
+        eye, at, theta, phi, is_front = camera if camera is not None else self.sample_camera(iter_i)
+        pose = h2d.upload(lookat(eye, at, np.array([0, 1, 0])), dev)
+        prior = torch.as_tensor(self.prior_renderer(eye, at), dtype=torch.float32, device=dev)
+        head = self._view_head_fused if self._fused_head() else self._view_head_torch
+        H, W, rays_o, rays_d, near, far, true_rgb, mask, dilated_mask, sel_idx = head(pose, prior)
         ray_of_pixel = None
         if sel_idx is not None and dev.type == "cuda":     # pixel -> ray (or -1): what the fused glue scatters with (glue.ShadeLossFn)
             ray_of_pixel = torch.full((H * W,), -1, dtype=torch.int32, device=dev)
@@ -429,13 +442,10 @@ class Runner:
                                      dilated_mask=dilated_mask, sel_idx=sel_idx, ray_of_pixel=ray_of_pixel, mask_binary=True)
 
     def _take_view(self, iter_i, camera=None):
-        """the view of this iteration: the one prefetch_view prepared, or a fresh one (silhouette mode: on the side stream)"""
-        fut, self._view_future = getattr(self, "_view_future", None), None
-        if fut is not None:
-            view = fut[1].result()              # (always collected: the helper thread must not run into the next make_view)
-            if camera is None and fut[0] == iter_i:
-                return self._adopt_view(view)
-        return self.make_view_on_side_stream(iter_i, camera) if self.use_silhouettes else self.make_view(iter_i, camera)
+        """the view of this iteration: in silhouette mode on the GPU it is built on the side stream (AVC_OVERLAP_HEAD=0: on one stream)"""
+        if self.use_silhouettes and self.device.type == "cuda" and os.environ.get("AVC_OVERLAP_HEAD", "1") != "0":
+            return self.make_view_on_side_stream(iter_i, camera)
+        return self.make_view(iter_i, camera)
 
     def make_view_on_side_stream(self, iter_i, camera=None):
         """make_view for the silhouette mode, enqueued on a second HIP stream.  The ray set of that mode has a data-dependent size, so
@@ -446,69 +456,16 @@ class Runner:
         is unchanged; the main stream waits for the view's event before its first use, and every tensor of the view is registered
         with the main stream so the caching allocator does not hand its memory back to the side stream while main-stream kernels
         still read it.  (In full-frame mode there is nothing to gain: no round trips, and small kernels do not become resident beside
-        the persistent MLP kernels -- profiles/r03_side_stream.txt.)  AVC_OVERLAP_HEAD=0: everything on one stream."""
-        if self.device.type != "cuda" or os.environ.get("AVC_OVERLAP_HEAD", "1") == "0":
-            return self.make_view(iter_i, camera)
-        return self._make_view_side(iter_i, camera)
-
-    # ---- the next iteration's view, prepared beside this iteration's CLIP pass
-    def _prefetch_allowed(self, iter_i):
-        """The camera of iteration i + 1 may be drawn inside iteration i only when NOTHING draws from the host's numpy generator between
-        the two in main.py's order: not when the validation hooks fire after this iteration (validate_image picks a random view,
-        main.py:741-744), not on the last iteration of the run or at the reference's iter_i == 30010 break (a left-over view would have
-        consumed draws the reference never makes).  Off unless AVC_PREFETCH_VIEW=1."""
-        if (self.device.type != "cuda" or os.environ.get("AVC_PREFETCH_VIEW", "0") != "1" or os.environ.get("AVC_OVERLAP_HEAD", "1") == "0"):
-            return False
-        nxt = self.iter_step + 1          # the step count the hooks of THIS iteration will see
-        if (self.val_freq > 0 and nxt % self.val_freq == 0) or (self.val_mesh_freq > 0 and nxt % self.val_mesh_freq == 0):
-            return False
-        return nxt < self.end_iter and iter_i + 1 != 30010
-
-    def prefetch_view(self, iter_i, after=None):
-        """Start make_view(iter_i) for the NEXT iteration on the side stream.  The view depends on nothing the optimiser writes, and
-        its ~100-140 small kernels (camera, prior rasterisation, rays; 1.0-1.3 ms of GPU time) fit beside the only other stretch of
-        small kernels in the iteration -- the CLIP pass, 24-96 workgroups on a 256-CU chip -- whereas beside the persistent MLP kernels
-        nothing becomes resident (profiles/r03_side_stream.txt, r04_ab_kernels.txt).  clip_loss() calls this right before it launches
-        CLIP, when every numpy draw of the current iteration (background, light, ambience) has been made: the camera of iteration
-        i + 1 is drawn HERE, in the caller's thread, exactly where main.py:348-358 would draw it next -- clip_loss skips the prefetch on
-        the iterations where something else draws in between (_prefetch_allowed: validation hooks, end of the run) -- so the draw order is
-        unchanged.
-        `after` = an event on the main stream the side stream waits for (the end of the render + shading work), so that the view's
-        kernels start when the GPU reaches CLIP.  In silhouette mode make_view makes two round trips to the host (pixel counts -> ray
-        grid -> ray count): a helper thread does that waiting.  Injected cameras (tests) bypass it.  OPT-IN (AVC_PREFETCH_VIEW=1):
-        measured, the two streams of small kernels hardly overlap -- 6.3 vs 6.6 ms per iteration at 7 000 silhouette rays, but 9.27 vs
-        9.14 at 12 544, 26.98 vs 26.85 at 224^2, 121.8 vs 122.1 at 512^2 (profiles/r04_ab_kernels.txt)."""
-        if (self.device.type != "cuda" or os.environ.get("AVC_PREFETCH_VIEW", "0") != "1" or os.environ.get("AVC_OVERLAP_HEAD", "1") == "0"
-                or getattr(self, "_view_future", None) is not None):
-            return
-        camera = self.sample_camera(iter_i)
-        if self.use_silhouettes:
-            if getattr(self, "_view_pool", None) is None:
-                from concurrent.futures import ThreadPoolExecutor
-                self._view_pool = ThreadPoolExecutor(max_workers=1, thread_name_prefix="avc-view")
-            self._view_future = (iter_i, self._view_pool.submit(self._make_view_side, iter_i, camera, False, after))
-        else:
-            self._view_future = (iter_i, _Done(self._make_view_side(iter_i, camera, False, after)))
-
-    def _make_view_side(self, iter_i, camera, adopt=True, after=None):
+        the persistent MLP kernels -- profiles/r03_side_stream.txt.)"""
         main = torch.cuda.current_stream(self.device)
-        side = getattr(self, "_side_stream", None)
-        if side is None:
-            side = self._side_stream = torch.cuda.Stream(device=self.device)
-            side.wait_stream(main)       # first use: whatever initialisation is still in flight on the main stream
-        if after is not None:
-            side.wait_event(after)
-        with torch.cuda.device(self.device), torch.cuda.stream(side):
+        if self._side_stream is None:
+            self._side_stream = torch.cuda.Stream(device=self.device)
+            self._side_stream.wait_stream(main)       # first use: whatever initialisation is still in flight on the main stream
+        with torch.cuda.device(self.device), torch.cuda.stream(self._side_stream):
             view = self.make_view(iter_i, camera)
-            view.ready = torch.cuda.Event()
-            view.ready.record(side)
-        return self._adopt_view(view) if adopt else view
-
-    def _adopt_view(self, view):
-        """the consuming (main) stream waits for the view's event; every tensor of the view is registered with it so that the
-        caching allocator does not hand the memory back to the side stream while main-stream kernels still read it"""
-        main = torch.cuda.current_stream(self.device)
-        main.wait_event(view.ready)
+            ready = torch.cuda.Event()
+            ready.record(self._side_stream)
+        main.wait_event(ready)
         for t in vars(view).values():
             if torch.is_tensor(t) and t.is_cuda:
                 t.record_stream(main)
@@ -521,7 +478,7 @@ class Runner:
         if choice_i is None:
             choice_i = np.random.choice(4) if self.use_bg_aug else 3
         if choice_i == 0:
-            background_rgb = torch.ones([1, 3], device=dev)
+            background_rgb = self._white_background()
         elif choice_i == 1:
             # (= torch.normal(zeros + 0.5, zeros + 0.2), main.py:393-394, draw for draw -- without the host-side check of the std TENSOR
             # that form makes, a stream synchronisation; test_gpu_iteration compares the two on the device)
@@ -530,8 +487,7 @@ class Runner:
         elif choice_i == 2:
             chess_length = H // np.random.choice(np.arange(10, 20))
             sigma = torch.empty(1).uniform_(0.1, 2.0).item()   # torchvision GaussianBlur.get_params: torch CPU RNG
-            background_rgb = chess_background_fused(H, W, chess_length, sigma, dev) if dev.type == "cuda" and os.environ.get("AVC_FUSED_HEAD", "1") != "0" \
-                else chess_background(H, W, chess_length, sigma, dev)
+            background_rgb = (chess_background_fused if self._fused_head() else chess_background)(H, W, chess_length, sigma, dev)
         if self.use_silhouettes and choice_i in (1, 2):
             idx = getattr(view, "sel_idx", None)      # (gather by index: boolean-mask indexing would synchronise the stream for the count)
             masked_background_rgb = background_rgb.reshape(-1, 1).index_select(0, idx) if idx is not None else \
@@ -539,6 +495,29 @@ class Runner:
         else:
             masked_background_rgb = background_rgb
         return choice_i, background_rgb, masked_background_rgb
+
+    def _draw_light(self, view):
+        """main.py:433, :440 -> (light_dir[3], ambience): a random light around the camera and a random ambience, the numpy draws in the
+        reference's order (theta offset, phi offset, ambience).  The reference makes the third draw a few device statements after the
+        first two; no other host draw lies between them, so drawing the three together leaves the sequence camera -> background ->
+        light -> ambience of an iteration unchanged."""
+        light_dir = sphere_coord(view.theta + np.random.uniform(-np.pi / 4, np.pi / 4), view.phi + np.random.uniform(-np.pi / 4, np.pi / 4))
+        return light_dir, np.random.uniform(0, 0.2)
+
+    def _weighted_normals(self, render_out):
+        """main.py:427-429: sum of the sample normals under the compositing weights; renderer.RenderOut carries the same sum out of the compositing kernel"""
+        normals = getattr(render_out, "weighted_normals", None)
+        if normals is None:
+            normals = (render_out["gradients"] * render_out["weights"][:, :, None]).sum(dim=1)
+        return normals
+
+    def _prompt_for(self, iter_i, view):
+        """main.py:499-507: the face prompt on the face camera's iterations, the back prompt behind the body, else the prompt"""
+        if self.use_face_prompt and iter_i % 4 == 0:
+            return self.encoded_face_text
+        if self.use_back_prompt and view.is_front == 0:
+            return self.encoded_back_text
+        return self.encoded_text
 
     def shade_and_scatter(self, render_out, view, choice_i, background_rgb, light=None):
         """main.py:422-487: Lambert shading from the rendered normals (random light around the camera, random ambience),
@@ -549,20 +528,13 @@ class Runner:
         extra_color_fine = render_out["extra_color_fine"]
         texture_shading = rand_shading_rgb = None
         if self.add_no_texture or self.texture_cast_light:
-            normals = getattr(render_out, "weighted_normals", None)      # the same sum out of the compositing kernel (renderer.RenderOut)
-            if normals is None:
-                normals = (render_out["gradients"] * render_out["weights"][:, :, None]).sum(dim=1)
+            light_dir, ambience = self._draw_light(view) if light is None else (np.asarray(light[0]), float(light[1]))
+            normals = self._weighted_normals(render_out)
             normals = normals / (torch.norm(normals, dim=-1, keepdim=True) + 1e-7)
-            if light is None:
-                light_dir = sphere_coord(view.theta + np.random.uniform(-np.pi / 4, np.pi / 4),
-                                         view.phi + np.random.uniform(-np.pi / 4, np.pi / 4))
-            else:
-                light_dir = np.asarray(light[0])
             rand_light_d = torch.zeros_like(normals) + h2d.upload(np.asarray(light_dir), dev)
             rand_light_d = rand_light_d / (torch.norm(rand_light_d, dim=-1, keepdim=True) + 1e-7)
             rand_diffuse_shading = (normals * rand_light_d).sum(-1, keepdim=True).clamp(min=0, max=1)
             rand_diffuse_shading = torch.where(torch.isnan(rand_diffuse_shading), torch.ones_like(rand_diffuse_shading), rand_diffuse_shading)
-            ambience = np.random.uniform(0, 0.2) if light is None else float(light[1])
             rand_shading = ambience + (1 - ambience) * rand_diffuse_shading
             ws = render_out["weight_sum"].reshape(-1)
             bgm = (ws < 0.5)[:, None]
@@ -597,7 +569,7 @@ class Runner:
     def assemble_loss(self, render_out, comp, view, iter_i):
         """main.py:489-534."""
         H, W = view.H, view.W
-        mask = (view.mask > 0.5).float() if self.mask_weight > 0.0 else torch.ones_like(view.mask)
+        mask = self._loss_mask(view.mask)
         mask_sum = mask.sum() + 1e-5
         color_error = (comp["color_fine"] - view.true_rgb) * mask
         color_fine_loss = F.l1_loss(color_error, torch.zeros_like(color_error), reduction="sum") / mask_sum
@@ -607,12 +579,7 @@ class Runner:
                 psnr = 20.0 * torch.log10(1.0 / (((comp["color_fine"] - view.true_rgb) ** 2 * mask).sum() / (mask_sum * 3.0)).sqrt())
         eikonal_loss = render_out["gradient_error"]
         mask_loss = F.binary_cross_entropy(comp["weight_sum"].clip(1e-3, 1.0 - 1e-3), mask)
-        if self.use_face_prompt and iter_i % 4 == 0:
-            text = self.encoded_face_text
-        elif self.use_back_prompt and view.is_front == 0:
-            text = self.encoded_back_text
-        else:
-            text = self.encoded_text
+        text = self._prompt_for(iter_i, view)
         img = comp["texture_shading"] if self.texture_cast_light else comp["extra_color_fine"]
         if self.add_no_texture:
             # main.py:512 and :524 encode the two images in two calls; the encoder treats batch entries independently, so
@@ -641,16 +608,9 @@ class Runner:
         shading = self.add_no_texture or self.texture_cast_light
         light4 = nsum = None
         if shading:
-            if light is None:
-                light_dir = sphere_coord(view.theta + np.random.uniform(-np.pi / 4, np.pi / 4),
-                                         view.phi + np.random.uniform(-np.pi / 4, np.pi / 4))
-                ambience = np.random.uniform(0, 0.2)
-            else:
-                light_dir, ambience = np.asarray(light[0]), float(light[1])
+            light_dir, ambience = self._draw_light(view) if light is None else (np.asarray(light[0]), float(light[1]))
             light4 = h2d.upload(glue.unit_light(light_dir, ambience), dev)
-            nsum = getattr(render_out, "weighted_normals", None)
-            if nsum is None:
-                nsum = (render_out["gradients"] * render_out["weights"][:, :, None]).sum(dim=1)
+            nsum = self._weighted_normals(render_out)
         bg, bg_const, rop = None, 0.0, None
         if self.use_silhouettes:
             rop = view.ray_of_pixel
@@ -658,10 +618,8 @@ class Runner:
                 bg_const = 1.0
             elif choice_i in (1, 2):
                 bg = background_rgb.reshape(-1)
-        if self.mask_weight > 0.0:      # main.py:489: (mask > 0.5).float() -- the identity on the 0 / 1 masks make_view produces
-            mask = view.mask if getattr(view, "mask_binary", False) else (view.mask > 0.5).float()
-        else:
-            mask = torch.ones_like(view.mask)
+        # main.py:489: (mask > 0.5).float() is the identity on the 0 / 1 masks make_view produces
+        mask = view.mask if self.mask_weight > 0.0 and getattr(view, "mask_binary", False) else self._loss_mask(view.mask)
         images, sums = glue.ShadeLossFn.apply(
             render_out["color_fine"], render_out["extra_color_fine"], render_out["weight_sum"].reshape(-1), nsum, view.true_rgb,
             mask.reshape(-1), rop, bg, bg_const, light4, not self.texture_cast_light)
@@ -670,12 +628,7 @@ class Runner:
             with torch.no_grad():
                 psnr = 20.0 * torch.log10(1.0 / (sums[3] / ((sums[1] + 1e-5) * 3.0)).sqrt())
         eikonal_loss = render_out["gradient_error"]
-        if self.use_face_prompt and iter_i % 4 == 0:
-            text = self.encoded_face_text
-        elif self.use_back_prompt and view.is_front == 0:
-            text = self.encoded_back_text
-        else:
-            text = self.encoded_text
+        text = self._prompt_for(iter_i, view)
         B = 2 if self.add_no_texture else 1
         enc_both = self.perceptor.encode_image(glue.ResizeNormFn.apply(images[:B].reshape(B, H, W, 3)))
         # main.py:491-534 from here on (colour / mask normalisation, the cosines, the weighted sum) in one launch: glue.LossTailFn
@@ -692,21 +645,9 @@ class Runner:
         fused = (self.device.type == "cuda" and os.environ.get("AVC_FUSED_GLUE", "1") != "0"
                  and not (self.use_silhouettes and getattr(view, "ray_of_pixel", None) is None))
         if fused:
-            # (its host draws -- light direction, ambience -- come first, as in shade_and_scatter; the prefetch draws the next camera)
-            light = None
-            if self.add_no_texture or self.texture_cast_light:
-                light = (sphere_coord(view.theta + np.random.uniform(-np.pi / 4, np.pi / 4), view.phi + np.random.uniform(-np.pi / 4, np.pi / 4)),
-                         np.random.uniform(0, 0.2))
+            loss, parts, _ = self.fused_shade_loss(render_out, view, choice_i, background_rgb, iter_i)
         else:
             comp = self.shade_and_scatter(render_out, view, choice_i, background_rgb)
-        if camera is None and self._prefetch_allowed(iter_i):
-            # every host draw of this iteration is made: the next view is prepared beside the CLIP pass that follows
-            reached = torch.cuda.Event()
-            reached.record(torch.cuda.current_stream(self.device))
-            self.prefetch_view(iter_i + 1, after=reached)
-        if fused:
-            loss, parts, _ = self.fused_shade_loss(render_out, view, choice_i, background_rgb, iter_i, light=light)
-        else:
             loss, parts = self.assemble_loss(render_out, comp, view, iter_i)
         self.last_view = view
         return loss, parts
@@ -716,12 +657,7 @@ class Runner:
         if release is not None:
             release()     # a graph-replayed encode_image of an earlier iteration that never reached backward (exception, probe call) does not hold its instance
         loss, parts = self.clip_loss(iter_i, camera)
-        self.optimizer.zero_grad(set_to_none=self.grad_bucket is None)
-        loss.backward()
-        if self.grad_bucket is not None:
-            self.grad_bucket.allreduce_mean()     # one RCCL all-reduce per step (K17)
-        self.optimizer.step()
-        self.iter_step += 1
+        self._optimizer_step(loss)
         self.last_stats = dict(loss=loss.detach(), color=parts["color"].detach(), eikonal=parts["eikonal"].detach(),
                                cosine=parts["cosine"].detach(), rays=self.last_view.rays_o.shape[0], s_val=parts["s_val"], psnr=parts["psnr"])
         if self.writer is not None:   # main.py:542-547
@@ -818,7 +754,7 @@ class Runner:
         """render() over chunks of rays without keeping a graph (main.py:752-783 and its siblings); returns dict of cats."""
         chunk = chunk or self.batch_size * 16     # the kernels want >= a few thousand rays per launch; the result is chunk-invariant
         outs = {k: [] for k in keys}
-        bg = torch.ones([1, 3], device=self.device) if self.use_white_bkgd else None
+        bg = self._white_background() if self.use_white_bkgd else None
         for o, d in zip(rays_o.split(chunk), rays_d.split(chunk)):
             near, far = self.dataset.near_far_from_sphere(o, d)
             with torch.no_grad():
@@ -943,7 +879,7 @@ class Runner:
             rgbs, diffs = [], []
             for ro, rd, di in zip(ro_all.split(chunk), rd_all.split(chunk), dist.split(chunk)):
                 near, far = self.dataset.near_far_from_sphere(ro, rd)
-                bg = torch.ones([1, 3], device=self.device) if self.use_white_bkgd else None
+                bg = self._white_background() if self.use_white_bkgd else None
                 with torch.no_grad():
                     out = self.renderer.render(ro.contiguous(), rd.contiguous(), near, far,
                                                cos_anneal_ratio=self.get_cos_anneal_ratio(), background_rgb=bg)
@@ -962,16 +898,6 @@ class Runner:
         mesh.write_ply(path, vertices, triangles, colors)
         logging.info("mesh: %d vertices, %d triangles -> %s", vertices.shape[0], triangles.shape[0], path)
         return path
-
-
-class _Done:
-    """a finished future (the full-frame view needs no helper thread: no round trips to wait for)"""
-
-    def __init__(self, value):
-        self._v = value
-
-    def result(self):
-        return self._v
 
 
 def clip_vit_random_state_dict(seed):

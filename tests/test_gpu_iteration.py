@@ -318,18 +318,20 @@ def test_train_clip_iteration_with_silhouette_rays_and_background_augmentation()
 
 
 @gpu
-@pytest.mark.parametrize("silhouettes", [True, False])
-def test_prefetched_views_keep_the_draw_order_and_the_losses(monkeypatch, silhouettes):
-    """Runner.prefetch_view (the next iteration's view prepared on the side stream beside this iteration's CLIP pass; in silhouette
-    mode a helper thread makes its two round trips): same cameras, same ray sets, same background choices and the same losses as the
-    run that prepares every view at the start of its own iteration -- the numpy draw order of main.py:348-440 is untouched."""
+def test_side_stream_view_keeps_the_draw_order_and_the_losses(monkeypatch):
+    """Runner.make_view_on_side_stream (silhouette mode: the iteration's view enqueued on a second HIP stream, the shipped default): same
+    cameras, same ray sets, same background choices and the same losses as the run that builds every view on the main stream
+    (AVC_OVERLAP_HEAD=0) -- the numpy draw order of main.py:348-440 is untouched.  (Full-frame mode uses no side stream.)"""
     import bench
     from avatarclip_amd.runner import Runner
 
-    def run(prefetch):
-        monkeypatch.setenv("AVC_PREFETCH_VIEW", "1" if prefetch else "0")
-        conf = bench.make_conf(256 if silhouettes else 48, 32, small=True)
-        conf.put("train.use_silhouettes", silhouettes)
+    def run(overlap):
+        if overlap:
+            monkeypatch.delenv("AVC_OVERLAP_HEAD", raising=False)
+        else:
+            monkeypatch.setenv("AVC_OVERLAP_HEAD", "0")
+        conf = bench.make_conf(256, 32, small=True)
+        conf.put("train.use_silhouettes", True)
         conf.put("train.max_ray_num", 3000)
         conf.put("train.warm_up_end", 0)
         torch.manual_seed(0)
@@ -343,7 +345,7 @@ def test_prefetched_views_keep_the_draw_order_and_the_losses(monkeypatch, silhou
             loss = r.train_clip_iteration(i)
             rec.append((np.asarray(r.last_view.eye).copy(), int(r.last_stats["rays"]), float(loss)))
             r.update_learning_rate()
-        assert (getattr(r, "_view_future", None) is not None) == prefetch
+        assert (r._side_stream is not None) == overlap
         return rec
     a, b = run(True), run(False)
     for (e1, n1, l1), (e2, n2, l2) in zip(a, b):
