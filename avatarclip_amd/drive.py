@@ -2,10 +2,11 @@
 on the device.
 
     python -m avatarclip_amd.drive --mesh X.ply --motion motion.npy --smpl SMPL.npz|pkl --pose_npy stand_pose.npy --out_dir D
-                                   [--name General] [--motion_name NAME]
+                                   [--name General] [--motion_name NAME] [--preview]
 
 writes D/<name>_cleaned_apose.ply (the largest island of the rotated mesh, colours kept) and D/<motion_name>.pc2 (T frames of the re-posed
-mesh), the reference's hard-coded paths turned into arguments.  The steps and their reference functions:
+mesh), the reference's hard-coded paths turned into arguments; with --preview also D/<name>_preview.gif, the motion played by
+avatarclip_amd.preview.  The steps and their reference functions:
   rotate (x, y, z) -> (x, -z, y)                        drive.py:317-324
   cleanup_mesh       largest island                      :172-210   csrc/avc_drive.hip (components, island choice, compaction)
   load_template_smpl SMPL template in the stand pose     :223-233   smpl_lbs.lbs (betas = 0, pose blend shapes included)
@@ -288,10 +289,14 @@ def main(argv=None):
     ap.add_argument("--out_dir", required=True)
     ap.add_argument("--name", default="General")
     ap.add_argument("--motion_name", default=None, help="base name of the .pc2 (default: the motion file's)")
+    ap.add_argument("--preview", action="store_true", help="also play the .pc2 into <out_dir>/<name>_preview.gif (avatarclip_amd.preview)")
     args = ap.parse_args(argv)
     ply, pc2 = generate_animation(args.mesh, args.motion, args.smpl, args.pose_npy, args.out_dir, name=args.name, motion_name=args.motion_name)
     print(ply)
     print(pc2)
+    if args.preview:
+        from . import preview
+        print(preview.preview(os.path.join(args.out_dir, "%s_preview.gif" % args.name), mesh=ply, pc2=pc2)[0])
 
 
 if __name__ == "__main__":

@@ -85,6 +85,11 @@ _SIGS = {
     "avc_skin_sort_template": (c_int, [P, c_int, c_int, P, P, P, P]),
     "avc_skin_pack": (c_int, [P, P, P, c_int, P, c_int, c_int, P, P, P, P]),
     "avc_rot_to_quat": (c_int, [P, c_long, P, P]),
+    "avc_preview_scratch_bytes": (c_long, [c_int, c_int]),
+    "avc_preview_project": (c_int, [P, c_int, c_int, P, c_float, c_float, c_float, c_int, P, P]),
+    "avc_preview_raster": (c_int, [P, c_int, c_int, P, c_int, c_int, P, P]),
+    "avc_preview_shade": (c_int, [P, P, c_int, c_int, P, c_int, P, c_int, P, c_float, c_float, c_float, c_float, c_float, c_int, c_int, P, P, P, P]),
+    "avc_skin_blend4": (c_int, [P, P, P, P, c_int, c_int, c_int, P, P]),
 }
 _OPTIONAL = {}
 

@@ -2,7 +2,7 @@
 
     python -m avatarclip_amd.rig --mesh X.ply --smpl SMPL.npz|pkl --pose_npy stand_pose.npy --out_dir D
                                  [--name NAME] [--motion motion.npy] [--fps 60] [--voxel_divisor 256] [--no_simplify]
-                                 [--cleanup] [--max_influences K] [--scale 1.0] [--keep_root]
+                                 [--cleanup] [--max_influences K] [--scale 1.0] [--keep_root] [--preview]
 
 writes D/<name>.glb (mesh, vertex colours, the 24-joint SMPL skeleton under Mixamo's bone names, the skin, and with --motion one rotation
 track per joint) and D/<name>_rig.npz (the reference's `smpl_object`, export_fbx.py:102-109, under its own keys and shapes, plus `nearest`
@@ -18,8 +18,11 @@ The steps and their reference lines:
   animation          the reference's TODO (fbx_utils.py:320)    drive.read_pose_my -> avc_rot_to_quat; this port's extension
 Choices this port makes where the reference leaves one open: the triangle order of the simplified mesh (open3d's comes out of a hash set)
 is the order of each surviving triangle's first occurrence in the input; the file carries ALL non-zero weights of a vertex, in as many
-JOINTS_n / WEIGHTS_n sets as the fullest vertex needs, unless --max_influences cuts them.  Which way up a viewer shows the file has not
-been checked on any viewer: the mesh is stored in SMPL's T-pose frame and the tracks carry drive's root rotation (pi/2, 0, 0)."""
+JOINTS_n / WEIGHTS_n sets as the fullest vertex needs, unless --max_influences cuts them.  The mesh is stored in SMPL's T-pose frame (y
+up) and the tracks carry drive's root rotation (pi/2, 0, 0), which turns the PLAYED avatar into Blender's frame (z up, as drive's .pc2):
+this project's own renderer (avatarclip_amd.preview) shows the rest pose upright with --up y and a played track upright with --up z, so
+a viewer that takes glTF's y-up convention at its word would show the motion lying down unless --keep_root is given.  --preview renders
+the file into D/<name>_preview.gif with the up axis that fits what was written.  No third-party viewer has been tried."""
 import argparse
 import json
 import os
@@ -462,6 +465,7 @@ def main(argv=None):
     ap.add_argument("--max_influences", type=int, default=0, help="keep the K largest weights per vertex and renormalise (0: all)")
     ap.add_argument("--scale", type=float, default=1.0, help="unit of the .glb: 1.0 = metres (glTF's), 100 = the reference's centimetres")
     ap.add_argument("--keep_root", action="store_true", help="keep the motion's own root rotation instead of drive's (pi/2, 0, 0)")
+    ap.add_argument("--preview", action="store_true", help="also render the .glb into <out_dir>/<name>_preview.gif (avatarclip_amd.preview)")
     args = ap.parse_args(argv)
     name = args.name or os.path.splitext(os.path.basename(args.mesh))[0]
     glb, npz = build_rig(args.mesh, args.smpl, args.pose_npy, args.out_dir, name=name, motion=args.motion, fps=args.fps,
@@ -469,6 +473,11 @@ def main(argv=None):
                          max_influences=args.max_influences, scale=args.scale, keep_root=args.keep_root)
     print(glb)
     print(npz)
+    if args.preview:
+        from . import preview
+        # the rest pose is y up; drive's root rotation (pi/2, 0, 0) in the tracks turns the played avatar into Blender's frame, z up
+        up = "z" if args.motion is not None and not args.keep_root else "y"
+        print(preview.preview(os.path.join(args.out_dir, "%s_preview.gif" % name), glb=glb, up=up)[0])
 
 
 if __name__ == "__main__":

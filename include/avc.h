@@ -388,6 +388,51 @@ int avc_skin_pack(const float* weights, const unsigned char* tj, const float* tw
  * quaternions (x, y, z, w) with w >= 0, Shepperd's method in fp64, rounded to float32.  q 16-byte aligned. */
 int avc_rot_to_quat(const float* R, long n, float* q, void* stream);
 
+/* ---- looking at the results (avatarclip_amd/preview.py, csrc/avc_preview.hip; tests/preview_restatement.py restates every rule) ----
+ * A batched, z-buffered, vertex-colour triangle renderer of this project's own (no counterpart in the reference, which renders through
+ * pyrender): exact integer coverage and depth, a watertight top-left fill rule, both windings drawn.  Not neural_renderer's rules -- those
+ * stay with avc_rasterize_*.  A plain launch chain on the caller's stream; no float atomics: bit-identical from run to run.  N = 0 is a
+ * no-op that returns 0; at most 65535 frames a call.  R = raster size = S * ss <= AVC_PREVIEW_MAX_RASTER, larger sizes are an error.
+ *
+ * avc_preview_project: v [N,V,3] float32 world space, cams [N,12] (eye, x / y / z axis of the look frame: the layout of avc_rasterize_mesh),
+ * width = tan(fov / 2), 0 < near < far -> proj [N,V] of four int32 (16-byte aligned): X, Y, Z, bits of the float32 1 / c_z.  In fp64, one
+ * rounded operation each, no FMA: d = v - eye; c_j = (d0 a_j0 + d1 a_j1) + d2 a_j2; s = c_z width; X = floor((c_x / s + 1) (R / 2) 256 + 0.5),
+ * Y = floor((1 - c_y / s) (R / 2) 256 + 0.5) (8 sub-pixel bits, y down: row 0 is the top row, the centre of pixel (i, j) is
+ * (256 i + 128, 256 j + 128)); Z = floor(((c_z - near) far) / (c_z (far - near)) (2^24 - 1) + 0.5) (24 bits of NDC z).  A vertex is invalid
+ * (Z = -1) unless near < c_z <= far and -2^16 <= X, Y <= 256 R + 2^16 (a guard band of 256 raster pixels).
+ * A FACE WITH AN INVALID VERTEX IS DROPPED, NOT CLIPPED: a camera inside the mesh, or nearer to it than `near`, loses whole faces.
+ * preview.frame_cameras never produces one; a caller's own camera can.
+ *
+ * avc_preview_raster: tris [F,3] int32 (a corner outside [0, V) drops the face).  Oriented area2 = (x1 - x0)(y2 - y0) - (y1 - y0)(x2 - x0):
+ * 0 skips the face, < 0 swaps vertices 1 and 2 (no back-face culling).  Edge i (opposite vertex i) runs a -> b: 1 -> 2, 2 -> 0, 0 -> 1;
+ * w_i(p) = (bx - ax)(py - ay) - (by - ay)(px - ax) in int64 at the pixel centre p; covered <=> w_i >= 0 for all i and w_i > 0 for every
+ * edge that is not top-left (top-left: by < ay, or by == ay and bx > ax).  depth = floor((w_0 Z_0 + w_1 Z_1 + w_2 Z_2) / area2); the
+ * winner of a pixel is the minimum of (depth << 32 | face), by 64-bit atomicMin: nearest face, ties to the lower face index.  No int64
+ * product overflows up to AVC_PREVIEW_MAX_RASTER (the proof is in csrc/avc_preview.hip).  Faces whose box holds more than 1024 pixel centres
+ * are handled per (face, 16 x 16 tile).  scratch: N x avc_preview_scratch_bytes(F, R) bytes (-1: a size outside the limits), 8-byte
+ * aligned, which the caller fills with 0xFF once; avc_preview_shade hands them back that way.
+ *
+ * avc_preview_shade: image uint8 [N,S,S,3], row 0 = top.  Per raster pixel the winner's weights are recomputed; colour = sum_i l_i c_i /
+ * sum_i l_i with l_i = w_i * (1 / c_z of vertex i) (perspective-correct) from colors uint8 [V,csize] (csize 3 or 4, the first three
+ * used), or the constant `grey` (0..255) when colors is NULL; times the face's flat two-sided shade ambient + (1 - ambient) |n . l| /
+ * (|n| |l|), n = (v1 - v0) x (v2 - v0) in world space, l = lights [N,3] (no direction in either: ambient alone); the background
+ * (bg_r, bg_g, bg_b; 0..255) elsewhere; then the ss x ss box average (ss = 1 or 2), floor(x + 0.5), clamped.  face_ids (may be NULL): int32 [N,R,R], the
+ * winning face of every raster pixel, -1 = background, row 0 = top. */
+#define AVC_PREVIEW_MAX_RASTER 2048
+long avc_preview_scratch_bytes(int F, int raster_size);
+int avc_preview_project(const float* v, int N, int V, const float* cams, float width, float near_, float far_, int raster_size, int* proj,
+                        void* stream);
+int avc_preview_raster(const int* proj, int N, int V, const int* tris, int F, int raster_size, void* scratch, void* stream);
+int avc_preview_shade(const int* proj, const float* v, int N, int V, const int* tris, int F, const unsigned char* colors, int csize,
+                      const float* lights, float ambient, float bg_r, float bg_g, float bg_b, float grey, int S, int ss, void* scratch,
+                      unsigned char* image, int* face_ids, void* stream);
+/* Four-influence linear blend skinning, for playing a .glb back: out [T,M,3], out[t,m] = sum_k weights[m,k] (joint_mats[t, joints[m,k]]
+ * (rest[m], 1)), k = 0..3 in this order, float32.  joints uint8 [M,4] (4-byte aligned), weights float32 [M,4] and joint_mats [T,J,12] =
+ * rows 0..2 of the 4 x 4 joint matrices (both 16-byte aligned), rest [M,3].  1 <= J <= 256.  Contract: every joint below J; one outside
+ * writes NaN for that vertex and reads nothing.  (avc_skin_apply is a different thing: ONE template transform per vertex.) */
+int avc_skin_blend4(const unsigned char* joints, const float* weights, const float* joint_mats, const float* rest, int M, int J, int T,
+                    float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
