@@ -136,32 +136,23 @@ class AnimateContext:
         v, _ = smpl_lbs.lbs(s["v_template"][None].expand(bs, -1, -1), rot, s["posedirs"], s["J_regressor"], s["parents"], s["lbs_weights"])
         return v
 
+    @torch.no_grad()
     def _render_hip(self, vertices, faces, angles):
-        """models/render.py:10-39 on the HIP rasteriser: camera_mode 'look_at' at distance 2, azimuth = the angle, elevation drawn per angle
-        from numpy's global generator (np.random.randn() * 0.3 degrees: the reference's draw, in its order).  White body under
-        neural_renderer's light -- the UV texture is an input of `render_fn` replacements."""
-        from .shapegen_render import get_points_from_angles
-        from .smpl_prior import MeshPrior
-        eyes = [get_points_from_angles(CAMERA_DISTANCE, np.random.randn() * 0.3, a) for a in angles]     # draw order: once per angle, before the batch loop
-        priors = [MeshPrior(v.detach().cpu().numpy(), faces, device=self.device, image_size=self.image_size) for v in vertices]
-        out = []
-        for eye in eyes:
-            for p in priors:
-                g = p.render_grey(eye.astype(np.float32), (-eye / np.linalg.norm(eye)).astype(np.float32))
-                out.append(g.unsqueeze(0).expand(3, -1, -1))
-        return torch.stack(out)
+        """_render_hip_grad without a gradient: the default render of the pose and motion scorers"""
+        return self._render_hip_grad(vertices.to(self.device), faces, angles)
 
     def _render_hip_grad(self, vertices, faces, angles):
-        """_render_hip with autograd to the vertices (mesh_render.render_grey_batch: one batched forward-with-save, neural_renderer's approximate
-        backward): the same elevation draws in the same order, the len(angles) x bs renders camera-major in one call"""
+        """models/render.py:10-39 on the HIP rasteriser: camera_mode 'look_at' at distance 2, azimuth = the angle, elevation drawn per angle
+        from numpy's global generator (np.random.randn() * 0.3 degrees: the reference's draw, in its order).  White body under
+        neural_renderer's light -- the UV texture is an input of `render_fn` replacements.  The len(angles) x bs renders camera-major in one
+        call of mesh_render.render_grey_batch (one batched forward-with-save, neural_renderer's approximate backward to the vertices)."""
         from .mesh_render import render_grey_batch
         from .shapegen_render import get_points_from_angles
         eyes = [get_points_from_angles(CAMERA_DISTANCE, np.random.randn() * 0.3, a) for a in angles]     # draw order: once per angle, before the batch loop
         bs = vertices.shape[0]
         eye_all = [e.astype(np.float32) for e in eyes for _ in range(bs)]
         dir_all = [(-e / np.linalg.norm(e)).astype(np.float32) for e in eyes for _ in range(bs)]
-        v = vertices.unsqueeze(0).expand(len(eyes), -1, -1, -1).reshape(len(eyes) * bs, *vertices.shape[1:])
-        g = render_grey_batch(v, faces, eye_all, dir_all, image_size=self.image_size)
+        g = render_grey_batch(vertices, faces, eye_all, dir_all, image_size=self.image_size)
         return g.unsqueeze(1).expand(-1, 3, -1, -1)
 
     def release_graphs(self):

@@ -1,5 +1,4 @@
-// Device helpers shared by the forward rasteriser (avc_raster.hip) and its batched save-for-backward form + pseudo-gradient
-// (avc_raster_grad.hip): the face set-up, edge / depth test, box and gather of the nine floats of a face, and the look + perspective
+// Device helpers shared by the forward rasteriser (avc_raster.hip) and its pseudo-gradient (avc_raster_grad.hip): the face set-up, edge / depth test, box and gather of the nine floats of a face, and the look + perspective
 // projection of one vertex.  Both translation units compile them under `fp contract(off)`: the edge tests are sign tests and the
 // backward's scan-line crossings are floored / ceiled, so every rounding must be the one the fp32 restatements make.
 #pragma once

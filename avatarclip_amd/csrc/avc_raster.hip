@@ -1,4 +1,4 @@
-// Silhouette + flat-shading rasteriser of the SMPL prior: the forward pass of
+// Silhouette + flat-shading rasteriser of the SMPL prior and of AvatarAnimate's renders (row f-4): the forward pass of
 // `neural_renderer` as AppearanceGen uses it (AvatarGen/AppearanceGen/models/utils.py:108-125, render_one_batch: white
 // texture, ambient 0.5 + directional 0.5 face lighting, anti-aliased 256 x 256) -- no host round trip, no neural_renderer.
 // Algorithm = the published one of neural_renderer's rasterize_cuda_kernel.cu (restated in oracle/nr_oracle.py, which this
@@ -17,28 +17,34 @@
 // file gave every 16 x 16 pixel tile a scan over ALL faces with an LDS survivor list: 0.37 ms for the 27 552 faces of the prior at
 // 512^2, bound by the few tiles over the head and the hands where a thousand small faces survive the box test; staging the faces
 // through LDS or scanning 1 024 per round did not move that.  profiles/r04_ab_kernels.txt)
+//
+// Three entry points, one set of kernels: avc_rasterize_mesh_save renders N vertex sets of one topology, each with its own camera, in one call
+// (render b = blockIdx.y / .z: its own ndc, z-buffer and large-face list) and saves the face-index map for the backward (avc_raster_grad.hip);
+// avc_rasterize_mesh (the prior) is N = 1 of it with the x flip and the three channels; avc_rasterize_faces takes projected faces [F,9], N = 1,
+// no projection and no pooling.
 #include "avc_common.h"
 #include "../../include/avc.h"
 #include "avc_raster.h"      // FaceEq, face_setup, face_depth, face_box, load_face, project_vertex, RS_*
 
 #pragma clang fp contract(off)   // same roundings as the fp32 restatement (edge tests are sign tests)
 
-// the projection of project_vertex (avc_raster.h), one thread per vertex; cam = device [12]
-__global__ __launch_bounds__(256) void prior_project_kernel(const float* __restrict__ vw, int V, const float* __restrict__ cam, float width,
-                                                            float* __restrict__ ndc) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
+// the projection of project_vertex (avc_raster.h), one thread per vertex of render b = blockIdx.y; cam = device [N,12]
+__global__ __launch_bounds__(256) void raster_project_kernel(const float* __restrict__ vw, int V, const float* __restrict__ cam, float width,
+                                                         float* __restrict__ ndc) {
+  const int i = blockIdx.x * 256 + threadIdx.x, b = blockIdx.y;
   if (i >= V) return;
-  project_vertex(vw, i, cam, width, ndc);
+  project_vertex(vw + (long)b * V * 3, i, cam + 12 * b, width, ndc + (long)b * V * 3);
 }
-// `large` = [count - 1 (0xFFFFFFFF = none), face indices ...]
-__global__ __launch_bounds__(256) void raster_faces_kernel(const float* __restrict__ faces /* [F,9] x,y (NDC), z (depth) */,
-                                                           const int* __restrict__ idx, int F, int is,
-                                                           float near, float far, unsigned long long* __restrict__ zbuf /* [is,is], y up */,
-                                                           unsigned* __restrict__ large) {
-  const int fn = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+// one wavefront per face of render b = blockIdx.y (its ndc [V,3], z-buffer and large-face list); faces = ndc gathered through idx [F,3], or
+// (idx == NULL, one render) ndc = the faces [F,9] themselves: x, y (NDC), z (depth).  `large` = [count - 1 (0xFFFFFFFF = none), face indices ...]
+__global__ __launch_bounds__(256) void raster_faces_kernel(const float* __restrict__ ndc, int V, const int* __restrict__ idx, int F, int is,
+                                                       float near, float far, unsigned long long* __restrict__ zbufs, unsigned* __restrict__ larges) {
+  const int fn = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63, b = blockIdx.y;
   if (fn >= F) return;
+  unsigned long long* zbuf = zbufs + (long)b * is * is;
+  unsigned* large = larges + (long)b * (F + 2);
   float f[9];
-  load_face(faces, idx, fn, f);
+  load_face(ndc + (long)b * V * 3, idx, fn, f);
   FaceEq e;
   if (!face_setup(f, is, e)) return;
   int xa, xb, ya, yb;
@@ -49,26 +55,29 @@ __global__ __launch_bounds__(256) void raster_faces_kernel(const float* __restri
     if (lane == 0) large[1 + (atomicAdd(&large[0], 1u) + 1u)] = (unsigned)fn;
     return;
   }
-  for (int idx = lane; idx < n; idx += 64) {
-    const int xi = xa + idx % w, yi = ya + idx / w;
+  for (int k = lane; k < n; k += 64) {
+    const int xi = xa + k % w, yi = ya + k / w;
     const float zp = face_depth(e, xi, yi, is, near, far);
     if (zp < 0.f) continue;
     atomicMin(&zbuf[(long)yi * is + xi], ((unsigned long long)__float_as_uint(zp) << 32) | (unsigned)fn);
   }
 }
-// the listed large faces, tile-parallel: thread = pixel of a 16 x 16 tile, every face of the list whose box meets the tile is
-// evaluated at the tile's pixels; the running minimum joins the key the small faces left (plain read-modify-write: one thread per pixel)
-__global__ __launch_bounds__(256) void raster_large_kernel(const float* __restrict__ faces, const int* __restrict__ idx, int is, float near,
-                                                           float far, unsigned long long* __restrict__ zbuf, const unsigned* __restrict__ large) {
+// the listed large faces of render b = blockIdx.z, tile-parallel: thread = pixel of a 16 x 16 tile, every face of the list whose box meets the
+// tile is evaluated at the tile's pixels; the running minimum joins the key the small faces left (plain read-modify-write: one thread per pixel)
+__global__ __launch_bounds__(256) void raster_large_kernel(const float* __restrict__ ndc, int V, const int* __restrict__ idx, int F, int is, float near,
+                                                       float far, unsigned long long* __restrict__ zbufs, const unsigned* __restrict__ larges) {
+  const int b = blockIdx.z;
+  const unsigned* large = larges + (long)b * (F + 2);
   const unsigned nl = large[0] + 1u;
   if (nl == 0u) return;
+  const float* nd = ndc + (long)b * V * 3;
   const int tx0 = blockIdx.x * RS_TILE, ty0 = blockIdx.y * RS_TILE;
   const int xi = tx0 + (threadIdx.x & 15), yi = ty0 + (threadIdx.x >> 4);
   unsigned long long best = RS_EMPTY;
   for (unsigned q = 0; q < nl; ++q) {
     const int fn = (int)large[1 + q];
     float f[9];
-    load_face(faces, idx, fn, f);
+    load_face(nd, idx, fn, f);
     FaceEq e;
     if (!face_setup(f, is, e)) continue;
     int xa, xb, ya, yb;
@@ -81,7 +90,7 @@ __global__ __launch_bounds__(256) void raster_large_kernel(const float* __restri
     best = key < best ? key : best;
   }
   if (xi < is && yi < is && best != RS_EMPTY) {
-    unsigned long long* z = &zbuf[(long)yi * is + xi];
+    unsigned long long* z = &zbufs[(long)b * is * is + (long)yi * is + xi];
     if (best < *z) *z = best;
   }
 }
@@ -97,30 +106,63 @@ __global__ __launch_bounds__(256) void raster_resolve_kernel(unsigned long long*
   zbuf[p] = RS_EMPTY;
 }
 
-// the same + what models/utils.py:108-125 does next, for the 2 x super-sampled render (anti_aliasing): 2 x 2 average (avg_pool2d: the window
-// summed row by row, then / 4), optionally the x flip of models/utils.py:124 (`[:, ::-1]`) and the white texture's three equal channels.
-// out [S,S] (channels == 1) or [S,S,3], S = is / 2.
-__global__ __launch_bounds__(256) void raster_resolve_pool_kernel(unsigned long long* __restrict__ zbuf, const float* __restrict__ light, int is,
-                                                                  float* __restrict__ out, int flip_x, int channels, unsigned* __restrict__ large) {
-  const int S = is >> 1;
+// the same for render b = blockIdx.y of the mesh forms + what models/utils.py:108-125 does next, for the 2 x super-sampled render
+// (anti_aliasing): 2 x 2 average (avg_pool2d: the window summed row by row, then / 4), optionally the x flip of models/utils.py:124
+// (`[:, ::-1]`) and the white texture's three equal channels -> out [N,S,S] (channels == 1) or [N,S,S,3], S = is / 2.  fidx != NULL: also the
+// face index of every super-sampled pixel [N,is,is] (z-buffer orientation, y up; -1 = background), which the backward reads.
+__global__ __launch_bounds__(256) void raster_resolve_pool_kernel(unsigned long long* __restrict__ zbufs, const float* __restrict__ light, int F, int is,
+                                                                  float* __restrict__ out, int* __restrict__ fidx, int flip_x, int channels,
+                                                                  unsigned* __restrict__ larges) {
+  const int S = is >> 1, b = blockIdx.y;
   const int p = blockIdx.x * 256 + threadIdx.x;
-  if (p == 0) large[0] = 0xFFFFFFFFu;
+  if (p == 0) larges[(long)b * (F + 2)] = 0xFFFFFFFFu;
   if (p >= S * S) return;
+  unsigned long long* zbuf = zbufs + (long)b * is * is;
+  const float* lt = light + (long)b * F;
+  int* fi = fidx ? fidx + (long)b * is * is : nullptr;
   const int y = p / S, x = p % S;
-  float acc = 0.f;
+  // the window's four keys first (independent loads in flight together), then their lights, summed in the order (dy, dx) = (0,0), (0,1), (1,0), (1,1)
+  long q[4];
+  unsigned long long key[4];
 #pragma unroll
-  for (int dy = 0; dy < 2; ++dy)
+  for (int k = 0; k < 4; ++k) {
+    q[k] = (long)(is - 1 - (2 * y + (k >> 1))) * is + 2 * x + (k & 1);       // image row r (0 = top) is z-buffer row is - 1 - r
+    key[k] = zbuf[q[k]];
+  }
+  float l[4];
 #pragma unroll
-    for (int dx = 0; dx < 2; ++dx) {
-      const int r = 2 * y + dy, c = 2 * x + dx;                       // image row r (0 = top) is z-buffer row is - 1 - r
-      unsigned long long* z = &zbuf[(long)(is - 1 - r) * is + c];
-      const unsigned long long key = *z;
-      acc += key == RS_EMPTY ? 0.f : light[(unsigned)(key & 0xFFFFFFFFull)];
-      *z = RS_EMPTY;
-    }
+  for (int k = 0; k < 4; ++k) {
+    const bool bg = key[k] == RS_EMPTY;
+    const unsigned face = (unsigned)(key[k] & 0xFFFFFFFFull);
+    l[k] = bg ? 0.f : lt[face];
+    if (fi) fi[q[k]] = bg ? -1 : (int)face;
+    zbuf[q[k]] = RS_EMPTY;
+  }
+  const float acc = ((l[0] + l[1]) + l[2]) + l[3];
   const float v = acc / 4.f;
   const int xo = flip_x ? S - 1 - x : x;
-  for (int ch = 0; ch < channels; ++ch) out[((long)y * S + xo) * channels + ch] = v;
+  for (int ch = 0; ch < channels; ++ch) out[(((long)b * S + y) * S + xo) * channels + ch] = v;
+}
+
+// The launches of all three entry points: N renders of one topology at is x is, render b with its own ndc [V,3], z-buffer and large-face list
+// (scratch = [N z-buffers][N x (F + 2) list words]).  v_world != NULL (the mesh forms, is = 2 S): ndc is projected from it (cam [N,12]) and the
+// resolve pools.  v_world == NULL (the face-list form, N = 1): ndc holds the faces [F,9] themselves, idx is NULL and the resolve does not pool.
+static void raster_forward(const float* v_world, int N, int V, const int* idx, int F, const float* cam, float width, const float* light, int is,
+                           float near, float far, const float* ndc, float* out, int* fidx, int flip_x, int channels, void* scratch, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  unsigned long long* zbufs = (unsigned long long*)scratch;
+  unsigned* larges = (unsigned*)(zbufs + (long)N * is * is);
+  if (v_world) hipLaunchKernelGGL(raster_project_kernel, dim3((V + 255) / 256, N), dim3(256), 0, s, v_world, V, cam, width, const_cast<float*>(ndc));
+  if (F) {
+    hipLaunchKernelGGL(raster_faces_kernel, dim3((F + 3) / 4, N), dim3(256), 0, s, ndc, V, idx, F, is, near, far, zbufs, larges);
+    const int nt = (is + RS_TILE - 1) / RS_TILE;
+    hipLaunchKernelGGL(raster_large_kernel, dim3(nt, nt, N), dim3(256), 0, s, ndc, V, idx, F, is, near, far, zbufs, larges);
+  }
+  if (v_world)
+    hipLaunchKernelGGL(raster_resolve_pool_kernel, dim3((is / 2 * (is / 2) + 255) / 256, N), dim3(256), 0, s, zbufs, light, F, is, out, fidx, flip_x,
+                       channels, larges);
+  else
+    hipLaunchKernelGGL(raster_resolve_kernel, dim3((is * is + 255) / 256), dim3(256), 0, s, zbufs, light, is, out, larges);
 }
 
 extern "C" long avc_rasterize_scratch_bytes(int F, int image_size) {
@@ -131,15 +173,7 @@ extern "C" int avc_rasterize_faces(const float* faces, const float* light, int F
   if (image_size <= 0) { avc_set_error("avc_rasterize_faces: image_size <= 0"); return 1; }
   if (F < 0 || near < 0.f) { avc_set_error("avc_rasterize_faces: F < 0 or near < 0"); return 1; }
   if (!image || !scratch || (F && (!faces || !light))) { avc_set_error("avc_rasterize_faces: NULL buffer"); return 1; }
-  hipStream_t s = (hipStream_t)stream;
-  unsigned long long* zbuf = (unsigned long long*)scratch;
-  unsigned* large = (unsigned*)(zbuf + (long)image_size * image_size);
-  if (F) {
-    hipLaunchKernelGGL(raster_faces_kernel, dim3((F + 3) / 4), dim3(256), 0, s, faces, (const int*)nullptr, F, image_size, near, far, zbuf, large);
-    const int nt = (image_size + RS_TILE - 1) / RS_TILE;
-    hipLaunchKernelGGL(raster_large_kernel, dim3(nt, nt), dim3(256), 0, s, faces, (const int*)nullptr, image_size, near, far, zbuf, large);
-  }
-  hipLaunchKernelGGL(raster_resolve_kernel, dim3((image_size * image_size + 255) / 256), dim3(256), 0, s, zbuf, light, image_size, image, large);
+  raster_forward(nullptr, 1, 0, nullptr, F, nullptr, 0.f, light, image_size, near, far, faces, image, nullptr, 0, 1, scratch, stream);
   return avc_check_launch("avc_rasterize_faces");
 }
 // The whole prior render of models/utils.py:108-125 from the world-space mesh: projection of the V vertices (cam = device [12]: eye + the
@@ -149,16 +183,15 @@ extern "C" int avc_rasterize_mesh(const float* v_world, int V, const int* idx, i
                                   int S, float near, float far, float* ndc, float* out, int flip_x, int channels, void* scratch, void* stream) {
   if (S <= 0 || V <= 0 || F < 0 || near < 0.f || (channels != 1 && channels != 3)) { avc_set_error("avc_rasterize_mesh: bad sizes"); return 1; }
   if (!v_world || !cam || !ndc || !out || !scratch || (F && (!idx || !light))) { avc_set_error("avc_rasterize_mesh: NULL buffer"); return 1; }
-  hipStream_t s = (hipStream_t)stream;
-  const int is = 2 * S;
-  unsigned long long* zbuf = (unsigned long long*)scratch;
-  unsigned* large = (unsigned*)(zbuf + (long)is * is);
-  hipLaunchKernelGGL(prior_project_kernel, dim3((V + 255) / 256), dim3(256), 0, s, v_world, V, cam, width, ndc);
-  if (F) {
-    hipLaunchKernelGGL(raster_faces_kernel, dim3((F + 3) / 4), dim3(256), 0, s, ndc, idx, F, is, near, far, zbuf, large);
-    const int nt = (is + RS_TILE - 1) / RS_TILE;
-    hipLaunchKernelGGL(raster_large_kernel, dim3(nt, nt), dim3(256), 0, s, ndc, idx, is, near, far, zbuf, large);
-  }
-  hipLaunchKernelGGL(raster_resolve_pool_kernel, dim3((S * S + 255) / 256), dim3(256), 0, s, zbuf, light, is, out, flip_x, channels, large);
+  raster_forward(v_world, 1, V, idx, F, cam, width, light, 2 * S, near, far, ndc, out, nullptr, flip_x, channels, scratch, stream);
   return avc_check_launch("avc_rasterize_mesh");
+}
+// AvatarAnimate's batched form (mesh_render.py): N such renders in one call, render i with its own vertices, camera and light, one shared
+// topology; no x flip, one channel, and the face-index map saved for avc_rasterize_mesh_grad (avc_raster_grad.hip)
+extern "C" int avc_rasterize_mesh_save(const float* v_world, int N, int V, const int* idx, int F, const float* cam, float width, const float* light,
+                                       int S, float near, float far, float* ndc, float* image, int* fidx, void* scratch, void* stream) {
+  if (N <= 0 || S <= 0 || V <= 0 || F < 0 || near < 0.f) { avc_set_error("avc_rasterize_mesh_save: bad sizes"); return 1; }
+  if (!v_world || !cam || !ndc || !image || !fidx || !scratch || (F && (!idx || !light))) { avc_set_error("avc_rasterize_mesh_save: NULL buffer"); return 1; }
+  raster_forward(v_world, N, V, idx, F, cam, width, light, 2 * S, near, far, ndc, image, fidx, 0, 1, scratch, stream);
+  return avc_check_launch("avc_rasterize_mesh_save");
 }

@@ -3,133 +3,18 @@
 // Ushiku and Harada, "Neural 3D Mesh Renderer" (CVPR 2018) section 3.3, restated from the paper and the published kernel in
 // tests/nr_grad_restatement.py (DESIGN.md section 8 states the rules; unpinned against neural_renderer itself).
 //
-// 1. avc_rasterize_mesh_save: N renders in one call (render i: its own vertices and camera, one shared topology), the projection and the
-//    z-buffer scheme of avc_raster.hip batched over blockIdx.y / .z (one z-buffer + large-face list per render); the resolve also writes the
-//    super-sampled face-index map the backward reads.  Same device helpers (avc_raster.h), same arithmetic: the pooled images are
-//    bit-identical to avc_rasterize_mesh's.
-// 2. avc_rasterize_mesh_grad: one wavefront per (render, face).  Light gradient = sum of the upstream gradient over the pixels the face
-//    won (its box, as raster_faces_kernel walks it).  Pseudo-gradient: for every edge, axis and scan line the edge crosses, the "out" run
-//    from the pixel just outside the edge to the image border and the "in" run across the face, lanes over the run's pixels; every lane
-//    accumulates its own contributions to the face's three vertices in registers, a fixed-order wave reduction sums them.  Then one thread
-//    per (render, vertex) gathers its faces' sums through a vertex -> face CSR.  No float atomics: the result is deterministic.
+// The forward with save (avc_rasterize_mesh_save: N renders in one call, the pooled images + the super-sampled face-index map) is in
+// avc_raster.hip with the other forward entry points.  Here, avc_rasterize_mesh_grad: one wavefront per (render, face).  Light gradient = sum of
+// the upstream gradient over the pixels the face won (its box, as raster_faces_kernel walks it).  Pseudo-gradient: for every edge, axis and scan
+// line the edge crosses, the "out" run from the pixel just outside the edge to the image border and the "in" run across the face, lanes over the
+// run's pixels; every lane accumulates its own contributions to the face's three vertices in registers, a fixed-order wave reduction sums them.
+// Then one thread per (render, vertex) gathers its faces' sums through a vertex -> face CSR.  No float atomics: the result is deterministic.
 #include "avc_common.h"
 #include "../../include/avc.h"
 #include "avc_raster.h"
 
 #pragma clang fp contract(off)   // the floors / ceilings of the crossings must be the fp32 restatement's
 
-// ------------------------------------------------------------------------------------------------------------- forward with save
-__global__ __launch_bounds__(256) void rg_project_kernel(const float* __restrict__ vw, int V, const float* __restrict__ cam, float width,
-                                                         float* __restrict__ ndc) {
-  const int i = blockIdx.x * 256 + threadIdx.x, b = blockIdx.y;
-  if (i >= V) return;
-  project_vertex(vw + (long)b * V * 3, i, cam + 12 * b, width, ndc + (long)b * V * 3);
-}
-// raster_faces_kernel of avc_raster.hip, render b = blockIdx.y (its ndc, z-buffer and large-face list)
-__global__ __launch_bounds__(256) void rg_faces_kernel(const float* __restrict__ ndc, int V, const int* __restrict__ idx, int F, int is,
-                                                       float near, float far, unsigned long long* __restrict__ zbufs, unsigned* __restrict__ larges) {
-  const int fn = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63, b = blockIdx.y;
-  if (fn >= F) return;
-  unsigned long long* zbuf = zbufs + (long)b * is * is;
-  unsigned* large = larges + (long)b * (F + 2);
-  float f[9];
-  load_face(ndc + (long)b * V * 3, idx, fn, f);
-  FaceEq e;
-  if (!face_setup(f, is, e)) return;
-  int xa, xb, ya, yb;
-  if (!face_box(e, is, xa, xb, ya, yb)) return;
-  const int w = xb - xa + 1, h = yb - ya + 1;
-  const int n = w * h;
-  if (n > RS_LARGE) {
-    if (lane == 0) large[1 + (atomicAdd(&large[0], 1u) + 1u)] = (unsigned)fn;
-    return;
-  }
-  for (int k = lane; k < n; k += 64) {
-    const int xi = xa + k % w, yi = ya + k / w;
-    const float zp = face_depth(e, xi, yi, is, near, far);
-    if (zp < 0.f) continue;
-    atomicMin(&zbuf[(long)yi * is + xi], ((unsigned long long)__float_as_uint(zp) << 32) | (unsigned)fn);
-  }
-}
-// raster_large_kernel of avc_raster.hip, render b = blockIdx.z
-__global__ __launch_bounds__(256) void rg_large_kernel(const float* __restrict__ ndc, int V, const int* __restrict__ idx, int F, int is, float near,
-                                                       float far, unsigned long long* __restrict__ zbufs, const unsigned* __restrict__ larges) {
-  const int b = blockIdx.z;
-  const unsigned* large = larges + (long)b * (F + 2);
-  const unsigned nl = large[0] + 1u;
-  if (nl == 0u) return;
-  const float* nd = ndc + (long)b * V * 3;
-  const int tx0 = blockIdx.x * RS_TILE, ty0 = blockIdx.y * RS_TILE;
-  const int xi = tx0 + (threadIdx.x & 15), yi = ty0 + (threadIdx.x >> 4);
-  unsigned long long best = RS_EMPTY;
-  for (unsigned q = 0; q < nl; ++q) {
-    const int fn = (int)large[1 + q];
-    float f[9];
-    load_face(nd, idx, fn, f);
-    FaceEq e;
-    if (!face_setup(f, is, e)) continue;
-    int xa, xb, ya, yb;
-    if (!face_box(e, is, xa, xb, ya, yb)) continue;
-    if (xb < tx0 || xa > tx0 + RS_TILE - 1 || yb < ty0 || ya > ty0 + RS_TILE - 1) continue;
-    if (xi >= is || yi >= is) continue;
-    const float zp = face_depth(e, xi, yi, is, near, far);
-    if (zp < 0.f) continue;
-    const unsigned long long key = ((unsigned long long)__float_as_uint(zp) << 32) | (unsigned)fn;
-    best = key < best ? key : best;
-  }
-  if (xi < is && yi < is && best != RS_EMPTY) {
-    unsigned long long* z = &zbufs[(long)b * is * is + (long)yi * is + xi];
-    if (best < *z) *z = best;
-  }
-}
-// raster_resolve_pool_kernel of avc_raster.hip (no x flip, one channel) + the face index of every super-sampled pixel (z-buffer
-// orientation, y up; -1 = background); render b = blockIdx.y; the scratch is left empty
-__global__ __launch_bounds__(256) void rg_resolve_kernel(unsigned long long* __restrict__ zbufs, const float* __restrict__ light, int F, int is,
-                                                         float* __restrict__ out, int* __restrict__ fidx, unsigned* __restrict__ larges) {
-  const int S = is >> 1, b = blockIdx.y;
-  const int p = blockIdx.x * 256 + threadIdx.x;
-  if (p == 0) larges[(long)b * (F + 2)] = 0xFFFFFFFFu;
-  if (p >= S * S) return;
-  unsigned long long* zbuf = zbufs + (long)b * is * is;
-  const float* lt = light + (long)b * F;
-  int* fi = fidx + (long)b * is * is;
-  const int y = p / S, x = p % S;
-  float acc = 0.f;
-#pragma unroll
-  for (int dy = 0; dy < 2; ++dy)
-#pragma unroll
-    for (int dx = 0; dx < 2; ++dx) {
-      const int r = 2 * y + dy, c = 2 * x + dx;                       // image row r (0 = top) is z-buffer row is - 1 - r
-      const long q = (long)(is - 1 - r) * is + c;
-      const unsigned long long key = zbuf[q];
-      const bool bg = key == RS_EMPTY;
-      const unsigned face = (unsigned)(key & 0xFFFFFFFFull);
-      acc += bg ? 0.f : lt[face];
-      fi[q] = bg ? -1 : (int)face;
-      zbuf[q] = RS_EMPTY;
-    }
-  out[(long)b * S * S + p] = acc / 4.f;
-}
-
-extern "C" int avc_rasterize_mesh_save(const float* v_world, int N, int V, const int* idx, int F, const float* cam, float width, const float* light,
-                                       int S, float near, float far, float* ndc, float* image, int* fidx, void* scratch, void* stream) {
-  if (N <= 0 || S <= 0 || V <= 0 || F < 0 || near < 0.f) { avc_set_error("avc_rasterize_mesh_save: bad sizes"); return 1; }
-  if (!v_world || !cam || !ndc || !image || !fidx || !scratch || (F && (!idx || !light))) { avc_set_error("avc_rasterize_mesh_save: NULL buffer"); return 1; }
-  hipStream_t s = (hipStream_t)stream;
-  const int is = 2 * S;
-  unsigned long long* zbufs = (unsigned long long*)scratch;
-  unsigned* larges = (unsigned*)(zbufs + (long)N * is * is);
-  hipLaunchKernelGGL(rg_project_kernel, dim3((V + 255) / 256, N), dim3(256), 0, s, v_world, V, cam, width, ndc);
-  if (F) {
-    hipLaunchKernelGGL(rg_faces_kernel, dim3((F + 3) / 4, N), dim3(256), 0, s, ndc, V, idx, F, is, near, far, zbufs, larges);
-    const int nt = (is + RS_TILE - 1) / RS_TILE;
-    hipLaunchKernelGGL(rg_large_kernel, dim3(nt, nt, N), dim3(256), 0, s, ndc, V, idx, F, is, near, far, zbufs, larges);
-  }
-  hipLaunchKernelGGL(rg_resolve_kernel, dim3((S * S + 255) / 256, N), dim3(256), 0, s, zbufs, light, F, is, image, fidx, larges);
-  return avc_check_launch("avc_rasterize_mesh_save");
-}
-
-// ------------------------------------------------------------------------------------------------------------- backward
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);

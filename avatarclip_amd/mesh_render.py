@@ -3,7 +3,7 @@ N grey renders of N vertex sets of one topology in one call, with autograd to th
 
 Forward: neural_renderer's conventions as `smpl_prior.MeshPrior.render_grey` applies them (vertices @ rot_mat, fill_back, ambient 0.5 +
 directional 0.5 face light, 60 degree field of view, 2 x super-sampling) on the HIP rasteriser (`avc_rasterize_mesh_save`,
-csrc/avc_raster_grad.hip): the images are bit-identical to MeshPrior's.  Backward: neural_renderer's approximate gradient (Kato, Ushiku and
+csrc/avc_raster.hip): the same kernels as MeshPrior's single render, batched.  Backward: neural_renderer's approximate gradient (Kato, Ushiku and
 Harada, "Neural 3D Mesh Renderer", CVPR 2018, section 3.3; `avc_rasterize_mesh_grad`, rules in DESIGN.md section 8) to the projected
 vertices and to the face light; the projection Jacobian (zero for vertices behind the camera, the reference README's patch) and the light's
 dependence on the face normals are torch.  No CPU fallback."""
@@ -12,35 +12,12 @@ import torch
 
 from . import h2d
 from . import lib as L
-from .smpl_prior import ROT_MAT
+from .smpl_prior import ROT_MAT, _checked, _scratch_for, camera_frame, face_light
 
 DEFAULT_EPS = 1e-4          # neural_renderer's DEFAULT_EPS
 VIEWING_ANGLE, NEAR, FAR = 30.0, 0.1, 100.0
 
 _topologies = {}            # faces bytes -> (faces2 int32 [2F,3], vf_ptr, vf_ent) on a device
-_scratch = {}               # (device, stream, (N, F, S), bytes) -> 0xFF-filled z-buffer scratch (every call leaves it so)
-
-
-def camera_frame(eye, direction):
-    """neural_renderer/look.py's frame in float32 on the host, as MeshPrior.render_grey builds it -> [12]: eye, x, y, z axes"""
-    f = np.float32
-    z = np.asarray(direction, f)
-    z = z / f(np.sqrt((z * z).sum(dtype=f)))
-    x = np.cross(np.array([0.0, 1.0, 0.0], f), z).astype(f)
-    x = x / f(np.sqrt((x * x).sum(dtype=f)))
-    y = np.cross(z, x).astype(f)
-    y = y / f(np.sqrt((y * y).sum(dtype=f)))
-    return np.concatenate([np.asarray(eye, f), x, y, z])
-
-
-def face_light(v, faces, light_ambient=0.5, light_directional=0.5, light_direction=(0.0, 1.0, 0.0)):
-    """neural_renderer/lighting.py in world space for one vertex set [V,3] -> light of the fill_back face list [2F]: MeshPrior.__init__'s
-    expression, differentiable"""
-    fv = v[faces]
-    n = torch.cross(fv[:, 0] - fv[:, 1], fv[:, 2] - fv[:, 1], dim=1)
-    n = n / n.norm(dim=1, keepdim=True).clamp(min=1e-5)
-    c = n @ torch.tensor(light_direction, dtype=v.dtype, device=v.device)
-    return torch.cat([light_ambient + light_directional * c.clamp(min=0), light_ambient + light_directional * (-c).clamp(min=0)])
 
 
 def project(v, cam, width):
@@ -89,18 +66,6 @@ def _topology(faces, V, device):
     return t
 
 
-def _scratch_for(device, layout, need):
-    """the z-buffers + large-face lists of one (N, F, S) layout.  A successful call leaves the z-buffers and the list counts empty, not the list
-    entries (face indices): a buffer is only ever reused for the same layout, where those bytes are list entries again."""
-    key = (str(device), L.stream(), layout, need)
-    z = _scratch.get(key)
-    if z is None:
-        for k in [k for k in _scratch if k[:2] == key[:2]]:
-            del _scratch[k]
-        z = _scratch[key] = torch.full((need,), 255, dtype=torch.uint8, device=device)
-    return z
-
-
 class _RasterFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, v_world, light2, cam, faces2, vf_ptr, vf_ent, S, width, eps):
@@ -112,14 +77,9 @@ class _RasterFn(torch.autograd.Function):
         ndc = torch.empty(N, V, 3, device=dev, dtype=torch.float32)
         image = torch.empty(N, S, S, device=dev, dtype=torch.float32)
         fidx = torch.empty(N, 2 * S, 2 * S, device=dev, dtype=torch.int32)
-        need = N * lib.avc_rasterize_scratch_bytes(F2, 2 * S)
-        scratch = _scratch_for(dev, (N, F2, S), need)
-        try:
-            L.check(lib.avc_rasterize_mesh_save(L.ptr(vw), N, V, L.ptr(faces2), F2, L.ptr(cam), width, L.ptr(lt), S, NEAR, FAR, L.ptr(ndc),
-                                                L.ptr(image), L.ptr(fidx), L.ptr(scratch), L.stream()), "avc_rasterize_mesh_save")
-        except Exception:
-            _scratch.clear()            # an interrupted render leaves keys behind: never reuse that scratch
-            raise
+        scratch = _scratch_for(dev, (N, F2, S), N * lib.avc_rasterize_scratch_bytes(F2, 2 * S))
+        _checked(lib.avc_rasterize_mesh_save(L.ptr(vw), N, V, L.ptr(faces2), F2, L.ptr(cam), width, L.ptr(lt), S, NEAR, FAR, L.ptr(ndc),
+                                             L.ptr(image), L.ptr(fidx), L.ptr(scratch), L.stream()), "avc_rasterize_mesh_save")
         ctx.save_for_backward(vw, lt, cam, faces2, vf_ptr, vf_ent, ndc, fidx)
         ctx.S, ctx.width, ctx.eps = S, width, eps
         ctx.mark_non_differentiable(ndc, fidx)
@@ -142,17 +102,21 @@ class _RasterFn(torch.autograd.Function):
 
 
 def render_grey_batch(v_world, faces, eyes, directions, image_size=256, eps=DEFAULT_EPS, return_state=False):
-    """v_world [N,V,3] (before rot_mat), faces [F,3], eyes / directions: N camera positions / viewing directions -> grey images [N,S,S]
-    (row 0 = top, no x flip; 0 = background) with autograd to v_world.  return_state: also (ndc [N,V,3], face index [N,2S,2S] y up)."""
+    """v_world [B,V,3] (before rot_mat), faces [F,3], eyes / directions: N = k B camera positions / viewing directions, render i of vertex set
+    i % B (k cameras, each on all B sets, camera-major; k = 1: one camera per set) -> grey images [N,S,S] (row 0 = top, no x flip; 0 =
+    background) with autograd to v_world.  return_state: also (ndc [N,V,3], face index [N,2S,2S] y up)."""
     dev = v_world.device
     if dev.type != "cuda":
         raise RuntimeError("render_grey_batch rasterises on the MI355X (no CPU fallback)")
-    N, V = v_world.shape[:2]
-    if len(eyes) != N or len(directions) != N:
-        raise ValueError("one camera per vertex set: %d vertex sets, %d eyes, %d directions" % (N, len(eyes), len(directions)))
+    B, V = v_world.shape[:2]
+    N = len(eyes)
+    if B == 0 or N % B or len(directions) != N:
+        raise ValueError("k cameras per vertex set: %d vertex sets, %d eyes, %d directions" % (B, N, len(directions)))
     faces2, f, vf_ptr, vf_ent = _topology(faces, V, dev)
     v = v_world.float() @ torch.tensor(ROT_MAT, dtype=torch.float32, device=dev)
-    light2 = torch.stack([face_light(v[i], f) for i in range(N)])
+    light2 = torch.stack([face_light(v[i], f) for i in range(B)])
+    if N != B:
+        v, light2 = v.repeat(N // B, 1, 1), light2.repeat(N // B, 1)
     cam = h2d.upload(np.stack([camera_frame(e, d) for e, d in zip(eyes, directions)]).reshape(-1), dev).reshape(N, 12)
     width = float(np.tan(np.deg2rad(VIEWING_ANGLE)))
     image, ndc, fidx = _RasterFn.apply(v, light2, cam, faces2, vf_ptr, vf_ent, int(image_size), width, float(eps))

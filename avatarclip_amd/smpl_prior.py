@@ -12,10 +12,56 @@ import torch
 from . import lib as L
 from . import h2d
 
-import os
-FUSED_PRIOR = os.environ.get("AVC_FUSED_PRIOR", "1") != "0"    # projection + rasteriser + pooling as four launches (0: torch ops around avc_rasterize_faces)
-
 ROT_MAT = ((1.0, 0.0, 0.0), (0.0, 0.0, -1.0), (0.0, 1.0, 0.0))    # models/utils.py:114-118
+
+_scratch = {}               # (device, stream, (N, F, S), bytes) -> 0xFF-filled z-buffer scratch of the rasteriser (every call leaves it so)
+
+
+def camera_frame(eye, direction):
+    """neural_renderer/look.py's camera frame, in float32 like there -- on the host (a dozen small launches otherwise) -> [12]: eye, x, y, z axes"""
+    f = np.float32
+    z = np.asarray(direction, f)
+    z = z / f(np.sqrt((z * z).sum(dtype=f)))
+    x = np.cross(np.array([0.0, 1.0, 0.0], f), z).astype(f)
+    x = x / f(np.sqrt((x * x).sum(dtype=f)))
+    y = np.cross(z, x).astype(f)
+    y = y / f(np.sqrt((y * y).sum(dtype=f)))
+    return np.concatenate([np.asarray(eye, f), x, y, z])
+
+
+def face_light(v, faces, light_ambient=0.5, light_directional=0.5, light_direction=(0.0, 1.0, 0.0)):
+    """neural_renderer/lighting.py in world space (view independent) for one vertex set [V,3] -> light of the fill_back face list [2F]: the
+    faces, then their reversed copies; differentiable"""
+    fv = v[faces]
+    n = torch.cross(fv[:, 0] - fv[:, 1], fv[:, 2] - fv[:, 1], dim=1)
+    n = n / n.norm(dim=1, keepdim=True).clamp(min=1e-5)
+    c = n @ torch.tensor(light_direction, dtype=v.dtype, device=v.device)
+    return torch.cat([light_ambient + light_directional * c.clamp(min=0), light_ambient + light_directional * (-c).clamp(min=0)])
+
+
+def _scratch_for(device, layout, need):
+    """The rasteriser's persistent scratch for one (N, F, S) layout (N z-buffers of 64-bit (depth, face) keys + N large-face lists): all bits
+    set = empty, and every successful call LEAVES the z-buffers and the list counts that way (the resolve launch restores what it read), which
+    is what saves a 2-MB fill per view.  The list entries (face indices) stay: a buffer is only ever reused for the same layout, where those
+    bytes are list entries again.  One buffer per device and HIP stream -- the launches of one render are ordered by their stream, two streams
+    must not interleave on one z-buffer (side-stream view preparation, main-stream validation renders)."""
+    key = (str(device), L.stream(), layout, need)
+    z = _scratch.get(key)
+    if z is None:
+        for k in [k for k in _scratch if k[:2] == key[:2]]:
+            del _scratch[k]
+        z = _scratch[key] = torch.full((need,), 255, dtype=torch.uint8, device=device)
+    return z
+
+
+def _checked(status, what):
+    """L.check; when a launch of the sequence reports an error every scratch is dropped (and refilled on its next use), so that stale keys of
+    an interrupted render cannot leak into later priors and silhouette masks"""
+    try:
+        L.check(status, what)
+    except Exception:
+        _scratch.clear()
+        raise
 
 
 def read_obj(path):
@@ -48,15 +94,10 @@ class MeshPrior:
         f = torch.as_tensor(np.asarray(faces).astype(np.int64)).to(dev).reshape(-1, 3)
         self.v_world = v.contiguous()
         self.faces2 = torch.cat([f, f.flip(1)], 0)                 # fill_back=True: every face also in reversed order
-        fv = v[f]                                                   # neural_renderer/lighting.py in world space (view independent)
-        n = torch.cross(fv[:, 0] - fv[:, 1], fv[:, 2] - fv[:, 1], dim=1)
-        n = n / n.norm(dim=1, keepdim=True).clamp(min=1e-5)
-        c = n @ torch.tensor(light_direction, dtype=torch.float32, device=dev)
-        self.light2 = torch.cat([light_ambient + light_directional * c.clamp(min=0),
-                                 light_ambient + light_directional * (-c).clamp(min=0)]).contiguous()
+        self.light2 = face_light(v, f, light_ambient, light_directional, light_direction).contiguous()
         self.lib = L.load()
-        self._zbufs = {}        # z-buffer scratch per HIP stream (the side-stream view preparation and main-stream validation renders never share one)
-        self._ndc = None
+        self._faces2_i32 = self.faces2.to(torch.int32).contiguous()
+        self._ndc = torch.empty_like(self.v_world)
 
     @classmethod
     def from_obj(cls, path, **kw):
@@ -75,63 +116,18 @@ class MeshPrior:
         verts, _ = smpl_lbs.lbs(vs, rot, smpl["posedirs"], smpl["J_regressor"], smpl["parents"], smpl["lbs_weights"])
         return cls(verts[0].detach().cpu().numpy(), smpl["faces"], **kw)
 
-    def _zbuf_for(self, need):
-        """The rasteriser's persistent scratch (64-bit (depth, face) keys + the large-face list): all bits set = empty, and every
-        successful call LEAVES it that way (the resolve launch restores the keys it read), which is what saves a 2-MB fill per view.
-        One buffer per HIP stream -- the launches of one render are ordered by their stream, two streams must not interleave on one
-        z-buffer -- dropped (and refilled on the next call) whenever a launch of the sequence reports an error, so that stale keys of
-        an interrupted render cannot leak into later priors and silhouette masks."""
-        key = (L.stream(), need)
-        z = self._zbufs.get(key)
-        if z is None:
-            for k in [k for k in self._zbufs if k[0] == key[0]]:
-                del self._zbufs[k]
-            z = self._zbufs[key] = torch.full((need,), 255, dtype=torch.uint8, device=self.device)
-        return z
-
-    def _checked(self, status, what):
-        try:
-            L.check(status, what)
-        except Exception:
-            self._zbufs.clear()          # the z-buffer of an interrupted render is not empty any more: never reuse it
-            raise
-
     @torch.no_grad()
     def render_grey(self, eye, direction, rgb_flipped=False):
-        """nr.Renderer(camera_mode='look')(vertices, faces, ones) -> [S,S] grey image (before the x flip)"""
-        dev = self.device
-        # neural_renderer/look.py: the camera frame, in float32 like there -- on the host (a dozen small launches otherwise), one upload
-        f = np.float32
-        z = np.asarray(direction, f)
-        z = z / f(np.sqrt((z * z).sum(dtype=f)))
-        x = np.cross(np.array([0.0, 1.0, 0.0], f), z).astype(f)
-        x = x / f(np.sqrt((x * x).sum(dtype=f)))
-        y = np.cross(z, x).astype(f)
-        y = y / f(np.sqrt((y * y).sum(dtype=f)))
-        cam = h2d.upload(np.concatenate([np.asarray(eye, f), x, y, z]), dev)
-        S = self.image_size
-        if FUSED_PRIOR:      # projection + rasteriser + 2 x 2 average (+ x flip + channels) in four launches (csrc/avc_raster.hip)
-            ch = 3 if rgb_flipped else 1
-            out = torch.empty((S, S, 3) if rgb_flipped else (S, S), device=dev, dtype=torch.float32)
-            zbuf = self._zbuf_for(self.lib.avc_rasterize_scratch_bytes(self.faces2.shape[0], 2 * S))
-            if self._ndc is None:
-                self._ndc = torch.empty_like(self.v_world)
-                self._faces2_i32 = self.faces2.to(torch.int32).contiguous()
-            self._checked(self.lib.avc_rasterize_mesh(L.ptr(self.v_world), self.v_world.shape[0], L.ptr(self._faces2_i32), self.faces2.shape[0], L.ptr(cam),
-                                                      self.width, L.ptr(self.light2), S, self.near, self.far, L.ptr(self._ndc), L.ptr(out),
-                                                      int(rgb_flipped), ch, L.ptr(zbuf), L.stream()), "avc_rasterize_mesh")
-            return out
-        v = (self.v_world - cam[:3]) @ cam[3:].reshape(3, 3).t()
-        ndc = torch.stack([v[:, 0] / v[:, 2] / self.width, v[:, 1] / v[:, 2] / self.width, v[:, 2]], dim=1)   # perspective.py
-        ndc = torch.where(v[:, 2:3] <= 0, torch.zeros_like(ndc), ndc)     # ... with the reference's patch (README.md:126-134): behind the camera -> 0
-        fz = ndc[self.faces2].reshape(-1, 9).contiguous()
-        S2 = 2 * self.image_size                                    # anti_aliasing=True
-        img = torch.empty(S2, S2, device=dev, dtype=torch.float32)
-        zbuf = self._zbuf_for(self.lib.avc_rasterize_scratch_bytes(fz.shape[0], S2))
-        self._checked(self.lib.avc_rasterize_faces(L.ptr(fz), L.ptr(self.light2), fz.shape[0], S2, self.near, self.far, L.ptr(img),
-                                                   L.ptr(zbuf), L.stream()), "avc_rasterize_faces")
-        grey = torch.nn.functional.avg_pool2d(img[None, None], kernel_size=2, stride=2)[0, 0]
-        return grey.flip(1)[..., None].repeat(1, 1, 3) if rgb_flipped else grey
+        """nr.Renderer(camera_mode='look')(vertices, faces, ones) -> [S,S] grey image (before the x flip); rgb_flipped: [S,S,3], x-flipped.
+        Projection + rasteriser + 2 x 2 average (+ x flip + channels) in four launches (csrc/avc_raster.hip), one upload (the camera)"""
+        dev, S, F2 = self.v_world.device, self.image_size, self.faces2.shape[0]
+        cam = h2d.upload(camera_frame(eye, direction), dev)
+        out = torch.empty((S, S, 3) if rgb_flipped else (S, S), device=dev, dtype=torch.float32)
+        zbuf = _scratch_for(dev, (1, F2, S), self.lib.avc_rasterize_scratch_bytes(F2, 2 * S))
+        _checked(self.lib.avc_rasterize_mesh(L.ptr(self.v_world), self.v_world.shape[0], L.ptr(self._faces2_i32), F2, L.ptr(cam), self.width,
+                                             L.ptr(self.light2), S, self.near, self.far, L.ptr(self._ndc), L.ptr(out), int(rgb_flipped),
+                                             3 if rgb_flipped else 1, L.ptr(zbuf), L.stream()), "avc_rasterize_mesh")
+        return out
 
     def __call__(self, eye, at):
         eye, at = np.asarray(eye, np.float64), np.asarray(at, np.float64)

@@ -291,7 +291,9 @@ int avc_probe_mfma(const void* a_f16, const void* b_f16, float* d, const void* a
  * (lighting.py, world space).  image[image_size, image_size], row 0 = top (rasterize.py's final flip applied).  scratch: the
  * z-buffer of 64-bit (depth bits, face index) keys the faces race into with atomicMin + the list of the faces too large for that
  * (handled tile by tile) -- avc_rasterize_scratch_bytes(F, image_size) bytes that the caller fills with 0xFF once; every call hands
- * them back that way. */
+ * them back that way.
+ * All three forward entry points launch one set of kernels (csrc/avc_raster.hip; the face-list form and avc_rasterize_mesh are the N = 1 case of
+ * avc_rasterize_mesh_save's), so their images agree to the bit. */
 /* The same from the world-space mesh in four launches (projection look.py / perspective.py -> rasteriser at the 2 x super-sampled size on
  * faces gathered through idx [F,3] -> 2 x 2 average, optional x flip (models/utils.py:124) and three equal channels): v_world [V,3], cam =
  * device [12] (eye, x / y / z axis of the look frame), width = tan(viewing angle); ndc [V,3] scratch; out [S,S] or [S,S,3];
@@ -308,7 +310,7 @@ int avc_rasterize_faces(const float* faces, const float* light, int F, int image
  * section 8; tests/nr_grad_restatement.py).
  * avc_rasterize_mesh_save: N renders in one call, render i = the world-space mesh v_world[i] [V,3] (one topology idx [F,3], fill_back
  * copies included) seen by camera cam[i] [12] (as avc_rasterize_mesh) with face light light[i] [F].  Outputs: image [N,S,S] (the pooled
- * grey image, no x flip: bit-identical to avc_rasterize_mesh with flip_x = 0, channels = 1), ndc [N,V,3], fidx int32 [N,2S,2S] = the
+ * grey image, no x flip: avc_rasterize_mesh's with flip_x = 0, channels = 1, the same kernels), ndc [N,V,3], fidx int32 [N,2S,2S] = the
  * winning face of every super-sampled pixel, z-buffer orientation (row 0 = bottom), -1 = background.  scratch: N x
  * avc_rasterize_scratch_bytes(F, 2 S) bytes, 0xFF-filled on entry, left so. */
 int avc_rasterize_mesh_save(const float* v_world, int N, int V, const int* idx, int F, const float* cam, float width, const float* light, int S,

@@ -1,7 +1,8 @@
-"""The rasteriser's batched forward with save and neural_renderer's approximate backward on the MI355X (csrc/avc_raster_grad.hip behind
+"""The rasteriser's forward entry points and neural_renderer's approximate backward on the MI355X (csrc/avc_raster.hip, avc_raster_grad.hip behind
 avatarclip_amd.mesh_render): images bit-identical to MeshPrior's, the face-index map and the backward against the fp32 restatement
-(tests/nr_grad_restatement.py) at production size and on adversarial meshes, batched renders against single ones, the scratch the calls leave
-behind, F = 0 at the C ABI, determinism, and the paper's silhouette-fitting experiment."""
+(tests/nr_grad_restatement.py) at production size and on adversarial meshes, the single-render and face-list forms against the same restatement,
+batched renders against single ones, the scratch the calls leave behind, F = 0 at the C ABI, determinism, and the paper's silhouette-fitting
+experiment."""
 import os
 
 import numpy as np
@@ -437,8 +438,8 @@ def test_batched_renders_equal_single_renders():
 
 @gpu
 def test_animate_expand_path_sums_the_per_render_gradients():
-    """AnimateContext._render_hip_grad: 5 angles x bs = 2 bodies in one call through an expand; the vertices' gradient is the sum of the
-    gradients of the ten renders made one by one"""
+    """AnimateContext._render_hip_grad: 5 angles x bs = 2 bodies in one call (render_grey_batch repeats the bodies, one copy per camera); the
+    vertices' gradient is the sum of the gradients of the ten renders made one by one"""
     from types import SimpleNamespace
     from avatarclip_amd import animate as A
     from avatarclip_amd.mesh_render import render_grey_batch
@@ -471,6 +472,7 @@ def test_scratch_is_left_empty_and_layout_changes_do_not_leak():
     point rejects (N = 0), all give what the first call gave, bit for bit"""
     from avatarclip_amd import lib as L
     from avatarclip_amd import mesh_render as M
+    from avatarclip_amd import smpl_prior as SP
     vws, Fc = _template_batch(3, 8)
     F2n = 2 * len(Fc)
 
@@ -481,8 +483,8 @@ def test_scratch_is_left_empty_and_layout_changes_do_not_leak():
         img.backward(torch.randn(img.shape, generator=torch.Generator().manual_seed(N)).cuda())
         need = N * L.load().avc_rasterize_scratch_bytes(F2n, 2 * S)
         key = (str(vw.device), L.stream(), (N, F2n, S), need)
-        assert key in M._scratch
-        assert _scratch_is_empty(M._scratch_for(vw.device, (N, F2n, S), need), N, F2n, S)
+        assert key in SP._scratch
+        assert _scratch_is_empty(SP._scratch_for(vw.device, (N, F2n, S), need), N, F2n, S)
         return [t.detach().clone() for t in (img, ndc, fidx, vw.grad)]
 
     def same(a, b):
@@ -516,3 +518,96 @@ def test_no_faces_at_the_c_abi():
                                             None, L.stream()) == 0
     torch.cuda.synchronize()
     assert (gn == 0).all()
+
+
+def _single(vw, faces2, light, S, flip_x, channels):
+    """avc_rasterize_mesh (IDENT_CAM, width 1) on its own fresh 0xFF scratch; outputs pre-filled with NaN -> (rc, out, ndc, scratch)"""
+    from avatarclip_amd import lib as L
+    from avatarclip_amd.mesh_render import NEAR, FAR
+    lib = L.load()
+    F2n = faces2.shape[0] if faces2 is not None else 0
+    out = torch.full((S, S, 3) if channels == 3 else (S, S), float("nan"), device="cuda")
+    ndc = torch.full((vw.shape[0], 3), float("nan"), device="cuda")
+    scratch = torch.full((lib.avc_rasterize_scratch_bytes(F2n, 2 * S),), 255, dtype=torch.uint8, device="cuda")
+    rc = lib.avc_rasterize_mesh(L.ptr(vw), vw.shape[0], L.ptr(faces2), F2n, L.ptr(torch.from_numpy(IDENT_CAM).cuda()), 1.0, L.ptr(light), S, NEAR, FAR,
+                                L.ptr(ndc), L.ptr(out), flip_x, channels, L.ptr(scratch), L.stream())
+    return rc, out, ndc, scratch
+
+
+def _face_list(faces9, light, n):
+    """avc_rasterize_faces at n x n on its own fresh 0xFF scratch; the image pre-filled with NaN -> (rc, image, scratch)"""
+    from avatarclip_amd import lib as L
+    from avatarclip_amd.mesh_render import NEAR, FAR
+    lib = L.load()
+    Fn = faces9.shape[0] if faces9 is not None else 0
+    image = torch.full((n, n), float("nan"), device="cuda")
+    scratch = torch.full((lib.avc_rasterize_scratch_bytes(Fn, n),), 255, dtype=torch.uint8, device="cuda")
+    rc = lib.avc_rasterize_faces(L.ptr(faces9), L.ptr(light), Fn, n, NEAR, FAR, L.ptr(image), L.ptr(scratch), L.stream())
+    return rc, image, scratch
+
+
+@gpu
+@pytest.mark.parametrize("case", sorted(SYNTH))
+def test_single_render_and_face_list_forms_match_the_restatement(case):
+    """avc_rasterize_mesh and avc_rasterize_faces bit for bit against the fp32 restatement on the adversarial meshes (the save form is pinned
+    by test_backward_matches_the_restatement_on_adversarial_meshes): ndc, the pooled image plain and x-flipped with three channels, the
+    un-pooled face-list image, and the scratch each call leaves"""
+    S = 32
+    n = 2 * S
+    vw, ndc_expect, faces, F2, light, _, _ = synthetic_case(case, S)
+    fi = R.rasterize_index(ndc_expect, F2, n)
+    pooled = R.pooled_image(fi, light)
+    faces2, lt = torch.from_numpy(F2.astype(np.int32)).cuda(), torch.from_numpy(light).cuda()
+    for flip_x, channels in ((0, 1), (1, 3)):
+        rc, out, ndc, scratch = _single(torch.from_numpy(vw).cuda(), faces2, lt, S, flip_x, channels)
+        assert rc == 0
+        assert np.array_equal(ndc.cpu().numpy(), ndc_expect)
+        out = out.cpu().numpy()
+        if channels == 3:
+            assert out.shape == (S, S, 3) and all(np.array_equal(out[..., c], pooled[:, ::-1]) for c in range(3))
+        else:
+            assert np.array_equal(out, pooled), np.argwhere(out != pooled)[:5]
+        assert _scratch_is_empty(scratch, 1, len(F2), S)
+    rc, image, scratch = _face_list(torch.from_numpy(np.ascontiguousarray(ndc_expect[F2].reshape(-1, 9))).cuda(), lt, n)
+    assert rc == 0
+    expect = np.where(fi >= 0, light[np.maximum(fi, 0)], np.float32(0))[::-1]
+    assert np.array_equal(image.cpu().numpy(), expect), np.argwhere(image.cpu().numpy() != expect)[:5]
+    assert _scratch_is_empty(scratch, 1, len(F2), S)
+
+
+@gpu
+def test_no_faces_in_the_single_render_and_face_list_forms():
+    """F = 0: both forms return 0, give an all-zero image and leave the scratch empty"""
+    S = 32
+    vw = torch.from_numpy(np.random.RandomState(0).uniform(-1, 1, (5, 3)).astype(np.float32) + np.float32([0, 0, 3])).cuda()
+    for flip_x, channels in ((0, 1), (1, 3)):
+        rc, out, ndc, scratch = _single(vw, None, None, S, flip_x, channels)
+        assert rc == 0 and (out == 0).all() and torch.isfinite(ndc).all()
+        assert _scratch_is_empty(scratch, 1, 0, S)
+    rc, image, scratch = _face_list(None, None, 2 * S)
+    assert rc == 0 and (image == 0).all()
+    assert _scratch_is_empty(scratch, 1, 0, S)
+
+
+@gpu
+def test_render_hip_equals_one_prior_render_per_camera_and_body():
+    """AnimateContext._render_hip (one no-gradient batched call) against the statement it replaces: the same elevation draws, then every
+    (camera, body) rendered by its own MeshPrior, camera-major -- bit for bit"""
+    from avatarclip_amd import animate as A
+    from avatarclip_amd.shapegen_render import get_points_from_angles
+    from avatarclip_amd.smpl_prior import MeshPrior
+    S, bs, angles = 32, 2, A.DEFAULT_ANGLES[:3]
+    vws, Fc = _template_batch(bs, 9)
+    verts = torch.from_numpy(vws).cuda()
+    ctx = A.AnimateContext(None, None, None, None, device="cuda", image_size=S)
+    np.random.seed(13)
+    out = ctx.render_fn(verts, Fc, angles)
+    assert ctx.render_fn.__name__ == "_render_hip" and out.shape == (len(angles) * bs, 3, S, S) and not out.requires_grad
+    np.random.seed(13)
+    eyes = [get_points_from_angles(A.CAMERA_DISTANCE, np.random.randn() * 0.3, a) for a in angles]
+    priors = [MeshPrior(v, Fc, device="cuda", image_size=S) for v in vws]
+    for j, eye in enumerate(eyes):
+        for i, p in enumerate(priors):
+            g = p.render_grey(eye.astype(np.float32), (-eye / np.linalg.norm(eye)).astype(np.float32))
+            assert (g > 0).any()
+            assert torch.equal(out[j * bs + i], g.unsqueeze(0).expand(3, -1, -1)), (j, i)

@@ -62,6 +62,28 @@ def test_renderer_restatement_conventions_against_reference_renders():
         assert abs(float(img[both].mean() * 255) - float(ims[k][both].mean())) < 25     # same light model (grey level of the body)
 
 
+def _prior_by_torch_ops(prior, eye, at):
+    """MeshPrior.__call__ stated with torch ops around the face-list rasteriser: look + perspective, the reference's patch (behind the camera
+    -> 0), the gather to faces [F,9], avc_rasterize_faces at 2 S, avg_pool2d, the x flip and the three equal channels"""
+    from avatarclip_amd import h2d, lib as L
+    from avatarclip_amd.smpl_prior import camera_frame
+    dev = prior.v_world.device
+    eye, at = np.asarray(eye, np.float64), np.asarray(at, np.float64)
+    cam = h2d.upload(camera_frame(eye, (at - eye) / np.linalg.norm(at - eye)), dev)
+    v = (prior.v_world - cam[:3]) @ cam[3:].reshape(3, 3).t()
+    ndc = torch.stack([v[:, 0] / v[:, 2] / prior.width, v[:, 1] / v[:, 2] / prior.width, v[:, 2]], dim=1)   # perspective.py
+    ndc = torch.where(v[:, 2:3] <= 0, torch.zeros_like(ndc), ndc)     # ... with the reference's patch (README.md:126-134)
+    fz = ndc[prior.faces2].reshape(-1, 9).contiguous()
+    S2 = 2 * prior.image_size                                    # anti_aliasing=True
+    img = torch.empty(S2, S2, device=dev, dtype=torch.float32)
+    lib = L.load()
+    zbuf = torch.full((lib.avc_rasterize_scratch_bytes(fz.shape[0], S2),), 255, dtype=torch.uint8, device=dev)
+    L.check(lib.avc_rasterize_faces(L.ptr(fz), L.ptr(prior.light2), fz.shape[0], S2, prior.near, prior.far, L.ptr(img), L.ptr(zbuf), L.stream()),
+            "avc_rasterize_faces")
+    grey = torch.nn.functional.avg_pool2d(img[None, None], kernel_size=2, stride=2)[0, 0]
+    return grey.flip(1)[..., None].repeat(1, 1, 3)
+
+
 @gpu
 def test_hip_rasteriser_matches_restatement():
     import time
@@ -75,13 +97,10 @@ def test_hip_rasteriser_matches_restatement():
             # close-ups: faces whose boxes hold thousands of sub-pixels (the tile-parallel pass of the rasteriser), the second one
             # from so near that part of the body is beside / behind the camera
             (np.array([0.05, 0.35, 0.55]), np.array([0.0, 0.3, 0.0])), (np.array([0.1, 0.0, 0.22]), np.array([0.0, 0.1, 0.0]))]
-    import avatarclip_amd.smpl_prior as SP
     for eye, at in cams:
         # the four-launch form (projection + pooling inside the library) against the torch ops around avc_rasterize_faces: same image up to
         # the few sub-pixels whose edge test sits within an ulp of the projection's rounding
-        SP.FUSED_PRIOR = False
-        unf = prior(eye, at).cpu().numpy()
-        SP.FUSED_PRIOR = True
+        unf = _prior_by_torch_ops(prior, eye, at).cpu().numpy()
         out = prior(eye, at).cpu().numpy()
         nd = (np.abs(out[..., 0] - unf[..., 0]) > 1e-6).sum()
         assert nd <= 24 and np.abs(out - unf).max() <= 0.51, (nd, np.abs(out - unf).max())     # (13 of 65 536 pixels on the nearest close-up, 0 on the far views)
