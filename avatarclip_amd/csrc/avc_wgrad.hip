@@ -380,6 +380,25 @@ extern "C" int avc_weight_grad_all(const void* fpanels, int ftiles, const void* 
       avc_set_error("avc_weight_grad_all: 1 <= ta <= 8, 1 <= tb <= 9 (or the 9 x 9 product)");
       return 1;
     }
+    // a table that would read outside a block's region or write outside a split's row is refused here, before anything is launched
+    const int* d = pp.v[i];
+    if ((d[6] != 0 && d[6] != 1) || (d[7] != 0 && d[7] != 1)) {
+      avc_set_error("avc_weight_grad_all: operand types are 0 (F region) or 1 (G region)");
+      return 1;
+    }
+    const long tiles_a = d[6] ? gtiles : ftiles, tiles_b = d[7] ? gtiles : ftiles;
+    if (d[0] < 0 || (long)d[0] + d[1] > tiles_a || d[2] < 0 || (long)d[2] + d[3] > tiles_b) {
+      avc_set_error("avc_weight_grad_all: a pair's tiles lie outside their region");
+      return 1;
+    }
+    if (d[4] < 0 || (long)d[4] + (long)d[1] * d[3] * 1024 > out_stride) {
+      avc_set_error("avc_weight_grad_all: a pair's products lie outside out_stride");
+      return 1;
+    }
+    if (d[5] >= 0 && (long)d[5] + 32 * d[1] > bias_stride) {
+      avc_set_error("avc_weight_grad_all: a pair's bias sums lie outside bias_stride");
+      return 1;
+    }
   }
   if (nsplit < 1) nsplit = 1;
   const int lds_bytes = WG_DEPTH * WG_BUF_BYTES;

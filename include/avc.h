@@ -140,7 +140,9 @@ int avc_render_points_bwd(int net, const float* pts, const float* rays_o, const 
  * products accumulate in fp32.  partial[split][out_off + ((ta_i * tb + tb_j) * 64 + lane) * 16 + r] = element
  * dW[32 ta_i + (r&3)+8(r>>2)+4h][32 tb_j + n] of lane (n,h); bias_partial[split][bias_off + 32 ta_i + n] = sum_points
  * A[:, 32 ta_i + n] (bias_off < 0: none).  nsplit = split-K factor (grid x); split s writes its slab at
- * partial + s*out_stride (bias_partial + s*bias_stride), floats; the caller sums the slabs (no atomics). */
+ * partial + s*out_stride (bias_partial + s*bias_stride), floats; the caller sums the slabs (no atomics).  A table that would leave its buffers is refused
+ * before the launch (returns 1): types outside {0, 1}, a tile range outside [0, ftiles) resp. [0, gtiles), out_off + ta*tb*1024 >
+ * out_stride, bias_off + 32*ta > bias_stride. */
 int avc_weight_grad_all(const void* fpanels, int ftiles, const void* gpanels, int gtiles, int npairs,
                         const int* pairs /* host */, long nblk, float* partial, float* bias_partial, int nsplit,
                         int out_stride, int bias_stride, void* stream);

@@ -11,6 +11,8 @@ Tolerances (fp32 oracle vs f16-MFMA forward / bf16-MFMA gradient sweeps, fp32 ac
                  amplifies 1e-7 weight noise where the pdf is flat)
   compositing    <= 2e-5 (pure fp32 kernels)
   dense grads    relative L2 error <= 3e-2 per tensor (bf16 operands), cosine >= 0.999
+  weight-gradient kernel (avc_weight_grad_all / _reduce)   exact on integer panels; on real panels n 2^-23 sum |a| |b| per element of
+                 a split of n points (tests/test_gpu_wgrad.py)
 """
 import numpy as np
 import pytest
