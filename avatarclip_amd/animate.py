@@ -522,9 +522,32 @@ def build_motion_generator(conf, ctx, **assets):
     return MOTION_GENERATORS[name](ctx, name=name, **conf, **assets)
 
 
-def run(conf, ctx, pose_assets=None, motion_assets=None):
+def _write_previews(ctx, out_dir, poses, motion, size):
+    """candidate_<i>.png (the front view of every candidate, all under ONE camera framed over all of them, so the pictures compare) and
+    motion.gif (the fixed front camera, preview's default fps): the SMPL body of ctx.smpl posed by smpl_lbs.pose_hip, rendered by the preview
+    rasteriser.  Draws nothing from any random generator and leaves its inputs alone."""
+    from . import preview as P
+    from . import smpl_lbs
+    for name, p in (("candidate", poses), ("motion", motion)):
+        if p is None or p.shape[0] == 0:
+            continue
+        body = torch.from_numpy(P.body_pose(p.detach().cpu().numpy()))
+        v = smpl_lbs.pose_hip(ctx.smpl, body)
+        eyes, ats, near, far = P.frame_cameras(v, 1, up="y")
+        images = P.render_frames(v, ctx.smpl["faces"], None, eyes, ats, up="y", image_size=size, near=near, far=far)
+        if name == "motion":
+            P.save_frames(images, os.path.join(out_dir, "motion.gif"))
+        else:
+            for i in range(images.shape[0]):
+                P.save_frames(images[i:i + 1], os.path.join(out_dir, "candidate_%d.png" % i))
+
+
+def run(conf, ctx, pose_assets=None, motion_assets=None, preview=False, preview_size=512):
     """main.py:14-41: candidate poses (saved as candidate_<i>.npy), then -- unless general.mode == 'pose' -- the motion (motion.npy).  The
-    reference also writes pyrender previews (visualize.py); those are not part of the generators and are left to the caller."""
+    reference also writes pyrender pictures of them (candidate_<i>.jpg, motion.mp4; visualize.py render_pose / render_motion): with
+    `preview` this writes candidate_<i>.png and motion.gif of `preview_size` pixels from the HIP posing kernel and the preview rasteriser
+    (preview.py: its own camera framing and shading, not pyrender's; no .jpg / .mp4 encoder here).  Off by default; the returned tensors
+    are the same either way."""
     out_dir = conf.get_string("general.base_exp_dir")
     os.makedirs(out_dir, exist_ok=True)
     text = conf.get_string("general.text")
@@ -532,14 +555,18 @@ def run(conf, ctx, pose_assets=None, motion_assets=None):
     for i in range(poses.shape[0]):
         np.save(os.path.join(out_dir, "candidate_%d.npy" % i), poses[i].detach().cpu().numpy())
     if conf.get_string("general.mode") == "pose":
+        if preview:
+            _write_previews(ctx, out_dir, poses, None, int(preview_size))
         return poses, None
     motion = build_motion_generator(dict(conf["motion_generator"]), ctx, **(motion_assets or {})).get_motion(text, poses=poses)
     np.save(os.path.join(out_dir, "motion.npy"), motion.detach().cpu().numpy())
+    if preview:
+        _write_previews(ctx, out_dir, poses, motion, int(preview_size))
     return poses, motion
 
 
 def main(argv=None):
-    """python -m avatarclip_amd.animate [--renderer_gradient] --conf confs/base.conf --clip_weights ViT-B-32.pt --bpe bpe_simple_vocab_16e6.txt.gz --smpl SMPL_NEUTRAL.pkl
+    """python -m avatarclip_amd.animate [--renderer_gradient] [--preview] --conf confs/base.conf --clip_weights ViT-B-32.pt --bpe bpe_simple_vocab_16e6.txt.gz --smpl SMPL_NEUTRAL.pkl
     --vposer data/vposer [--codebook data/codebook.pth] [--realnvp data/pose_realnvp.pth] [--motion_vae data/motion_vae.pth]
     (AvatarAnimate/main.py with the assets its constructors load named on the command line; VPoser itself comes from the `human_body_prior` package)"""
     import argparse
@@ -551,6 +578,8 @@ def main(argv=None):
     ap.add_argument("--renderer_gradient", action="store_true",
                     help="differentiate the renders (neural_renderer's approximate backward, restated): PoseOptimizer, VPoserOptimizer and "
                          "MotionOptimizer with clip_coef > 0 (the reference's confs/base.conf) need it")
+    ap.add_argument("--preview", action="store_true", help="also write candidate_<i>.png and, in motion mode, motion.gif: the SMPL body in those poses")
+    ap.add_argument("--preview_size", type=int, default=512)
     for name in ("clip_weights", "bpe", "smpl", "vposer"):
         ap.add_argument("--" + name, required=True)
     for name in ("codebook", "realnvp", "motion_vae"):
@@ -571,7 +600,8 @@ def main(argv=None):
     with open(args.conf) as fh:
         conf = ConfigFactory.parse_string(fh.read())
     pose_assets = {"codebook_path": args.codebook} if args.codebook else ({"ckpt_path": args.realnvp} if args.realnvp else {})
-    run(conf, ctx, pose_assets=pose_assets, motion_assets={"ckpt_path": args.motion_vae} if args.motion_vae else {})
+    run(conf, ctx, pose_assets=pose_assets, motion_assets={"ckpt_path": args.motion_vae} if args.motion_vae else {}, preview=args.preview,
+        preview_size=args.preview_size)
 
 
 if __name__ == "__main__":

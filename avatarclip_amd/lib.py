@@ -90,6 +90,8 @@ _SIGS = {
     "avc_preview_raster": (c_int, [P, c_int, c_int, P, c_int, c_int, P, P]),
     "avc_preview_shade": (c_int, [P, P, c_int, c_int, P, c_int, P, c_int, P, c_float, c_float, c_float, c_float, c_float, c_int, c_int, P, P, P, P]),
     "avc_skin_blend4": (c_int, [P, P, P, P, c_int, c_int, c_int, P, P]),
+    "avc_smpl_joint_mats": (c_int, [P, P, P, c_int, P, P, P]),
+    "avc_smpl_pose": (c_int, [P, P, P, P, P, c_int, c_int, P, P]),
 }
 _OPTIONAL = {}
 

@@ -1,11 +1,15 @@
-"""Look at what the pipeline writes: a turn-table or a played motion of a .ply, a .ply + .pc2 or a .glb, as a GIF or a PNG.
+"""Look at what the pipeline writes: a turn-table or a played motion of a .ply, a .ply + .pc2, a .glb, or of the SMPL body in the poses
+animate writes, as a GIF or a PNG.
 
-    python -m avatarclip_amd.preview (--mesh X.ply [--pc2 M.pc2] | --glb X.glb) --out P.gif|P.png
+    python -m avatarclip_amd.preview (--mesh X.ply [--pc2 M.pc2] | --glb X.glb | --smpl SMPL.npz --poses X.npy) --out P.gif|P.png
                                      [--views 36] [--size 512] [--ss 2] [--up y|z] [--elevation deg] [--fov deg]
                                      [--fps 30] [--every k] [--frames-dir D] [--orbit]
 
-A static source (a .ply alone, a .glb without a track) makes a turn-table of --views frames; a moving one (a .pc2, a .glb with a track)
-plays its frames from the fixed front camera, or from a camera that goes round once with --orbit.  A .png takes the first frame.  --up is
+A static source (a .ply alone, a .glb without a track, one pose) makes a turn-table of --views frames; a moving one (a .pc2, a .glb with a
+track, a motion of more than one pose) plays its frames from the fixed front camera, or from a camera that goes round once with --orbit.
+A .png takes the first frame.  --smpl / --poses pose the SMPL body itself (smpl_lbs.pose_hip, csrc/avc_smpl.hip) in animate's
+candidate_<i>.npy or motion.npy: the uncoloured grey body, y up, facing +z, the root rotation dropped as the reference's previews drop it
+(AvatarAnimate/visualize.py:98-102, :115-119), under frame_cameras' auto-framed camera -- NOT pyrender's fixed camera of f = 5000.  --up is
 the axis that points up in the file: y for Runner.validate_mesh's .ply and for rig's .glb (SMPL's frame), z for drive's outputs (drive
 rotates into Blender's frame), which is the default as soon as --pc2 is given.  A .glb that rig wrote WITH --motion (and without
 --keep_root) also plays in Blender's frame, because its tracks carry drive's root rotation (pi/2, 0, 0): give --up z for it (rig --preview
@@ -291,6 +295,44 @@ def glb_source(glb, every=1, device=None):
     return v, t, c, bool(g["animation"])
 
 
+def body_pose(array):
+    """float32 [T,72] full SMPL poses for a preview, from the layouts drive.read_pose_my accepts: [T, >= 72] (the first 72 values), [T, 69]
+    (the body pose without the root: animate's motion.npy), [T, 63] (6 zeros appended: animate's candidate_<i>.npy); a 1-D pose is one
+    frame.  The root rotation is set to ZERO, not to drive's (pi/2, 0, 0): the body stands y up and faces +z.  (visualize.py:98-102,
+    :115-119 drop the root as well; their global_orient of pi about x and their mesh's turn by 180 degrees about x cancel up to a
+    translation, which the auto-framing removes.)  Plain numpy."""
+    p = np.array(array.detach().cpu().numpy() if torch.is_tensor(array) else array, dtype=np.float32)
+    if p.ndim == 1:
+        p = p[None]
+    if p.ndim != 2 or p.shape[0] == 0 or not (p.shape[1] in (63, 69) or p.shape[1] >= 72):
+        raise ValueError("poses are [T, 72], [T, 69] or [T, 63] (or one such pose), got %s" % (p.shape,))
+    if p.shape[1] == 63:
+        p = np.concatenate([p, np.zeros((p.shape[0], 6), np.float32)], 1)
+    if p.shape[1] == 69:
+        p = np.concatenate([np.zeros((p.shape[0], 3), np.float32), p], 1)
+    p = np.ascontiguousarray(p[:, :72])
+    p[:, :3] = 0
+    return p
+
+
+def smpl_source(smpl, poses, every=1, device=None):
+    """(vertices [T,V,3] device tensor, faces, None, moving): the SMPL body in the given poses (a .npy path or an array, body_pose's
+    layouts), posed by smpl_lbs.pose_hip.  smpl: a path for smpl_lbs.load_smpl_arrays or its dict (with `faces`).  moving = T > 1."""
+    from . import smpl_lbs
+    p = body_pose(np.load(poses) if isinstance(poses, (str, os.PathLike)) else poses)[::max(1, int(every))]
+    dev = torch.device(device) if device is not None else torch.device("cuda")
+    if isinstance(smpl, (str, os.PathLike)):
+        a = smpl_lbs.load_smpl_arrays(str(smpl), dev)
+    else:                                     # (pose_hip works where the arrays live; a device given here moves them first)
+        a = smpl if device is None else {k: (x.to(dev) if torch.is_tensor(x) and k != "parents" else x) for k, x in smpl.items()}
+    if "faces" not in a:
+        raise ValueError("the SMPL arrays hold no faces")
+    v = smpl_lbs.pose_hip(a, torch.from_numpy(np.ascontiguousarray(p)))
+    faces = a["faces"]
+    faces = np.asarray(faces.cpu() if torch.is_tensor(faces) else faces).reshape(-1, 3).astype(np.int32)
+    return v, faces, None, p.shape[0] > 1
+
+
 # ---------------------------------------------------------------------------------------------------------------- files
 def save_frames(images, out, fps=30.0, frames_dir=None):
     """uint8 [N,S,S,3] -> an animated GIF (all frames) or a PNG (the first); frames_dir: numbered PNGs of every frame as well"""
@@ -314,10 +356,12 @@ def save_frames(images, out, fps=30.0, frames_dir=None):
 
 
 def preview(out, mesh=None, pc2=None, glb=None, views=36, size=512, ss=2, up=None, elevation=10.0, fov=40.0, fps=30.0, every=1,
-            frames_dir=None, orbit=False, margin=0.05):
+            frames_dir=None, orbit=False, margin=0.05, smpl=None, poses=None):
     """The whole tool: one source -> frames -> a file.  Returns (out, images)."""
-    if (mesh is None) == (glb is None):
-        raise ValueError("give exactly one source: --mesh X.ply [--pc2 M.pc2] or --glb X.glb")
+    if (smpl is None) != (poses is None):
+        raise ValueError("--smpl and --poses go together: the SMPL model and the poses to put it in")
+    if (mesh is not None) + (glb is not None) + (smpl is not None) != 1:
+        raise ValueError("give exactly one source: --mesh X.ply [--pc2 M.pc2], --glb X.glb or --smpl SMPL.npz --poses X.npy")
     if pc2 is not None and mesh is None:
         raise ValueError("--pc2 needs the --mesh it was written for")
     check_raster(size, ss)
@@ -325,7 +369,12 @@ def preview(out, mesh=None, pc2=None, glb=None, views=36, size=512, ss=2, up=Non
         raise ValueError("--out ends in .gif or .png, got %r" % out)
     if up is None:
         up = "z" if pc2 is not None else "y"
-    v, t, c, moving = mesh_source(mesh, pc2, every) if mesh is not None else glb_source(glb, every)
+    if mesh is not None:
+        v, t, c, moving = mesh_source(mesh, pc2, every)
+    elif glb is not None:
+        v, t, c, moving = glb_source(glb, every)
+    else:
+        v, t, c, moving = smpl_source(smpl, poses, every)
     v = v if torch.is_tensor(v) else torch.from_numpy(v).cuda()
     T = v.shape[0]
     n = T if moving else int(views)
@@ -339,6 +388,8 @@ def main(argv=None):
     ap.add_argument("--mesh", default=None, help="a .ply (Runner.validate_mesh's, or drive's <name>_cleaned_apose.ply)")
     ap.add_argument("--pc2", default=None, help="drive's point cache of that mesh: plays its frames")
     ap.add_argument("--glb", default=None, help="rig's .glb: plays its rotation tracks, or shows the rest pose")
+    ap.add_argument("--smpl", default=None, help="the SMPL model (.npz export or the official .pkl): the body itself, in the poses of --poses")
+    ap.add_argument("--poses", default=None, help="animate's candidate_<i>.npy (one pose: a turn-table) or motion.npy (played), for --smpl")
     ap.add_argument("--out", required=True, help="P.gif (all frames) or P.png (the first)")
     ap.add_argument("--views", type=int, default=36, help="frames of the turn-table of a static source")
     ap.add_argument("--size", type=int, default=512)
@@ -355,7 +406,8 @@ def main(argv=None):
         if args.views < 1 or args.every < 1 or args.fps <= 0:
             raise ValueError("--views, --every and --fps are positive")
         out, _ = preview(args.out, mesh=args.mesh, pc2=args.pc2, glb=args.glb, views=args.views, size=args.size, ss=args.ss, up=args.up,
-                         elevation=args.elevation, fov=args.fov, fps=args.fps, every=args.every, frames_dir=args.frames_dir, orbit=args.orbit)
+                         elevation=args.elevation, fov=args.fov, fps=args.fps, every=args.every, frames_dir=args.frames_dir, orbit=args.orbit,
+                         smpl=args.smpl, poses=args.poses)
     except ValueError as e:
         raise SystemExit("preview: %s" % e)
     print(out)

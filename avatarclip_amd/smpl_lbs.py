@@ -57,6 +57,69 @@ def lbs(v_shaped, rot_mats, posedirs, J_regressor, parents, lbs_weights):
     return verts, J_transformed
 
 
+def _check_pose_hip(smpl_arrays, pose, v_shaped):
+    """the shapes pose_hip's kernels are written for; returns (T, V)"""
+    a = smpl_arrays
+    for k in ("v_template", "posedirs", "J_regressor", "parents", "lbs_weights"):
+        if k not in a:
+            raise ValueError("pose_hip: the SMPL arrays lack %r" % k)
+    vt, pd, jr, w = a["v_template"], a["posedirs"], a["J_regressor"], a["lbs_weights"]
+    parents = [int(p) for p in np.asarray(a["parents"].cpu() if torch.is_tensor(a["parents"]) else a["parents"]).reshape(-1)]
+    if vt.dim() != 2 or vt.shape[1] != 3:
+        raise ValueError("pose_hip: v_template must be [V, 3], got %s" % (tuple(vt.shape),))
+    V = vt.shape[0]
+    if len(parents) != 24 or jr.dim() != 2 or jr.shape[0] != 24 or w.dim() != 2 or w.shape[1] != 24:
+        raise ValueError("pose_hip poses SMPL's 24 joints, got %d parents, J_regressor %s, lbs_weights %s"
+                         % (len(parents), tuple(jr.shape), tuple(w.shape)))
+    if jr.shape[1] != V or w.shape[0] != V:
+        raise ValueError("pose_hip: J_regressor %s / lbs_weights %s do not fit %d vertices" % (tuple(jr.shape), tuple(w.shape), V))
+    if pd.dim() != 2 or pd.shape[0] != 207:
+        raise ValueError("pose_hip: posedirs must hold 207 = 23 x 9 pose-blend rows, got %s" % (tuple(pd.shape),))
+    if pd.shape[1] != 3 * V:
+        raise ValueError("pose_hip: posedirs must be [207, %d], got %s" % (3 * V, tuple(pd.shape)))
+    for i in range(1, 24):
+        if not 0 <= parents[i] < i:
+            raise ValueError("pose_hip: parents[%d] = %d, a parent must come before its child (0 <= parents[i] < i)" % (i, parents[i]))
+    if not (pose.dim() == 2 and pose.shape[1] == 72) and not (pose.dim() == 3 and tuple(pose.shape[1:]) == (24, 3)):
+        raise ValueError("pose_hip: pose must be [T, 72] or [T, 24, 3] axis-angle, got %s" % (tuple(pose.shape),))
+    if v_shaped is not None and tuple(v_shaped.shape) != (V, 3):
+        raise ValueError("pose_hip: v_shaped must be [%d, 3], got %s" % (V, tuple(v_shaped.shape)))
+    return pose.shape[0], V
+
+
+def pose_hip(smpl_arrays, pose, v_shaped=None):
+    """SMPL vertices float32 [T,V,3] (a device tensor) of axis-angle poses [T,72] or [T,24,3], FORWARD ONLY: two HIP launches
+    (csrc/avc_smpl.hip: avc_smpl_joint_mats, avc_smpl_pose) instead of lbs's hundred small kernels, no [T,V,4,4] tensor, no gradient.
+    `lbs` remains the differentiable path, and the one whose arithmetic the pinned scores were taken with (the two agree to fp32
+    rounding, not bit for bit).  v_shaped [V,3] defaults to v_template (betas = 0); the rest joints are J_regressor v_shaped, in torch.
+    smpl_arrays: load_smpl_arrays' dict.  The device is the arrays' when they live on one, else the current cuda device."""
+    as_t = lambda x: x if torch.is_tensor(x) else torch.as_tensor(np.asarray(x))
+    pose = as_t(pose)
+    v_shaped = None if v_shaped is None else as_t(v_shaped)
+    a = dict(smpl_arrays)
+    for k in ("v_template", "posedirs", "J_regressor", "lbs_weights"):
+        if k in a:
+            a[k] = as_t(a[k])
+    T, V = _check_pose_hip(a, pose, v_shaped)
+    from . import lib as L                                  # (after the checks: they need no library)
+    dev = a["v_template"].device if a["v_template"].is_cuda else torch.device("cuda")
+    f32 = lambda x: x.detach().to(device=dev, dtype=torch.float32).contiguous()
+    out = torch.empty(T, V, 3, device=dev, dtype=torch.float32)
+    if T == 0 or V == 0:
+        return out
+    vs = f32(a["v_template"] if v_shaped is None else v_shaped)
+    joints = torch.matmul(f32(a["J_regressor"]), vs).contiguous()
+    parents = torch.as_tensor(np.asarray(as_t(a["parents"]).cpu()).reshape(-1)).to(device=dev, dtype=torch.int32).contiguous()
+    feat = torch.empty(T, 207, device=dev, dtype=torch.float32)
+    A = torch.empty(T, 24, 12, device=dev, dtype=torch.float32)
+    # (every operand has a name that lives to the end of the function: memory a launch reads is not handed back before it is enqueued)
+    pose_d, posedirs, weights = f32(pose).reshape(T, 72), f32(a["posedirs"]), f32(a["lbs_weights"])
+    lib, s = L.load(), L.stream()
+    L.check(lib.avc_smpl_joint_mats(L.ptr(pose_d), L.ptr(joints), L.ptr(parents), T, L.ptr(feat), L.ptr(A), s), "avc_smpl_joint_mats")
+    L.check(lib.avc_smpl_pose(L.ptr(vs), L.ptr(posedirs), L.ptr(weights), L.ptr(feat), L.ptr(A), V, T, L.ptr(out), s), "avc_smpl_pose")
+    return out
+
+
 def load_smpl_arrays(path, device="cpu"):
     """.npz with the SMPL field names, or the official SMPL_*.pkl (chumpy objects are read through their `.r` array when the
     chumpy package is importable; posedirs is reshaped to [(J-1)*9, V*3] like smplx does)."""

@@ -437,6 +437,26 @@ int avc_preview_shade(const int* proj, const float* v, int N, int V, const int* 
 int avc_skin_blend4(const unsigned char* joints, const float* weights, const float* joint_mats, const float* rest, int M, int J, int T,
                     float* out, void* stream);
 
+/* ---- posing the SMPL body without a gradient (avatarclip_amd/smpl_lbs.py pose_hip, csrc/avc_smpl.hip) ----
+ * The forward of smpl_lbs.lbs (models/utils.py:176-224 with batch_rodrigues :72-106 and smplx's batch_rigid_transform) as two launches, for
+ * the previews the reference renders from smplx's vertices (AvatarAnimate/visualize.py:98-102 render_pose, :115-119 render_motion).  fp32,
+ * every multiply-add one fused operation in the order csrc/avc_smpl.hip's header states, no atomics: a frame's result is the same bits in
+ * every run, every batch and at every place in a batch.  T = 0 (or V = 0) returns 0 without a launch; a NULL or misaligned buffer is an error.
+ *
+ * avc_smpl_joint_mats: pose [T,24,3] axis-angle, joints [24,3] rest joints (J_regressor v_shaped, computed by the caller), parents int32 [24]
+ * with 0 <= parents[i] < i for i >= 1 (parents[0] is not read) -> feat [T,207] = (R_j - I), j = 1..23, row-major (lbs's pose_feature) and
+ * A [T,24,12] (16-byte aligned) = rows 0..2 of the rest-pose-relative joint transforms.  R = I + sin K + (1 - cos) K^2 with
+ * angle = |r + 1e-8| and K from r / angle (batch_rodrigues, its quirk at tiny angles kept); world_i = world_parent(i) [R_i | j_i - j_parent(i)],
+ * A_i = world_i - [0 | world_i.R j_i].  Contract: the caller checks the tree; a joint whose parent does not come before it gets NaN and reads
+ * nothing.
+ *
+ * avc_smpl_pose: v_shaped [V,3], posedirs [207, 3V], weights [V,24] dense (16-byte aligned), feat and A (16-byte aligned) as above ->
+ * out [T,V,3]: v_posed[t,v] = (sum_k feat[t,k] posedirs[k, 3v..3v+2]) + v_shaped[v], k ascending from 0; M = sum_j weights[v,j] A[t,j],
+ * j ascending from 0; out[t,v] = M (v_posed[t,v], 1).  Any T: the wrapper splits what one grid does not take. */
+int avc_smpl_joint_mats(const float* pose, const float* joints, const int* parents, int T, float* feat, float* A, void* stream);
+int avc_smpl_pose(const float* v_shaped, const float* posedirs, const float* weights, const float* feat, const float* A, int V, int T,
+                  float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
