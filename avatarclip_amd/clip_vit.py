@@ -1,8 +1,8 @@
 """CLIP ViT-B/32 image encoder on the gfx950 kernels -- drop-in for `perceptor.encode_image`
 (AvatarGen/AppearanceGen/main.py:259-260,512,518,524; upstream: OpenAI clip/model.py VisionTransformer, un-vendored).
 
-All GEMMs (patch embedding, in_proj, out_proj, c_fc, c_proj, visual.proj) run in avc_vit_linear (bf16 MFMA, fp32
-accumulate; the reference runs CLIP in fp16 on GPU), attention in avc_vit_attention_*.  Weights are frozen
+All GEMMs (patch embedding, in_proj, out_proj, c_fc, c_proj, visual.proj) run in avc_vit_linear / avc_vit_linear_packed (bf16 MFMA,
+fp32 accumulate; the reference runs CLIP in fp16 on GPU), attention in avc_vit_attention_*.  Weights are frozen
 (`requires_grad_(False)`, main.py:260): the backward only propagates to the pixels, re-using the same GEMM kernel on
 the packed transposes.  LayerNorm / residual bookkeeping are torch elementwise ops under autograd.
 Accepts an OpenAI-format state dict (`visual.*` keys, e.g. torch.jit.load('ViT-B-32.pt').state_dict()).
@@ -31,10 +31,7 @@ def pack_weight(w: torch.Tensor) -> torch.Tensor:
     return p.to(torch.bfloat16).reshape(-1)
 
 
-LIBRARY_GEMM = os.environ.get("AVC_VIT_LIBRARY_GEMM") == "1"   # see _linear_raw
-PACKED_PIPELINE = os.environ.get("AVC_VIT_PACKED", "1") != "0"   # see ClipVisionB32._encode_image_batched
 TRAIN_GRAPH = os.environ.get("AVC_CLIP_GRAPH", "1") != "0"        # see ClipVisionB32.encode_image
-FUSED_BLOCKS = os.environ.get("AVC_CLIP_FUSED_BLOCKS", "1") != "0"   # see BlocksFn (0: one autograd node per kernel)
 
 
 class _Lin:
@@ -43,7 +40,6 @@ class _Lin:
         self.N, self.K = w.shape
         self.wp = pack_weight(w)
         self.wtp = pack_weight(w.t().contiguous())
-        self.wd = w.to(torch.bfloat16) if LIBRARY_GEMM else None   # dense copy for the library-GEMM comparison path only
         self.b = None if b is None else b.float().to(dev).contiguous()
 
 
@@ -58,14 +54,8 @@ def _ws(device, nbytes):
     return _workspace[key]
 
 
-BIG_M = 192   # rows from which a call counts as "batched" (B >= 4 images): the kernel then takes groups of 4 row tiles per workgroup
-# AVC_VIT_LIBRARY_GEMM=1 (LIBRARY_GEMM above): batched calls go to the library GEMM (torch.mm -> hipBLASLt) instead of the
-# hand-written kernel -- the comparison point of the batched scoring path (ShapeGen codebook search, pose retrieval), not the default
-
-
-def _gelu_grad(pre):
-    s = torch.sigmoid(1.702 * pre)
-    return s + 1.702 * pre * s * (1 - s)
+BIG_M = 129   # rows from which a call counts as "batched" (3+ images): the linears then run in the LDS-staged GEMM (the C side decides
+# that by itself), BlocksFn has no backward and takes the grown-on-demand operands; up to 128 rows the latency kernel
 
 
 def _linear_raw(x2d, lin, transposed, bias, residual, act, want_pre, gelu_pre=None):
@@ -74,20 +64,6 @@ def _linear_raw(x2d, lin, transposed, bias, residual, act, want_pre, gelu_pre=No
     lib = L.load()
     M = x2d.shape[0]
     N, K = (lin.K, lin.N) if transposed else (lin.N, lin.K)
-    if LIBRARY_GEMM and M >= BIG_M:
-        if gelu_pre is not None:
-            x2d = x2d * _gelu_grad(gelu_pre)
-        w = lin.wd if transposed else lin.wd.t()
-        y = torch.mm(x2d.to(torch.bfloat16), w, out_dtype=torch.float32)
-        if bias is not None:
-            y += bias
-        pre = None
-        if act:
-            pre = y.clone() if want_pre else None
-            y = y * torch.sigmoid(1.702 * y)
-        if residual is not None:
-            y += residual
-        return y, pre
     wp = lin.wtp if transposed else lin.wp
     y = torch.empty(M, N, device=x2d.device, dtype=torch.float32)
     pre = torch.empty_like(y) if (act and want_pre) else None
@@ -150,13 +126,15 @@ class AttentionFn(torch.autograd.Function):
 
 
 class BlocksFn(torch.autograd.Function):
-    """The 12 residual blocks (clip/model.py ResidualAttentionBlock) of a per-iteration call (M = B * 50 <= 128 rows) as ONE autograd
-    node: activations go from kernel to kernel as packed bf16 operands, forward and backward -- LayerNorm writes the operand of the
-    linear behind it, attention that of the out-projection, c_fc + QuickGELU that of c_proj; in the backward the proj^T product leaves
-    already multiplied by QuickGELU' and packed, and the LayerNorm backward adds the residual branch's gradient and packs its result
-    for the transposed linear below.  7 + 8 launches per block instead of 11 + ~14 (a packing launch per linear, torch LayerNorm
-    kernels, AccumulateGrad adds).  Arithmetic as in LinearFn / AttentionFn / F.layer_norm: bf16 operands, fp32 accumulation, fp32
-    residual stream and LayerNorm statistics."""
+    """The 12 residual blocks (clip/model.py ResidualAttentionBlock) as ONE autograd node: activations go from kernel to kernel as
+    packed bf16 operands -- LayerNorm writes the operand of the linear behind it, attention that of the out-projection, c_fc +
+    QuickGELU that of c_proj -- instead of fp32 rows and a packing pass in front of every linear.  The forward serves any number of
+    rows: up to 128 (the per-iteration call, 1-2 images) on the latency kernel, more (scoring calls, no gradient: ShapeGen/main.py:
+    104-128, pose_generation.py:79-110) on the LDS-staged GEMM; avc_vit_linear_packed chooses.  The backward exists up to 128 rows: the
+    proj^T product leaves already multiplied by QuickGELU' and packed, and the LayerNorm backward adds the residual branch's gradient
+    and packs its result for the transposed linear below.  7 + 8 launches per block instead of 11 + ~14 (a packing launch per linear,
+    torch LayerNorm kernels, AccumulateGrad adds).  Arithmetic as in LinearFn / AttentionFn / F.layer_norm: bf16 operands, fp32
+    accumulation, fp32 residual stream and LayerNorm statistics."""
 
     @staticmethod
     def forward(ctx, x, model):
@@ -167,31 +145,38 @@ class BlocksFn(torch.autograd.Function):
         nb = len(model.blocks)
         dev = x0.device
         keep = ctx.needs_input_grad[0]
-        xs = torch.empty(nb, M, W, device=dev, dtype=torch.float32)            # block outputs (= the next block's input)
-        x2s = torch.empty(nb if keep else 1, M, W, device=dev, dtype=torch.float32)
+        if keep and M >= BIG_M:
+            raise RuntimeError("BlocksFn: the packed backward covers up to 128 rows (2 images); ClipVisionB32._blocks_per_kernel is the "
+                               "route of a gradient call with more")
+        # what the backward reads is kept per block; without one a block writes over the one before it and the residual stream is
+        # updated in place, in x0 (the caller's ln_pre output: nobody reads it again)
         qkvs = torch.empty(nb if keep else 1, M, 3 * W, device=dev, dtype=torch.float32)
+        x2s = torch.empty(nb if keep else 1, M, W, device=dev, dtype=torch.float32)
+        xs = torch.empty(nb, M, W, device=dev, dtype=torch.float32) if keep else x0.unsqueeze(0)   # block outputs (= the next block's input)
         pres = torch.empty(nb, M, 4 * W, device=dev, dtype=torch.float32) if keep else None
-        a_ln, a_at, a_fc = model._train_buf("ln", M, W), model._train_buf("attn", M, W), model._train_buf("fc", M, 4 * W)
+        # up to 128 rows the operands captured graphs point at, never re-allocated; beyond, one buffer per role grown on demand
+        buf = model._train_buf if M < BIG_M else model._packed_buf
+        a_ln, a_at, a_fc = buf("ln", M, W), buf("attn", M, W), buf("fc", M, 4 * W)
+
+        def linear(xs_, lin, res, y, y_pre, ys, N, K, act):
+            L.check(lib.avc_vit_linear_packed(L.ptr(xs_), L.ptr(lin.wp), L.ptr(lin.b), L.ptr(res), None, L.ptr(y), L.ptr(y_pre), L.ptr(ys),
+                                              M, N, K, act, st), "avc_vit_linear_packed")
         cur = x0
         for i, blk in enumerate(model.blocks):
             k = i if keep else 0
-            x2, qkv, out = x2s[k], qkvs[k], xs[i]
+            x2, qkv, out = x2s[k], qkvs[k], xs[k]
             L.check(lib.avc_vit_ln_pack(L.ptr(cur), L.ptr(blk["ln1"][0]), L.ptr(blk["ln1"][1]), 1e-5, M, W, L.ptr(a_ln), st), "avc_vit_ln_pack")
-            L.check(lib.avc_vit_linear_small(L.ptr(a_ln), L.ptr(blk["qkv"].wp), L.ptr(blk["qkv"].b), None, None, L.ptr(qkv), None, None,
-                                             M, 3 * W, W, 0, st), "avc_vit_linear_small")
+            linear(a_ln, blk["qkv"], None, qkv, None, None, 3 * W, W, 0)
             L.check(lib.avc_vit_attention_fwd_packed(L.ptr(qkv), L.ptr(a_at), B, TOKENS, W, HEADS, st), "avc_vit_attention_fwd_packed")
-            L.check(lib.avc_vit_linear_small(L.ptr(a_at), L.ptr(blk["out"].wp), L.ptr(blk["out"].b), L.ptr(cur), None, L.ptr(x2), None, None,
-                                             M, W, W, 0, st), "avc_vit_linear_small")
+            linear(a_at, blk["out"], cur, x2, None, None, W, W, 0)
             L.check(lib.avc_vit_ln_pack(L.ptr(x2), L.ptr(blk["ln2"][0]), L.ptr(blk["ln2"][1]), 1e-5, M, W, L.ptr(a_ln), st), "avc_vit_ln_pack")
-            L.check(lib.avc_vit_linear_small(L.ptr(a_ln), L.ptr(blk["fc"].wp), L.ptr(blk["fc"].b), None, None, None,
-                                             L.ptr(pres[i]) if keep else None, L.ptr(a_fc), M, 4 * W, W, 1, st), "avc_vit_linear_small")
-            L.check(lib.avc_vit_linear_small(L.ptr(a_fc), L.ptr(blk["proj"].wp), L.ptr(blk["proj"].b), L.ptr(x2), None, L.ptr(out), None, None,
-                                             M, W, 4 * W, 0, st), "avc_vit_linear_small")
+            linear(a_ln, blk["fc"], None, None, pres[i] if keep else None, a_fc, 4 * W, W, 1)
+            linear(a_fc, blk["proj"], x2, out, None, None, W, 4 * W, 0)      # (out may be cur: this launch does not read cur)
             cur = out
         if keep:
             ctx.model, ctx.B = model, B
             ctx.save_for_backward(x0, xs, x2s, qkvs, pres)
-        return xs[nb - 1].reshape(B, TOKENS, W)
+        return cur.reshape(B, TOKENS, W)
 
     @staticmethod
     def backward(ctx, g):
@@ -205,24 +190,24 @@ class BlocksFn(torch.autograd.Function):
         p_g2, p_dqkv = model._train_buf("g2", M, W), model._train_buf("dqkv", M, 3 * W)
         t768 = torch.empty(5, M, W, device=dev, dtype=torch.float32)
         dy2, da, dy1, bufa, bufb = t768[0], t768[1], t768[2], t768[3], t768[4]
+
+        def linear_t(xs_, lin, gelu_pre, y, ys, N, K, act):
+            L.check(lib.avc_vit_linear_packed(L.ptr(xs_), L.ptr(lin.wtp), None, None, L.ptr(gelu_pre), L.ptr(y), None, L.ptr(ys),
+                                              M, N, K, act, st), "avc_vit_linear_packed")
         L.check(lib.avc_vit_pack(L.ptr(g), None, L.ptr(p_g), M, W, st), "avc_vit_pack")
         for i in range(len(model.blocks) - 1, -1, -1):
             blk = model.blocks[i]
             xin = x0 if i == 0 else xs[i - 1]
             # c_proj^T, times QuickGELU'(pre), packed for c_fc^T
-            L.check(lib.avc_vit_linear_small(L.ptr(p_g), L.ptr(blk["proj"].wtp), None, None, L.ptr(pres[i]), None, None, L.ptr(p_dh),
-                                             M, 4 * W, W, 2, st), "avc_vit_linear_small")
-            L.check(lib.avc_vit_linear_small(L.ptr(p_dh), L.ptr(blk["fc"].wtp), None, None, None, L.ptr(dy2), None, None,
-                                             M, W, 4 * W, 0, st), "avc_vit_linear_small")
+            linear_t(p_g, blk["proj"], pres[i], None, p_dh, 4 * W, W, 2)
+            linear_t(p_dh, blk["fc"], None, dy2, None, W, 4 * W, 0)
             # ln_2 backward + the residual branch's gradient: fp32 (the next residual sum) and packed (out_proj^T)
             L.check(lib.avc_vit_ln_bwd(L.ptr(dy2), L.ptr(x2s[i]), L.ptr(blk["ln2"][0]), 1e-5, L.ptr(g), L.ptr(bufa), L.ptr(p_g2), M, W, st),
                     "avc_vit_ln_bwd")
-            L.check(lib.avc_vit_linear_small(L.ptr(p_g2), L.ptr(blk["out"].wtp), None, None, None, L.ptr(da), None, None,
-                                             M, W, W, 0, st), "avc_vit_linear_small")
+            linear_t(p_g2, blk["out"], None, da, None, W, W, 0)
             L.check(lib.avc_vit_attention_bwd_packed(L.ptr(qkvs[i]), L.ptr(da), L.ptr(p_dqkv), B, TOKENS, W, HEADS, st),
                     "avc_vit_attention_bwd_packed")
-            L.check(lib.avc_vit_linear_small(L.ptr(p_dqkv), L.ptr(blk["qkv"].wtp), None, None, None, L.ptr(dy1), None, None,
-                                             M, W, 3 * W, 0, st), "avc_vit_linear_small")
+            linear_t(p_dqkv, blk["qkv"], None, dy1, None, W, 3 * W, 0)
             # ln_1 backward + residual: the gradient of the block's input, packed for the block below
             L.check(lib.avc_vit_ln_bwd(L.ptr(dy1), L.ptr(xin), L.ptr(blk["ln1"][0]), 1e-5, L.ptr(bufa), L.ptr(bufb),
                                        L.ptr(p_g) if i else None, M, W, st), "avc_vit_ln_bwd")
@@ -275,7 +260,7 @@ class ClipVisionB32:
         return self
 
     def _packed_buf(self, tag, M, K):
-        """a packed bf16 activation buffer of the batched pipeline (one per role, grown on demand, stream-ordered reuse)"""
+        """a packed operand of BlocksFn above 128 rows (scoring calls): one per role, grown on demand, stream-ordered reuse"""
         need = L.load().avc_vit_workspace_bytes(M, K)
         buf = self._packed.get(tag)
         if buf is None or buf.numel() < need:
@@ -283,56 +268,21 @@ class ClipVisionB32:
         return buf
 
     def _train_buf(self, tag, M, K):
-        """a packed operand of the per-iteration pipeline (BlocksFn): one per (role, shape), never re-allocated -- captured graphs
-        point at it; zero-filled once (the attention kernel only writes the rows below M)"""
+        """a packed operand of BlocksFn up to 128 rows (the per-iteration call): one per (role, shape), never re-allocated -- captured
+        graphs point at it; zero-filled once (the attention kernel only writes the rows below M)"""
         key = ("train", tag, M, K)
         buf = self._packed.get(key)
         if buf is None:
             buf = self._packed[key] = torch.zeros(L.load().avc_vit_workspace_bytes(M, K), dtype=torch.uint8, device=self.device)
         return buf
 
-    @torch.no_grad()
-    def _encode_image_batched(self, image: torch.Tensor) -> torch.Tensor:
-        """encode_image for scoring calls (no gradient, 3+ images: ShapeGen/main.py:104-128, pose_generation.py:79-110): the same
-        arithmetic as the autograd path below (bf16 GEMM operands, fp32 accumulation, fp32 residual stream and LayerNorm
-        statistics), with the activations handed from kernel to kernel as packed bf16 operands -- LayerNorm writes the operand of
-        the linear behind it, attention that of the out-projection, c_fc + QuickGELU that of c_proj -- instead of fp32 rows and a
-        packing pass in front of every linear."""
-        lib, st = L.load(), L.stream()
-        B = image.shape[0]
-        x = image.float().reshape(B, 3, RES // PATCH, PATCH, RES // PATCH, PATCH).permute(0, 2, 4, 1, 3, 5)
-        x = x.reshape(B, (RES // PATCH) ** 2, 3 * PATCH * PATCH)
-        x = LinearFn.apply(x, self.conv, 0, None)
-        x = torch.cat([self.cls.expand(B, 1, WIDTH), x], dim=1) + self.pos
-        x = F.layer_norm(x, (WIDTH,), self.ln_pre[0], self.ln_pre[1], 1e-5).reshape(B * TOKENS, WIDTH).contiguous()
-        M = B * TOKENS
-        a768, b768, a3072 = self._packed_buf("ln", M, WIDTH), self._packed_buf("attn", M, WIDTH), self._packed_buf("fc", M, 4 * WIDTH)
-        qkv = torch.empty(M, 3 * WIDTH, device=x.device, dtype=torch.float32)
-        x2 = torch.empty_like(x)
-        for blk in self.blocks:
-            L.check(lib.avc_vit_ln_pack(L.ptr(x), L.ptr(blk["ln1"][0]), L.ptr(blk["ln1"][1]), 1e-5, M, WIDTH, L.ptr(a768), st), "avc_vit_ln_pack")
-            L.check(lib.avc_vit_linear_packed(L.ptr(a768), L.ptr(blk["qkv"].wp), L.ptr(blk["qkv"].b), None, L.ptr(qkv), None,
-                                              M, 3 * WIDTH, WIDTH, 0, st), "avc_vit_linear_packed")
-            L.check(lib.avc_vit_attention_fwd_packed(L.ptr(qkv), L.ptr(b768), B, TOKENS, WIDTH, HEADS, st), "avc_vit_attention_fwd_packed")
-            L.check(lib.avc_vit_linear_packed(L.ptr(b768), L.ptr(blk["out"].wp), L.ptr(blk["out"].b), L.ptr(x), L.ptr(x2), None,
-                                              M, WIDTH, WIDTH, 0, st), "avc_vit_linear_packed")
-            L.check(lib.avc_vit_ln_pack(L.ptr(x2), L.ptr(blk["ln2"][0]), L.ptr(blk["ln2"][1]), 1e-5, M, WIDTH, L.ptr(a768), st), "avc_vit_ln_pack")
-            L.check(lib.avc_vit_linear_packed(L.ptr(a768), L.ptr(blk["fc"].wp), L.ptr(blk["fc"].b), None, None, L.ptr(a3072),
-                                              M, 4 * WIDTH, WIDTH, 1, st), "avc_vit_linear_packed")
-            L.check(lib.avc_vit_linear_packed(L.ptr(a3072), L.ptr(blk["proj"].wp), L.ptr(blk["proj"].b), L.ptr(x2), L.ptr(x), None,
-                                              M, WIDTH, 4 * WIDTH, 0, st), "avc_vit_linear_packed")
-        x = F.layer_norm(x.reshape(B, TOKENS, WIDTH)[:, 0, :], (WIDTH,), self.ln_post[0], self.ln_post[1], 1e-5)
-        return LinearFn.apply(x, self.proj, 0, None)
-
     def encode_image(self, image: torch.Tensor) -> torch.Tensor:
-        """main.py:512,524.  Three routes with the same arithmetic: scoring calls (no gradient, 3+ images) -> the packed pipeline;
-        the per-iteration call (1-2 images WITH a gradient to the pixels) -> the encoder's ~250 forward and ~250 backward launches
-        replayed as two HIP graphs (torch.cuda.make_graphed_callables: captured once per batch size after three warm-up passes;
-        bit-identical results, 3.8 -> 0.34 ms of host time per forward + backward) -- what matters when the ray set is small and
-        the iteration is bound by the host's launch rate (the reference's default silhouette mode: 7 000 rays); everything else eager."""
+        """main.py:512,524.  The per-iteration call (1-2 images WITH a gradient to the pixels) -> the encoder's ~250 forward and ~250
+        backward launches replayed as two HIP graphs (torch.cuda.make_graphed_callables: captured once per batch size after three
+        warm-up passes; bit-identical results, 3.8 -> 0.34 ms of host time per forward + backward) -- what matters when the ray set
+        is small and the iteration is bound by the host's launch rate (the reference's default silhouette mode: 7 000 rays);
+        everything else eager, on the routes of _encode_image_eager."""
         B = image.shape[0]
-        if PACKED_PIPELINE and B * TOKENS > 128 and not LIBRARY_GEMM and not (torch.is_grad_enabled() and image.requires_grad):
-            return self._encode_image_batched(image)
         if (TRAIN_GRAPH and B <= 2 and image.is_cuda and torch.is_grad_enabled() and image.requires_grad
                 and tuple(image.shape[1:]) == (3, RES, RES) and not torch.cuda.is_current_stream_capturing()):
             g = self._graphed.get(B)
@@ -389,18 +339,14 @@ class ClipVisionB32:
         for B in self._graph_busy:
             self._graph_busy[B] = False
 
-    def _encode_image_eager(self, image: torch.Tensor) -> torch.Tensor:
-        B = image.shape[0]
-        # conv1 (32x32, stride 32, no bias) == GEMM over flattened patches in (c, ky, kx) order
-        x = image.float().reshape(B, 3, RES // PATCH, PATCH, RES // PATCH, PATCH).permute(0, 2, 4, 1, 3, 5)
-        x = x.reshape(B, (RES // PATCH) ** 2, 3 * PATCH * PATCH)
-        x = LinearFn.apply(x, self.conv, 0, None)
-        x = torch.cat([self.cls.expand(B, 1, WIDTH), x], dim=1) + self.pos
-        x = F.layer_norm(x, (WIDTH,), self.ln_pre[0], self.ln_pre[1], 1e-5)
-        if FUSED_BLOCKS and B * TOKENS <= 128 and not LIBRARY_GEMM:
-            x = BlocksFn.apply(x, self)
-            x = F.layer_norm(x[:, 0, :], (WIDTH,), self.ln_post[0], self.ln_post[1], 1e-5)
-            return LinearFn.apply(x, self.proj, 0, None)
+    def _blocks_packed(self, x):
+        """the residual blocks with packed bf16 hand-offs between the kernels (BlocksFn): every call without a gradient to the
+        pixels, and gradient calls of up to 128 rows (2 images)"""
+        return BlocksFn.apply(x, self)
+
+    def _blocks_per_kernel(self, x):
+        """the residual blocks as one autograd node per kernel (fp32 rows + a packing pass in front of every linear, torch LayerNorm):
+        gradient calls with 3+ images (AvatarAnimate's CLIP-guided optimisers), and what the tests hold BlocksFn against"""
         for blk in self.blocks:
             y = F.layer_norm(x, (WIDTH,), blk["ln1"][0], blk["ln1"][1], 1e-5)
             a = AttentionFn.apply(LinearFn.apply(y, blk["qkv"], 0, None))
@@ -408,6 +354,21 @@ class ClipVisionB32:
             y = F.layer_norm(x, (WIDTH,), blk["ln2"][0], blk["ln2"][1], 1e-5)
             y = LinearFn.apply(y, blk["fc"], 1, None)                    # QuickGELU fused
             x = LinearFn.apply(y, blk["proj"], 0, x)
+        return x
+
+    def _encode_image_eager(self, image: torch.Tensor, blocks=None) -> torch.Tensor:
+        """blocks: _blocks_packed or _blocks_per_kernel; None = the route this call is meant to take"""
+        B = image.shape[0]
+        # conv1 (32x32, stride 32, no bias) == GEMM over flattened patches in (c, ky, kx) order
+        x = image.float().reshape(B, 3, RES // PATCH, PATCH, RES // PATCH, PATCH).permute(0, 2, 4, 1, 3, 5)
+        x = x.reshape(B, (RES // PATCH) ** 2, 3 * PATCH * PATCH)
+        x = LinearFn.apply(x, self.conv, 0, None)
+        x = torch.cat([self.cls.expand(B, 1, WIDTH), x], dim=1) + self.pos
+        x = F.layer_norm(x, (WIDTH,), self.ln_pre[0], self.ln_pre[1], 1e-5)
+        if blocks is None:
+            grad = torch.is_grad_enabled() and x.requires_grad
+            blocks = self._blocks_per_kernel if grad and B * TOKENS >= BIG_M else self._blocks_packed
+        x = blocks(x)
         x = F.layer_norm(x[:, 0, :], (WIDTH,), self.ln_post[0], self.ln_post[1], 1e-5)
         return LinearFn.apply(x, self.proj, 0, None)
 

@@ -1,6 +1,6 @@
 // CLIP ViT-B/32 image-encoder kernels (perceptor.encode_image, main.py:512; OpenAI clip/model.py VisionTransformer).
 //   avc_vit_linear   Y[M,N] = act(X[M,K] W[N,K]^T + b) (+ residual)   -- bf16 MFMA 32x32x16, fp32 accumulate.
-//                    M = 50..100 tokens: the GEMM is weight-streaming / latency bound, so W is pre-packed in B-operand
+//                    More than 128 rows: the LDS-staged GEMM of avc_vit_gemm.hip.  M = 50..100 tokens: the GEMM is weight-streaming / latency bound, so W is pre-packed in B-operand
 //                    fragment order and X is packed into A-operand fragments by a pre-pass (one coalesced 16-B load per
 //                    lane per k-step for both), the K range is dealt to the 8 wavefronts of a workgroup and reduced
 //                    through LDS, one workgroup per 32 output columns.
@@ -9,7 +9,7 @@
 #include "avc_common.h"
 #include "../../include/avc.h"
 
-#define VIT_MAX_MT 4   // up to 128 rows (tokens): the per-iteration latency path (one row tile per workgroup); more rows: groups of 4
+#define VIT_MAX_MT 4   // up to 128 rows (tokens): the latency kernel (one row tile per workgroup); more rows: avc_vit_gemm.hip, groups of 4
 #define VIT_WAVES 8    // wavefronts per workgroup = K-split factor
 
 // X[M,K] fp32 -> bf16 A-operand fragments [m-tile][k-step][lane][8] (lane (i,h) holds X[32m+i][16s+8h+j]): the GEMM then
@@ -67,7 +67,7 @@ __global__ __launch_bounds__(64 * VIT_WAVES) void vit_linear_kernel(const b8* __
   // blockIdx.y = group of MT 32-row tiles of the rows.  Per-iteration calls (M <= 128 rows): MT = 1, one workgroup per (column tile,
   // row tile) -- it then reads a quarter of the packed activations (the K = 3072 linears re-read 768 KB of them per workgroup from
   // L2 otherwise: 35 us) and the four workgroups that share a weight tile sit on one XCD (block id = x + gridDim.x * y, gridDim.x a
-  // multiple of 8), i.e. share its L2.  Batched scoring (hundreds of images): MT = 4, a weight fragment feeds four MFMAs.
+  // multiple of 8), i.e. share its L2.  (MT = 4, a weight fragment feeding four MFMAs, was the batched kernel before avc_vit_gemm.hip.)
   const int mb = blockIdx.y;
   Xs += (long)mb * MT * KS * 64;
   const int row0 = 32 * MT * mb;
@@ -127,83 +127,10 @@ __global__ __launch_bounds__(64 * VIT_WAVES) void vit_linear_kernel(const b8* __
     } else {
       v = 0.f;
     }
-    // the per-iteration training pipeline (avc_vit_linear_small): the result leaves (also) as the packed bf16 operand of the linear
+    // the packed pipeline (avc_vit_linear_packed): the result leaves (also) as the packed bf16 operand of the linear
     // behind it -- element (row, col) is slot col & 7 of lane (row & 31, (col >> 3) & 1) of k-step col >> 4 of row tile row >> 5; the
     // rows of the last tile past M are written as zeros
     if (Ys) Ys[((((long)(row >> 5)) * (N >> 4) + (col >> 4)) * 64 + (row & 31) + 32 * ((col >> 3) & 1)) * 8 + (col & 7)] = (__bf16)v;
-  }
-}
-
-// Batched calls (hundreds of images: ShapeGen codebook search, pose retrieval -- row f-4): a plain tiled GEMM.  One 4-wavefront
-// workgroup per 128 x 128 output block, every wavefront a 64 x 64 quarter of it (2 x 2 MFMA tiles: each fragment it loads feeds two
-// MFMAs, 1 KiB of operands per MFMA; the two wavefronts that share a row / column pair meet in the CU's L1), the whole K range per
-// wavefront (no split-K, no LDS), fragments prefetched VIT_GEMM_AHEAD k-steps ahead.  Both operands arrive pre-packed in fragment
-// order, so every load is one coalesced 16 B per lane.
-constexpr int VIT_GEMM_AHEAD = 3;
-__global__ __launch_bounds__(256) void vit_gemm_kernel(const b8* __restrict__ Xs, const b8* __restrict__ Wp, const float* __restrict__ bias,
-                                                       const float* __restrict__ res, float* __restrict__ Y, float* __restrict__ Ypre,
-                                                       int M, int N, int K, int act) {
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int n = lane & 31, h = lane >> 5;
-  const int KS = K >> 4;
-  const int mt0 = 4 * blockIdx.y + 2 * (wv & 1), nt0 = 4 * blockIdx.x + 2 * (wv >> 1);
-  const b8* xa = Xs + (long)mt0 * KS * 64 + lane;
-  const b8* wb = Wp + (long)nt0 * KS * 64 + lane;
-  const long xstep = (long)KS * 64;     // next row / column tile
-  facc acc[2][2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-  b8 fx[VIT_GEMM_AHEAD][2], fw[VIT_GEMM_AHEAD][2];
-#pragma unroll
-  for (int d = 0; d < VIT_GEMM_AHEAD; ++d) {
-    if (d < KS) {
-      fx[d][0] = xa[(long)d * 64]; fx[d][1] = xa[xstep + (long)d * 64];
-      fw[d][0] = wb[(long)d * 64]; fw[d][1] = wb[xstep + (long)d * 64];
-    }
-  }
-  for (int s0 = 0; s0 < KS; s0 += VIT_GEMM_AHEAD) {
-#pragma unroll
-    for (int d = 0; d < VIT_GEMM_AHEAD; ++d) {
-      const int s = s0 + d;
-      if (s < KS) {
-        const b8 x0 = fx[d][0], x1 = fx[d][1], w0 = fw[d][0], w1 = fw[d][1];
-        const int sn = s + VIT_GEMM_AHEAD;
-        if (sn < KS) {
-          fx[d][0] = xa[(long)sn * 64]; fx[d][1] = xa[xstep + (long)sn * 64];
-          fw[d][0] = wb[(long)sn * 64]; fw[d][1] = wb[xstep + (long)sn * 64];
-        }
-        acc[0][0] = MF<b8>::mma(x0, w0, acc[0][0]);
-        acc[0][1] = MF<b8>::mma(x0, w1, acc[0][1]);
-        acc[1][0] = MF<b8>::mma(x1, w0, acc[1][0]);
-        acc[1][1] = MF<b8>::mma(x1, w1, acc[1][1]);
-      }
-    }
-  }
-#pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    const int col = 32 * (nt0 + j) + n;
-    const float bv = bias ? bias[col] : 0.f;
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int row = 32 * (mt0 + i) + (r & 3) + 8 * (r >> 2) + 4 * h;
-        if (row < M) {
-          float v = acc[i][j][r] + bv;
-          const long o = (long)row * N + col;
-          if (act == 1) {
-            if (Ypre) Ypre[o] = v;
-            v = v * sigmoidf_(1.702f * v);
-          }
-          if (res) v += res[o];
-          Y[o] = v;
-        }
-      }
-    }
   }
 }
 
@@ -217,59 +144,54 @@ extern "C" long avc_vit_workspace_bytes(int M, int K) {
   return mt * (K / 16) * 1024L;
 }
 
-// one row tile per workgroup (M <= 128): the batch of loads a wave keeps in flight covers its whole share of K up to K = 3072
-static void vit_launch_small(dim3 grid, int lds, hipStream_t s, const b8* xs, const b8* wp, const float* bias, const float* res, float* y,
-                             float* y_pre, int M, int N, int K, int act, __bf16* ys, const float* gpre) {
-  const int per_wave = ((K >> 4) + VIT_WAVES - 1) / VIT_WAVES;
-  const dim3 block(64 * VIT_WAVES);
-  if (per_wave <= 6) hipLaunchKernelGGL((vit_linear_kernel<1, 6>), grid, block, lds, s, xs, wp, bias, res, y, y_pre, M, N, K, act, ys, gpre);
-  else if (per_wave <= 12) hipLaunchKernelGGL((vit_linear_kernel<1, 12>), grid, block, lds, s, xs, wp, bias, res, y, y_pre, M, N, K, act, ys, gpre);
-  else if (per_wave <= 18) hipLaunchKernelGGL((vit_linear_kernel<1, 18>), grid, block, lds, s, xs, wp, bias, res, y, y_pre, M, N, K, act, ys, gpre);
-  else hipLaunchKernelGGL((vit_linear_kernel<1, 24>), grid, block, lds, s, xs, wp, bias, res, y, y_pre, M, N, K, act, ys, gpre);
-}
-
-static int vit_linear_impl(const float* x, const float* x_gelu_pre, const void* w_packed, const float* bias, const float* residual,
-                           float* y, float* y_pre, int M, int N, int K, int act, void* workspace, void* stream) {
+// The one dispatch of the file: y = f(xs W^T + b) (+ residual) from a packed operand (rows packed as avc_vit_workspace_bytes lays them
+// out).  Up to 128 rows the latency kernel, one row tile per workgroup, with all of its modes (the batch of loads a wave keeps in flight
+// covers its whole share of K up to K = 3072); more rows: the LDS-staged GEMM, or an error for what that does not cover.
+static int vit_linear_dispatch(const char* who, const void* xs, const void* wp, const float* bias, const float* res, const float* gpre,
+                               float* y, float* y_pre, void* ys, int M, int N, int K, int act, void* stream) {
   if (M <= 0) return 0;
-  if ((N & 31) || (K & 15)) {
-    avc_set_error("avc_vit_linear: need N % 32 == 0, K % 16 == 0");
+  if ((N & 31) || (K & 15)) { avc_set_error("avc_vit_linear: need N % 32 == 0, K % 16 == 0"); return 1; }
+  if ((act == 2) != (gpre != nullptr) || (!y && !ys)) { avc_set_error("avc_vit_linear: act 2 <=> gelu_pre; y or ys_packed"); return 1; }
+  if (M <= 32 * VIT_MAX_MT) {
+    const int per_wave = ((K >> 4) + VIT_WAVES - 1) / VIT_WAVES;
+    const dim3 grid(N / 32, (M + 31) / 32), block(64 * VIT_WAVES);
+    const int lds = VIT_WAVES * 4096;
+    hipStream_t s = (hipStream_t)stream;
+    const b8 *x8 = (const b8*)xs, *w8 = (const b8*)wp;
+    __bf16* y8 = (__bf16*)ys;
+    if (per_wave <= 6) hipLaunchKernelGGL((vit_linear_kernel<1, 6>), grid, block, lds, s, x8, w8, bias, res, y, y_pre, M, N, K, act, y8, gpre);
+    else if (per_wave <= 12) hipLaunchKernelGGL((vit_linear_kernel<1, 12>), grid, block, lds, s, x8, w8, bias, res, y, y_pre, M, N, K, act, y8, gpre);
+    else if (per_wave <= 18) hipLaunchKernelGGL((vit_linear_kernel<1, 18>), grid, block, lds, s, x8, w8, bias, res, y, y_pre, M, N, K, act, y8, gpre);
+    else hipLaunchKernelGGL((vit_linear_kernel<1, 24>), grid, block, lds, s, x8, w8, bias, res, y, y_pre, M, N, K, act, y8, gpre);
+  } else if (act == 2 || (y && ys) || !avc_vit_gemm_lds(xs, wp, bias, res, y, y_pre, ys, M, N, K, act, ((M + 127) / 128) * 4, stream)) {
+    avc_set_error("avc_vit_linear: more than 128 rows need N % 128 == 0, K % 32 == 0, act 0 or 1, no residual with an activation, and "
+                  "neither y, residual nor y_pre with a packed output");
     return 1;
   }
+  return avc_check_launch(who);
+}
+
+// fp32 rows in: the packing pre-pass into `workspace` (whole groups of 4 row tiles above 128 rows), then the dispatch above
+static int vit_linear_impl(const char* who, const float* x, const float* x_gelu_pre, const void* w_packed, const float* bias,
+                           const float* residual, float* y, float* y_pre, int M, int N, int K, int act, void* workspace, void* stream) {
+  if (M <= 0) return 0;
+  if ((N & 31) || (K & 15)) { avc_set_error("avc_vit_linear: need N % 32 == 0, K % 16 == 0"); return 1; }
   if (!workspace) { avc_set_error("avc_vit_linear: workspace == NULL (avc_vit_workspace_bytes)"); return 1; }
-  hipStream_t s = (hipStream_t)stream;
-  const int mt = (M + 31) / 32;
-  const bool batched = mt > VIT_MAX_MT;                 // more than 128 rows: groups of 4 row tiles per workgroup
-  const int mt_packed = batched ? ((mt + 3) / 4) * 4 : mt;
-  b8* xs = (b8*)workspace;
-  hipLaunchKernelGGL(vit_pack_x_kernel, dim3(K / 16, mt_packed), dim3(64), 0, s, x, x_gelu_pre, xs, M, K);
-  const dim3 grid(N / 32, batched ? mt_packed / 4 : mt), block(64 * VIT_WAVES);
-  const b8* wp = (const b8*)w_packed;
-  const int lds = VIT_WAVES * (batched ? 4 : 1) * 4096;
-  static unsigned long long attr_seen = 0;
-  if (avc_first_use_on_device(attr_seen)) {
-    (void)hipFuncSetAttribute((const void*)vit_linear_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, VIT_WAVES * 4 * 4096);
-  }
-  if (batched && avc_vit_gemm_lds(xs, wp, bias, residual, y, y_pre, nullptr, M, N, K, act, mt_packed, stream)) {
-  } else if (batched && (N & 127) == 0) {
-    hipLaunchKernelGGL(vit_gemm_kernel, dim3(N / 128, mt_packed / 4), dim3(256), 0, s, xs, wp, bias, residual, y, y_pre, M, N, K, act);
-  } else if (batched) {   // the split-K latency kernel with 4 row tiles per workgroup (13.5 k images/s at B = 512)
-    hipLaunchKernelGGL((vit_linear_kernel<4>), grid, block, lds, s, xs, wp, bias, residual, y, y_pre, M, N, K, act);
-  } else {
-    vit_launch_small(grid, lds, s, xs, wp, bias, residual, y, y_pre, M, N, K, act, nullptr, nullptr);
-  }
-  return avc_check_launch("avc_vit_linear");
+  const int mt = M <= 32 * VIT_MAX_MT ? (M + 31) / 32 : ((M + 127) / 128) * 4;
+  hipLaunchKernelGGL(vit_pack_x_kernel, dim3(K / 16, mt), dim3(64), 0, (hipStream_t)stream, x, x_gelu_pre, (b8*)workspace, M, K);
+  return vit_linear_dispatch(who, workspace, w_packed, bias, residual, nullptr, y, y_pre, nullptr, M, N, K, act, stream);
 }
 
 extern "C" int avc_vit_linear(const float* x, const void* w_packed, const float* bias, const float* residual, float* y,
                               float* y_pre, int M, int N, int K, int act, void* workspace, void* stream) {
-  return vit_linear_impl(x, nullptr, w_packed, bias, residual, y, y_pre, M, N, K, act, workspace, stream);
+  return vit_linear_impl("avc_vit_linear", x, nullptr, w_packed, bias, residual, y, y_pre, M, N, K, act, workspace, stream);
 }
 extern "C" int avc_vit_linear_bwd_gelu(const float* dy, const float* pre, const void* wt_packed, float* dx, int M, int N, int K,
                                        void* workspace, void* stream) {
-  return vit_linear_impl(dy, pre, wt_packed, nullptr, nullptr, dx, nullptr, M, N, K, 0, workspace, stream);
+  return vit_linear_impl("avc_vit_linear_bwd_gelu", dy, pre, wt_packed, nullptr, nullptr, dx, nullptr, M, N, K, 0, workspace, stream);
 }
 
-// ---- the batched no-grad pipeline (scoring): activations stay packed bf16 between the kernels ----
+// ---- the packed pipeline (clip_vit.BlocksFn): activations stay packed bf16 between the kernels ----
 // LayerNorm (fp32 statistics, eps inside the square root like torch) of x[M,K] straight into the packed operand of the next linear.
 // One workgroup per 32-row tile: a wavefront normalises 8 rows into an LDS image of the tile, then the fragments go out whole.
 #define LNP_LD (768 + 8)
@@ -378,17 +300,14 @@ extern "C" int avc_vit_ln_pack(const float* x, const float* gamma, const float* 
   hipLaunchKernelGGL(vit_ln_pack_kernel, dim3(mt), dim3(256), 0, (hipStream_t)stream, x, gamma, beta, eps, (b8*)xs_packed, M);
   return avc_check_launch("avc_vit_ln_pack");
 }
-// y = act(xs W^T + b) (+ residual) from an already packed operand (avc_vit_ln_pack, avc_vit_attention_fwd_packed or a previous
-// call's ys_packed); ys_packed != NULL: the result leaves as the packed operand of the next linear instead of fp32 rows
-extern "C" int avc_vit_linear_packed(const void* xs_packed, const void* w_packed, const float* bias, const float* residual, float* y,
-                                     void* ys_packed, int M, int N, int K, int act, void* stream) {
-  if (M <= 0) return 0;
-  const int mt_packed = ((M + 127) / 128) * 4;
-  if (!avc_vit_gemm_lds(xs_packed, w_packed, bias, residual, y, nullptr, ys_packed, M, N, K, act, mt_packed, stream)) {
-    avc_set_error("avc_vit_linear_packed: shape not covered (N % 128, K % 32, no residual / activation mix with a packed output)");
-    return 1;
-  }
-  return avc_check_launch("avc_vit_linear_packed");
+// y = f(xs W^T + b) (+ residual) from an already packed operand (avc_vit_ln_pack, avc_vit_pack, avc_vit_attention_*_packed, avc_vit_ln_bwd
+// or a previous call's ys_packed).  act 0: identity; 1: QuickGELU (y_pre, if given, receives the pre-activation); 2: times
+// QuickGELU'(gelu_pre[M,N]) (the backward of a QuickGELU layer folded into the product that yields the gradient of its output).  y (fp32
+// rows) and ys_packed (the operand of the next linear) are both optional; which combinations more than 128 rows allow: include/avc.h
+extern "C" int avc_vit_linear_packed(const void* xs_packed, const void* w_packed, const float* bias, const float* residual,
+                                     const float* gelu_pre, float* y, float* y_pre, void* ys_packed, int M, int N, int K, int act,
+                                     void* stream) {
+  return vit_linear_dispatch("avc_vit_linear_packed", xs_packed, w_packed, bias, residual, gelu_pre, y, y_pre, ys_packed, M, N, K, act, stream);
 }
 
 // ---- the per-iteration training pipeline (1-2 images WITH a gradient to the pixels, M <= 128 rows): the same packed hand-offs for
@@ -401,20 +320,6 @@ extern "C" int avc_vit_pack(const float* x, const float* gelu_pre, void* xs_pack
   const int mt = (M + 31) / 32;
   hipLaunchKernelGGL(vit_pack_x_kernel, dim3(K / 16, mt), dim3(64), 0, (hipStream_t)stream, x, gelu_pre, (b8*)xs_packed, M, K);
   return avc_check_launch("avc_vit_pack");
-}
-// y = f(xs W^T + b) (+ residual), M <= 128 rows, from a packed operand.  act 0: identity; 1: QuickGELU (y_pre, if given, receives
-// the pre-activation); 2: times QuickGELU'(gelu_pre[M,N]) (the backward of a QuickGELU layer folded into the product that yields the
-// gradient of its output).  y (fp32 rows) and ys_packed (the operand of the next linear) are both optional.
-extern "C" int avc_vit_linear_small(const void* xs_packed, const void* w_packed, const float* bias, const float* residual,
-                                    const float* gelu_pre, float* y, float* y_pre, void* ys_packed, int M, int N, int K, int act,
-                                    void* stream) {
-  if (M <= 0) return 0;
-  if (M > 32 * VIT_MAX_MT || (N & 31) || (K & 15)) { avc_set_error("avc_vit_linear_small: need M <= 128, N % 32 == 0, K % 16 == 0"); return 1; }
-  if ((act == 2) != (gelu_pre != nullptr) || (!y && !ys_packed)) { avc_set_error("avc_vit_linear_small: act 2 <=> gelu_pre; y or ys_packed"); return 1; }
-  const int mt = (M + 31) / 32;
-  vit_launch_small(dim3(N / 32, mt), VIT_WAVES * 4096, (hipStream_t)stream, (const b8*)xs_packed, (const b8*)w_packed, bias, residual, y, y_pre,
-                   M, N, K, act, (__bf16*)ys_packed, gelu_pre);
-  return avc_check_launch("avc_vit_linear_small");
 }
 // backward of LayerNorm over the last dimension (768) + the residual branch's gradient: dx = LN'(x; gamma)^T dy (+ res), written as
 // fp32 rows and (xs_packed != NULL) as the packed operand of the transposed linear that consumes it.  Statistics recomputed from x

@@ -8,7 +8,7 @@ import torch
 from . import build as _build
 
 _lib = None
-ABI_VERSION = 3          # AVC_ABI_VERSION of include/avc.h this binding was written against
+ABI_VERSION = 4          # AVC_ABI_VERSION of include/avc.h this binding was written against
 
 c_int, c_long, c_float, c_double, c_void_p = ctypes.c_int, ctypes.c_long, ctypes.c_float, ctypes.c_double, ctypes.c_void_p
 P = c_void_p
@@ -38,10 +38,9 @@ _SIGS = {
     "avc_vit_linear_bwd_gelu": (c_int, [P, P, P, P, c_int, c_int, c_int, P, P]),
     "avc_vit_workspace_bytes": (c_long, [c_int, c_int]),
     "avc_vit_ln_pack": (c_int, [P, P, P, c_float, c_int, c_int, P, P]),
-    "avc_vit_linear_packed": (c_int, [P, P, P, P, P, P, c_int, c_int, c_int, c_int, P]),
+    "avc_vit_linear_packed": (c_int, [P, P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, P]),
     "avc_vit_pack": (c_int, [P, P, P, c_int, c_int, P]),
     "avc_vit_attention_bwd_packed": (c_int, [P, P, P, c_int, c_int, c_int, c_int, P]),
-    "avc_vit_linear_small": (c_int, [P, P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, P]),
     "avc_vit_ln_bwd": (c_int, [P, P, P, c_float, P, P, P, c_int, c_int, P]),
     "avc_vit_attention_fwd_packed": (c_int, [P, P, c_int, c_int, c_int, c_int, P]),
     "avc_vit_attention_fwd": (c_int, [P, P, c_int, c_int, c_int, c_int, P]),

@@ -24,10 +24,11 @@ extern "C" {
 
 /* Interface revision of this header.  It changes whenever an existing entry point's argument list or meaning changes (2: round 5 put
  * `colsum` into avc_render_points_bwd and moved the second-order row-0 term out of the weight-gradient products; 3: the rasteriser's
- * batched forward with save and its backward, avc_rasterize_mesh_save / avc_rasterize_mesh_grad), so a caller built
+ * batched forward with save and its backward, avc_rasterize_mesh_save / avc_rasterize_mesh_grad; 4: avc_vit_linear_packed has the
+ * arguments gelu_pre and y_pre, serves any M and replaces the separate entry for up to 128 rows), so a caller built
  * against an older header can refuse the library instead of passing arguments in the wrong slots:
  *     if (avc_version() != AVC_ABI_VERSION) abort();       (avatarclip_amd/lib.py: load() does exactly this) */
-#define AVC_ABI_VERSION 3
+#define AVC_ABI_VERSION 4
 
 const char* avc_last_error(void);
 int avc_version(void);
@@ -232,9 +233,12 @@ int avc_mc_emit(const float* u, int nx, int ny, int nz, float iso, const int* vf
 /* ---- CLIP ViT-B/32 image encoder (perceptor.encode_image, main.py:512,518,524; OpenAI clip/model.py) ----
  * y[M,N] = act(x[M,K] W^T + bias) (+ residual); W pre-packed bf16 [N/32][K/16][64][8] (lane (n,h): W[32t+n][16s+8h+j]).
  * act 1 = QuickGELU (y_pre, if given, receives the pre-activation for the backward).  The backward dX = dY W is the same
- * call with the packed W^T (weights are frozen in AvatarCLIP: main.py:260).  Any M: up to 128 rows (the per-iteration calls) one
- * 8-wavefront split-K workgroup per (32 columns, 32 rows); beyond (batched scoring) an LDS-staged GEMM, one 4-wavefront workgroup
- * per 128 x 128 output block (N % 128 == 0, K % 32 == 0; csrc/avc_vit_gemm.hip). */
+ * call with the packed W^T (weights are frozen in AvatarCLIP: main.py:260).  N % 32 == 0, K % 16 == 0.  Up to 128 rows (the
+ * per-iteration calls, the text tower's 77) one 8-wavefront split-K workgroup per (32 columns, 32 rows), every combination of the
+ * arguments.  More than 128 rows (batched scoring) an LDS-staged GEMM, one 4-wavefront workgroup per 128 x 128 output block
+ * (csrc/avc_vit_gemm.hip), which covers N % 128 == 0, K % 32 == 0 and no residual together with an activation -- every linear of
+ * both CLIP towers, forward and transposed (N, K in {512, 768, 1536, 2048, 2304, 3072}); anything else returns 1 with the condition in
+ * avc_last_error(), there is no slower kernel behind it. */
 int avc_vit_linear(const float* x, const void* w_packed, const float* bias, const float* residual, float* y,
                    float* y_pre, int M, int N, int K, int act, void* workspace /* avc_vit_workspace_bytes(M, K) */,
                    void* stream);
@@ -244,32 +248,30 @@ int avc_vit_linear_bwd_gelu(const float* dy, const float* pre, const void* wt_pa
                             void* workspace, void* stream);
 /* bytes of the bf16 fragment copy of x that avc_vit_linear builds in `workspace` */
 long avc_vit_workspace_bytes(int M, int K);
-/* The batched scoring calls (no gradient; hundreds of images: ShapeGen/main.py:104-128, AvatarAnimate pose_generation.py:79-110) keep
- * the activations between the kernels as packed bf16 operands ([row tile][k-step][lane (row, half)][8], avc_vit_workspace_bytes(M, K)
- * bytes for an [M,K] activation) instead of fp32 rows + a packing pass per linear:
+/* The 12 residual blocks (clip_vit.BlocksFn: clip/model.py ResidualAttentionBlock as one autograd node; weights frozen, main.py:260)
+ * keep the activations between the kernels as packed bf16 operands ([row tile][k-step][lane (row, half)][8], avc_vit_workspace_bytes(M, K)
+ * bytes for an [M,K] activation) instead of fp32 rows + a packing pass per linear -- forward for any M (the batched scoring calls, no
+ * gradient, hundreds of images: ShapeGen/main.py:104-128, AvatarAnimate pose_generation.py:79-110), forward AND backward up to 128 rows
+ * (the per-iteration call of the training loop, main.py:512,524: 1-2 images WITH a gradient to the pixels):
  *   avc_vit_ln_pack               LayerNorm(x[M,768]; gamma, beta, eps) (clip/model.py LayerNorm, fp32 statistics) -> packed
- *   avc_vit_linear_packed         y = act(xs W^T + b) (+ residual) from a packed operand; with ys_packed != NULL the result leaves
- *                                 packed for the next linear (then y, residual must be NULL), else fp32 y[M,N]
  *   avc_vit_attention_fwd_packed  attention with its output packed for the out-projection (rows = b * 50 + token)
- * Shapes: more than 128 rows' worth is not required, but N % 128 == 0 and K % 32 == 0 are. */
+ *   avc_vit_pack                  fp32 rows (optionally times QuickGELU'(gelu_pre)) -> packed operand
+ *   avc_vit_linear_packed         y = f(xs W^T + b) (+ residual) from a packed operand; act 0 identity, 1 QuickGELU (y_pre, if given,
+ *                                 receives the pre-activation), 2 times QuickGELU'(gelu_pre[M,N]) (backward of a QuickGELU layer; act 2
+ *                                 if and only if gelu_pre != NULL); the result leaves as fp32 rows y and / or as the packed operand
+ *                                 ys_packed of the next linear (one of the two must be given).  Kernels and shapes as avc_vit_linear:
+ *                                 up to 128 rows every combination; more than 128 rows N % 128 == 0, K % 32 == 0, act 0 or 1, no
+ *                                 residual with an activation, and with ys_packed neither y, residual nor y_pre -- else it returns 1
+ *   avc_vit_ln_bwd                dx = (d LayerNorm(x; gamma) / dx)^T dy (+ residual_grad): fp32 rows and, xs_packed != NULL, the packed
+ *                                 operand of the transposed linear behind it (statistics recomputed from x, eps as in avc_vit_ln_pack;
+ *                                 rows past M of xs_packed are not touched: up to 128 rows the caller's buffer holds zeros there) */
 int avc_vit_ln_pack(const float* x, const float* gamma, const float* beta, float eps, int M, int K, void* xs_packed, void* stream);
-int avc_vit_linear_packed(const void* xs_packed, const void* w_packed, const float* bias, const float* residual, float* y,
-                          void* ys_packed, int M, int N, int K, int act, void* stream);
+int avc_vit_linear_packed(const void* xs_packed, const void* w_packed, const float* bias, const float* residual, const float* gelu_pre,
+                          float* y, float* y_pre, void* ys_packed, int M, int N, int K, int act, void* stream);
 int avc_vit_attention_fwd_packed(const float* qkv, void* out_packed, int B, int T, int width, int heads, void* stream);
-/* The per-iteration call of the training loop (main.py:512,524: 1-2 images WITH a gradient to the pixels, M <= 128 rows) hands its
- * activations over the same way, forward AND backward, on the split-K latency kernel (clip_vit.BlocksFn: the residual blocks of
- * clip/model.py ResidualAttentionBlock as one autograd node; weights frozen, main.py:260):
- *   avc_vit_pack          fp32 rows (optionally times QuickGELU'(gelu_pre)) -> packed operand
- *   avc_vit_linear_small  y = f(xs W^T + b) (+ residual) from a packed operand; act 0 identity, 1 QuickGELU (y_pre receives the
- *                         pre-activation), 2 times QuickGELU'(gelu_pre[M,N]) (backward of a QuickGELU layer); the result leaves as
- *                         fp32 rows y and / or as the packed operand ys_packed of the next linear
- *   avc_vit_ln_bwd        dx = (d LayerNorm(x; gamma) / dx)^T dy (+ residual_grad): fp32 rows and, xs_packed != NULL, the packed
- *                         operand of the transposed linear behind it (statistics recomputed from x, eps as in avc_vit_ln_pack) */
 int avc_vit_pack(const float* x, const float* gelu_pre, void* xs_packed, int M, int K, void* stream);
 /* avc_vit_attention_bwd with dqkv leaving as the packed operand ([B * 50, 3 W]) of the transposed in-projection */
 int avc_vit_attention_bwd_packed(const float* qkv, const float* dout, void* dqkv_packed, int B, int T, int width, int heads, void* stream);
-int avc_vit_linear_small(const void* xs_packed, const void* w_packed, const float* bias, const float* residual, const float* gelu_pre,
-                         float* y, float* y_pre, void* ys_packed, int M, int N, int K, int act, void* stream);
 int avc_vit_ln_bwd(const float* dy, const float* x, const float* gamma, float eps, const float* residual_grad, float* dx,
                    void* xs_packed, int M, int K, void* stream);
 /* multi-head self-attention of ResidualAttentionBlock over T=50 tokens, head dim 64: qkv[B,T,3W] -> out[B,T,W] */

@@ -69,9 +69,10 @@ def test_vit_linear_and_attention_kernels():
 
 @gpu
 @pytest.mark.parametrize("B", [3, 8, 37])
-def test_batched_scoring_pipeline_matches_the_autograd_path_and_the_oracle(B, monkeypatch):
-    """ClipVisionB32._encode_image_batched (no-grad calls with 3+ images: LayerNorm / attention / c_fc hand packed bf16 operands to the
-    linear behind them) against the per-iteration path (fp32 rows + a packing pass per linear): the same arithmetic with the same
+def test_batched_scoring_pipeline_matches_the_autograd_path_and_the_oracle(B):
+    """The packed route above 128 rows (ClipVisionB32._blocks_packed: no-grad calls with 3+ images, LayerNorm / attention / c_fc hand
+    packed bf16 operands to the linear behind them) against the per-kernel route (_blocks_per_kernel: fp32 rows + a packing pass per
+    linear): the same arithmetic with the same
     rounding points; what differs is the fp32 LayerNorm (own kernel vs torch), whose last-bit differences flip bf16 roundings that
     twelve layers then carry along: cosine >= 0.99999, |d| <= 5e-3 of the norm (measured 2.5e-3 .. 3.0e-3 -- about what either
     pipeline differs from the fp32 oracle by); and against the fp32 CPU oracle with the tolerance of test_encode_image_matches_oracle.  B = 37: 1850 rows = 14.5 row-tile groups (ragged
@@ -82,11 +83,11 @@ def test_batched_scoring_pipeline_matches_the_autograd_path_and_the_oracle(B, mo
     model = V.ClipVisionB32(sd, dev)
     img = torch.randn(B, 3, 224, 224, generator=torch.Generator().manual_seed(B))
     with torch.no_grad():
-        assert V.PACKED_PIPELINE
         e_packed = model.encode_image(img.to(dev)).cpu()
-        assert len(model._packed) == 3                      # the packed pipeline ran
-        monkeypatch.setattr(V, "PACKED_PIPELINE", False)
-        e_rows = model.encode_image(img.to(dev)).cpu()
+        assert set(model._packed) == {"ln", "attn", "fc"}      # the packed route ran, on the grown-on-demand operands of > 128 rows
+        assert torch.equal(e_packed, model._encode_image_eager(img.to(dev), model._blocks_packed).cpu())
+        e_rows = model._encode_image_eager(img.to(dev), model._blocks_per_kernel).cpu()
+        assert set(model._packed) == {"ln", "attn", "fc"}      # ... and the per-kernel route is another one: no packed operand of its own
         ref = C.encode_image(sd, img[: min(B, 4)])
     cos = torch.cosine_similarity(e_packed, e_rows, dim=-1)
     rel = ((e_packed - e_rows).norm(dim=-1) / e_rows.norm(dim=-1)).max().item()
@@ -121,7 +122,7 @@ def test_training_call_replayed_as_hip_graphs_is_bit_identical_to_eager_launches
 
 @gpu
 @pytest.mark.parametrize("B", [1, 2])
-def test_fused_residual_blocks_equal_the_per_kernel_autograd_path(B, monkeypatch):
+def test_fused_residual_blocks_equal_the_per_kernel_autograd_path(B):
     """BlocksFn (the 12 residual blocks of a per-iteration call as one autograd node with packed bf16 hand-offs, forward and
     backward) against the same arithmetic as one autograd node per kernel (LinearFn / AttentionFn / F.layer_norm): the only
     difference is the LayerNorm statistics' summation order (last-bit fp32 -> an occasional bf16 rounding flip, carried through 12
@@ -134,14 +135,15 @@ def test_fused_residual_blocks_equal_the_per_kernel_autograd_path(B, monkeypatch
     text = torch.randn(1, 512, generator=torch.Generator().manual_seed(5)).to(dev)
     img = torch.randn(B, 3, 224, 224, generator=torch.Generator().manual_seed(31)).to(dev)
     res = []
-    for fused in (True, False):
-        monkeypatch.setattr(V, "FUSED_BLOCKS", fused)
+    for blocks in (model._blocks_packed, model._blocks_per_kernel):
         x = img.clone().requires_grad_(True)
-        e = model._encode_image_eager(x)
+        e = model._encode_image_eager(x, blocks)
         (1 - torch.cosine_similarity(e.mean(0), text.mean(0), dim=0)).backward()
         with torch.no_grad():
-            e0 = model._encode_image_eager(img)
+            e0 = model._encode_image_eager(img, blocks)
         res.append((e.detach().clone(), x.grad.clone(), e0))
+    x = img.clone().requires_grad_(True)                # the route a call of this size takes when nobody names one: the packed one
+    assert torch.equal(model._encode_image_eager(x).detach(), res[0][0])
     rel = lambda a, b: ((a - b).norm() / b.norm()).item()
     ee, eg, e0 = rel(res[0][0], res[1][0]), rel(res[0][1], res[1][1]), rel(res[0][2], res[1][2])
     print("fused blocks vs per-kernel autograd: embedding", ee, "pixel gradient", eg, "no-grad embedding", e0)
@@ -159,7 +161,9 @@ def test_fused_residual_blocks_equal_the_per_kernel_autograd_path(B, monkeypatch
 @gpu
 def test_layernorm_backward_and_packed_epilogues_of_the_training_pipeline():
     """avc_vit_ln_bwd against torch autograd of F.layer_norm (+ residual gradient), its packed output and the packed / QuickGELU'
-    epilogues of avc_vit_linear_small against avc_vit_pack of the fp32 result (bit-exact: the same values rounded once)."""
+    epilogues of avc_vit_linear_packed against avc_vit_pack of the fp32 result (bit-exact: the same values rounded once), on both sides
+    of its 128-row dispatch: 128 rows = the last row count of the latency kernel, 129 = the first of the GEMM (5 row tiles: a ragged
+    group of four), 160 = two whole tiles in a partial group.  Each side of a torch.equal runs the same kernel at that M."""
     from avatarclip_amd import clip_vit as V, lib as L
     lib, dev = L.load(), torch.device("cuda")
     g = torch.Generator().manual_seed(3)
@@ -188,21 +192,56 @@ def test_layernorm_backward_and_packed_epilogues_of_the_training_pipeline():
         y, pre = torch.empty(M, 3072, device=dev), torch.empty(M, 3072, device=dev)
         nb2 = lib.avc_vit_workspace_bytes(M, 3072)
         py, py_ref = torch.zeros(nb2, dtype=torch.uint8, device=dev), torch.zeros(nb2, dtype=torch.uint8, device=dev)
-        L.check(lib.avc_vit_linear_small(L.ptr(ps), L.ptr(lin.wp), L.ptr(b), None, None, L.ptr(y), L.ptr(pre), L.ptr(py), M, 3072, 768, 1,
-                                         L.stream()), "linear_small")
+        L.check(lib.avc_vit_linear_packed(L.ptr(ps), L.ptr(lin.wp), L.ptr(b), None, None, L.ptr(y), L.ptr(pre), L.ptr(py), M, 3072, 768, 1,
+                                          L.stream()), "linear_packed")
         y_ref = V.LinearFn.apply(x, lin, 1, None)
         assert torch.equal(y, y_ref)
         L.check(lib.avc_vit_pack(L.ptr(y), None, L.ptr(py_ref), M, 3072, L.stream()), "pack")
         used2 = ((M + 31) // 32) * 192 * 1024
         assert torch.equal(py[:used2], py_ref[:used2])
         # act 2: (x W^T) * QuickGELU'(pre), packed only
-        L.check(lib.avc_vit_linear_small(L.ptr(ps), L.ptr(lin.wp), None, None, L.ptr(pre), None, None, L.ptr(py), M, 3072, 768, 2,
-                                         L.stream()), "linear_small")
-        L.check(lib.avc_vit_linear_small(L.ptr(ps), L.ptr(lin.wp), None, None, None, L.ptr(y), None, None, M, 3072, 768, 0, L.stream()),
-                "linear_small")
+        L.check(lib.avc_vit_linear_packed(L.ptr(ps), L.ptr(lin.wp), None, None, L.ptr(pre), None, None, L.ptr(py), M, 3072, 768, 2,
+                                          L.stream()), "linear_packed")
+        L.check(lib.avc_vit_linear_packed(L.ptr(ps), L.ptr(lin.wp), None, None, None, L.ptr(y), None, None, M, 3072, 768, 0, L.stream()),
+                "linear_packed")
         L.check(lib.avc_vit_pack(L.ptr(y), L.ptr(pre), L.ptr(py_ref), M, 3072, L.stream()), "pack")
         assert torch.equal(py[:used2], py_ref[:used2])
-    assert lib.avc_vit_linear_small(L.ptr(ps), L.ptr(lin.wp), None, None, None, None, None, None, 100, 3072, 768, 0, L.stream()) != 0
+    assert lib.avc_vit_linear_packed(L.ptr(ps), L.ptr(lin.wp), None, None, None, None, None, None, 100, 3072, 768, 0, L.stream()) != 0
+    # the 128-row dispatch of the merged entry, N = K = 768: fp32 rows == LinearFn on the fp32 operand (identity, QuickGELU, residual),
+    # and the packed output == avc_vit_pack of those rows.  Up to 128 rows whole tiles are compared (the latency kernel writes the
+    # rows past M as zeros); the GEMM leaves f(bias) in the rows past M, which no valid row ever reads, so there the M valid rows are
+    # compared, every element of them.
+    def rows(packed, M, N):          # [row tile][k-step][half][row][8] -> [M, N]
+        mt = (M + 31) // 32
+        t = packed[:mt * (N // 16) * 1024].view(torch.bfloat16).reshape(mt, N // 16, 2, 32, 8)
+        return t.permute(0, 3, 1, 2, 4).reshape(mt * 32, N)[:M]
+    w = torch.randn(768, 768, generator=g) * 768 ** -0.5
+    b = (torch.randn(768, generator=g) * 0.1).to(dev)
+    lin = V._Lin(w, b.cpu(), dev)
+    for M in (128, 129, 160):
+        x = torch.randn(M, 768, generator=g).to(dev)
+        res = torch.randn(M, 768, generator=g).to(dev)
+        nb = lib.avc_vit_workspace_bytes(M, 768)
+        ps, py, py_ref = (torch.zeros(nb, dtype=torch.uint8, device=dev) for _ in range(3))
+        L.check(lib.avc_vit_pack(L.ptr(x), None, L.ptr(ps), M, 768, L.stream()), "pack")
+        for act, r in ((0, None), (1, None), (0, res)):
+            y = torch.empty(M, 768, device=dev)
+            L.check(lib.avc_vit_linear_packed(L.ptr(ps), L.ptr(lin.wp), L.ptr(b), L.ptr(r), None, L.ptr(y), None, None, M, 768, 768, act,
+                                              L.stream()), "linear_packed")
+            assert torch.equal(y, V.LinearFn.apply(x, lin, act, r)), (M, act)
+            if r is None:
+                L.check(lib.avc_vit_linear_packed(L.ptr(ps), L.ptr(lin.wp), L.ptr(b), None, None, None, None, L.ptr(py), M, 768, 768, act,
+                                                  L.stream()), "linear_packed")
+                py_ref.zero_()
+                L.check(lib.avc_vit_pack(L.ptr(y), None, L.ptr(py_ref), M, 768, L.stream()), "pack")
+                assert torch.equal(rows(py, M, 768).view(torch.int16), rows(py_ref, M, 768).view(torch.int16)), (M, act)
+                assert torch.equal(rows(py_ref, M, 768).float(), y.bfloat16().float())     # (the helper reads the layout right)
+                if M <= 128:
+                    used = ((M + 31) // 32) * 48 * 1024
+                    assert torch.equal(py[:used], py_ref[:used]), (M, act)
+    # host-side refusals above 128 rows (no launch): QuickGELU with a residual; a column count the GEMM does not cover
+    assert lib.avc_vit_linear_packed(L.ptr(ps), L.ptr(lin.wp), L.ptr(b), L.ptr(res), None, L.ptr(y), None, None, 129, 768, 768, 1, L.stream()) != 0
+    assert lib.avc_vit_linear_packed(L.ptr(ps), L.ptr(lin.wp), L.ptr(b), None, None, L.ptr(y), None, None, 129, 96, 768, 0, L.stream()) != 0
     # attention backward with its result packed for the transposed in-projection == packing of its fp32 result
     for B in (1, 2):
         M = 50 * B
@@ -456,7 +495,7 @@ def test_real_openai_weights_when_supplied(tmp_path):
 @gpu
 def test_batched_scoring_path_matches_the_per_pair_path():
     """row f-4 (ShapeGen codebook search / pose retrieval: hundreds of renders per encode_image call): above 128 token rows the
-    linears run in the tiled GEMM kernel (vit_gemm_kernel); the embeddings must agree with the M <= 128 latency-kernel path image by
+    linears run in the LDS-staged GEMM (csrc/avc_vit_gemm.hip); the embeddings must agree with the M <= 128 latency-kernel path image by
     image, and with the oracle"""
     from avatarclip_amd import clip_vit as V
     sd = C.random_state_dict(0)

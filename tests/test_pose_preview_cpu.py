@@ -121,4 +121,4 @@ def test_lib_lists_the_two_entry_points_with_the_headers_argument_counts():
         assert res is lib.c_int and len(args) == len(m.group(1).split(",")), name
         assert args[-1] is lib.P                                        # the stream
     assert "avc_smpl.hip" in build.SOURCES and os.path.exists(os.path.join(build.CSRC, "avc_smpl.hip"))
-    assert lib.ABI_VERSION == 3 and re.search(r"#define\s+AVC_ABI_VERSION\s+3\b", hdr)
+    assert lib.ABI_VERSION == 4 and re.search(r"#define\s+AVC_ABI_VERSION\s+4\b", hdr)
