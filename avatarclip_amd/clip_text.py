@@ -47,7 +47,6 @@ class ClipTextB32:
     def encode_text(self, tokens: torch.Tensor) -> torch.Tensor:
         tokens = tokens.to(self.device).long()
         B, T = tokens.shape
-        lib = L.load()
         outs = []
         for b in range(B):      # one sequence (77 rows) per pass: the linear kernel takes up to 128 rows
             x = (self.tok[tokens[b]] + self.pos[:T]).contiguous()
@@ -55,7 +54,7 @@ class ClipTextB32:
                 y = F.layer_norm(x, (WIDTH,), blk["ln1"][0], blk["ln1"][1], 1e-5)
                 qkv = self._lin(y, blk["qkv"]).contiguous()
                 a = torch.empty(T, WIDTH, device=self.device, dtype=torch.float32)
-                L.check(lib.avc_text_attention_fwd(L.ptr(qkv), L.ptr(a), 1, T, WIDTH, HEADS, 1, L.stream()), "avc_text_attention_fwd")
+                L.call("avc_text_attention_fwd", qkv, a, 1, T, WIDTH, HEADS, 1)
                 x = self._lin(a, blk["out"], 0, x)
                 y = F.layer_norm(x, (WIDTH,), blk["ln2"][0], blk["ln2"][1], 1e-5)
                 y = self._lin(y, blk["fc"], 1)

@@ -69,11 +69,9 @@ def _linear_raw(x2d, lin, transposed, bias, residual, act, want_pre, gelu_pre=No
     pre = torch.empty_like(y) if (act and want_pre) else None
     ws = _ws(x2d.device, lib.avc_vit_workspace_bytes(M, K))
     if gelu_pre is not None:
-        L.check(lib.avc_vit_linear_bwd_gelu(L.ptr(x2d), L.ptr(gelu_pre), L.ptr(wp), L.ptr(y), M, N, K, L.ptr(ws), L.stream()),
-                "avc_vit_linear_bwd_gelu")
+        L.call("avc_vit_linear_bwd_gelu", x2d, gelu_pre, wp, y, M, N, K, ws)
     else:
-        L.check(lib.avc_vit_linear(L.ptr(x2d), L.ptr(wp), L.ptr(bias), L.ptr(residual), L.ptr(y), L.ptr(pre), M, N, K, act, L.ptr(ws),
-                                   L.stream()), "avc_vit_linear")
+        L.call("avc_vit_linear", x2d, wp, bias, residual, y, pre, M, N, K, act, ws)
     return y, pre
 
 
@@ -105,23 +103,20 @@ class LinearFn(torch.autograd.Function):
 class AttentionFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, qkv):
-        lib = L.load()
         B, T, _ = qkv.shape
         qkv = qkv.contiguous().float()
         out = torch.empty(B, T, WIDTH, device=qkv.device, dtype=torch.float32)
-        L.check(lib.avc_vit_attention_fwd(L.ptr(qkv), L.ptr(out), B, T, WIDTH, HEADS, L.stream()), "avc_vit_attention_fwd")
+        L.call("avc_vit_attention_fwd", qkv, out, B, T, WIDTH, HEADS)
         ctx.save_for_backward(qkv)
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        lib = L.load()
         (qkv,) = ctx.saved_tensors
         B, T, _ = qkv.shape
         dout = dout.contiguous().float()
         dqkv = torch.empty_like(qkv)
-        L.check(lib.avc_vit_attention_bwd(L.ptr(qkv), L.ptr(dout), L.ptr(dqkv), B, T, WIDTH, HEADS, L.stream()),
-                "avc_vit_attention_bwd")
+        L.call("avc_vit_attention_bwd", qkv, dout, dqkv, B, T, WIDTH, HEADS)
         return dqkv
 
 
@@ -138,7 +133,7 @@ class BlocksFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, model):
-        lib, st = L.load(), L.stream()
+        st = L.stream()
         B = x.shape[0]
         M, W = B * TOKENS, WIDTH
         x0 = x.reshape(M, W).contiguous().float()
@@ -159,17 +154,16 @@ class BlocksFn(torch.autograd.Function):
         a_ln, a_at, a_fc = buf("ln", M, W), buf("attn", M, W), buf("fc", M, 4 * W)
 
         def linear(xs_, lin, res, y, y_pre, ys, N, K, act):
-            L.check(lib.avc_vit_linear_packed(L.ptr(xs_), L.ptr(lin.wp), L.ptr(lin.b), L.ptr(res), None, L.ptr(y), L.ptr(y_pre), L.ptr(ys),
-                                              M, N, K, act, st), "avc_vit_linear_packed")
+            L.call("avc_vit_linear_packed", xs_, lin.wp, lin.b, res, None, y, y_pre, ys, M, N, K, act, stream=st)
         cur = x0
         for i, blk in enumerate(model.blocks):
             k = i if keep else 0
             x2, qkv, out = x2s[k], qkvs[k], xs[k]
-            L.check(lib.avc_vit_ln_pack(L.ptr(cur), L.ptr(blk["ln1"][0]), L.ptr(blk["ln1"][1]), 1e-5, M, W, L.ptr(a_ln), st), "avc_vit_ln_pack")
+            L.call("avc_vit_ln_pack", cur, blk["ln1"][0], blk["ln1"][1], 1e-5, M, W, a_ln, stream=st)
             linear(a_ln, blk["qkv"], None, qkv, None, None, 3 * W, W, 0)
-            L.check(lib.avc_vit_attention_fwd_packed(L.ptr(qkv), L.ptr(a_at), B, TOKENS, W, HEADS, st), "avc_vit_attention_fwd_packed")
+            L.call("avc_vit_attention_fwd_packed", qkv, a_at, B, TOKENS, W, HEADS, stream=st)
             linear(a_at, blk["out"], cur, x2, None, None, W, W, 0)
-            L.check(lib.avc_vit_ln_pack(L.ptr(x2), L.ptr(blk["ln2"][0]), L.ptr(blk["ln2"][1]), 1e-5, M, W, L.ptr(a_ln), st), "avc_vit_ln_pack")
+            L.call("avc_vit_ln_pack", x2, blk["ln2"][0], blk["ln2"][1], 1e-5, M, W, a_ln, stream=st)
             linear(a_ln, blk["fc"], None, None, pres[i] if keep else None, a_fc, 4 * W, W, 1)
             linear(a_fc, blk["proj"], x2, out, None, None, W, 4 * W, 0)      # (out may be cur: this launch does not read cur)
             cur = out
@@ -180,7 +174,7 @@ class BlocksFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        lib, st = L.load(), L.stream()
+        st = L.stream()
         model, B = ctx.model, ctx.B
         x0, xs, x2s, qkvs, pres = ctx.saved_tensors
         M, W = B * TOKENS, WIDTH
@@ -192,9 +186,8 @@ class BlocksFn(torch.autograd.Function):
         dy2, da, dy1, bufa, bufb = t768[0], t768[1], t768[2], t768[3], t768[4]
 
         def linear_t(xs_, lin, gelu_pre, y, ys, N, K, act):
-            L.check(lib.avc_vit_linear_packed(L.ptr(xs_), L.ptr(lin.wtp), None, None, L.ptr(gelu_pre), L.ptr(y), None, L.ptr(ys),
-                                              M, N, K, act, st), "avc_vit_linear_packed")
-        L.check(lib.avc_vit_pack(L.ptr(g), None, L.ptr(p_g), M, W, st), "avc_vit_pack")
+            L.call("avc_vit_linear_packed", xs_, lin.wtp, None, None, gelu_pre, y, None, ys, M, N, K, act, stream=st)
+        L.call("avc_vit_pack", g, None, p_g, M, W, stream=st)
         for i in range(len(model.blocks) - 1, -1, -1):
             blk = model.blocks[i]
             xin = x0 if i == 0 else xs[i - 1]
@@ -202,15 +195,12 @@ class BlocksFn(torch.autograd.Function):
             linear_t(p_g, blk["proj"], pres[i], None, p_dh, 4 * W, W, 2)
             linear_t(p_dh, blk["fc"], None, dy2, None, W, 4 * W, 0)
             # ln_2 backward + the residual branch's gradient: fp32 (the next residual sum) and packed (out_proj^T)
-            L.check(lib.avc_vit_ln_bwd(L.ptr(dy2), L.ptr(x2s[i]), L.ptr(blk["ln2"][0]), 1e-5, L.ptr(g), L.ptr(bufa), L.ptr(p_g2), M, W, st),
-                    "avc_vit_ln_bwd")
+            L.call("avc_vit_ln_bwd", dy2, x2s[i], blk["ln2"][0], 1e-5, g, bufa, p_g2, M, W, stream=st)
             linear_t(p_g2, blk["out"], None, da, None, W, W, 0)
-            L.check(lib.avc_vit_attention_bwd_packed(L.ptr(qkvs[i]), L.ptr(da), L.ptr(p_dqkv), B, TOKENS, W, HEADS, st),
-                    "avc_vit_attention_bwd_packed")
+            L.call("avc_vit_attention_bwd_packed", qkvs[i], da, p_dqkv, B, TOKENS, W, HEADS, stream=st)
             linear_t(p_dqkv, blk["qkv"], None, dy1, None, W, 3 * W, 0)
             # ln_1 backward + residual: the gradient of the block's input, packed for the block below
-            L.check(lib.avc_vit_ln_bwd(L.ptr(dy1), L.ptr(xin), L.ptr(blk["ln1"][0]), 1e-5, L.ptr(bufa), L.ptr(bufb),
-                                       L.ptr(p_g) if i else None, M, W, st), "avc_vit_ln_bwd")
+            L.call("avc_vit_ln_bwd", dy1, xin, blk["ln1"][0], 1e-5, bufa, bufb, p_g if i else None, M, W, stream=st)
             g = bufb       # (bufa / bufb are re-used by the block below: each is dead by the time it is written again)
         return g.reshape(B, TOKENS, W), None
 

@@ -186,8 +186,8 @@ class SMPL_Dataset:
             Hp, Wp = prior.shape[0], prior.shape[1]
             true_rgb, mask = torch.empty(Hn * Wn, 3, **f32), torch.empty(Hn * Wn, 1, **f32)
         pose = torch.as_tensor(pose).to(dev).float().contiguous()
-        L.check(L.load().avc_gen_rays(L.ptr(pose), L.ptr(sel_idx), L.ptr(prior), Hp, Wp, float(self.W), float(self.H), float(self.focal), Wn, Hn, R,
-                                      L.ptr(rays_o), L.ptr(rays_d), L.ptr(near), L.ptr(far), L.ptr(true_rgb), L.ptr(mask), L.stream()), "avc_gen_rays")
+        L.call("avc_gen_rays", pose, sel_idx, prior, Hp, Wp, float(self.W), float(self.H), float(self.focal), Wn, Hn, R, rays_o, rays_d, near, far,
+               true_rgb, mask)
         return rays_o, rays_d, near, far, true_rgb, mask
 
     def near_far_from_sphere(self, rays_o, rays_d, is_sphere=False):

@@ -54,7 +54,7 @@ def mesh_components(triangles, num_vertices, device=None):
     if nf and (int(t.min()) < 0 or int(t.max()) >= nv):
         raise ValueError("a triangle names a vertex outside [0, %d)" % nv)
     label = torch.empty(nv, device=device, dtype=torch.int32)
-    L.check(L.load().avc_mesh_components(L.ptr(t) if nf else None, nf, nv, L.ptr(label), L.stream()), "avc_mesh_components")
+    L.call("avc_mesh_components", t if nf else None, nf, nv, label)
     return label
 
 
@@ -81,15 +81,13 @@ def cleanup_mesh(vertices, triangles, colors=None):
         c = c.contiguous()
     if nv == 0:
         return v, t, c
-    lib = L.load()
     label = mesh_components(t, nv, device)
     count = torch.empty(nv, device=device, dtype=torch.int32)
     best = torch.empty(1, device=device, dtype=torch.int64)
     vflag = torch.empty(nv, device=device, dtype=torch.int32)
     tflag = torch.empty(max(nf, 1), device=device, dtype=torch.int32)
-    tp = L.ptr(t) if nf else None
-    L.check(lib.avc_mesh_largest_island(tp, nf, nv, L.ptr(label), L.ptr(count), L.ptr(best), L.ptr(vflag), L.ptr(tflag), L.stream()),
-            "avc_mesh_largest_island")
+    tp = t if nf else None
+    L.call("avc_mesh_largest_island", tp, nf, nv, label, count, best, vflag, tflag)
     vinc = torch.cumsum(vflag, 0, dtype=torch.int32)
     tinc = torch.cumsum(tflag[:nf], 0, dtype=torch.int32)
     n_v, n_t = int(vinc[-1].item()), (int(tinc[-1].item()) if nf else 0)
@@ -97,9 +95,9 @@ def cleanup_mesh(vertices, triangles, colors=None):
     v_out = torch.empty(n_v, 3, device=device, dtype=torch.float32)
     t_out = torch.empty(max(n_t, 1), 3, device=device, dtype=torch.int32)
     c_out = torch.empty(n_v, 4, device=device, dtype=torch.uint8) if c is not None else None
-    L.check(lib.avc_mesh_compact(L.ptr(v), L.ptr(c), tp, nf, nv, L.ptr(vflag), L.ptr(vid), L.ptr(tflag) if nf else None,
-                                 L.ptr(tid) if nf else None, L.ptr(v_out), L.ptr(c_out), L.ptr(t_out) if nf else None, L.stream()),
-            "avc_mesh_compact")
+    as_words = lambda x: None if x is None else x.view(torch.int32)          # the kernel moves a colour as one 32-bit RGBA word
+    L.call("avc_mesh_compact", v, as_words(c), tp, nf, nv, vflag, vid, tflag if nf else None, tid if nf else None, v_out, as_words(c_out),
+           t_out if nf else None)
     return v_out, t_out[:n_t], c_out
 
 
@@ -172,7 +170,7 @@ def find_nearest_ind(new_vertices, template_vertices):
         raise ValueError("find_nearest_ind: empty template")
     idx = torch.empty(M, device=q.device, dtype=torch.int32)
     if M:
-        L.check(L.load().avc_nearest_point(L.ptr(q), M, L.ptr(r), K, L.ptr(idx), L.stream()), "avc_nearest_point")
+        L.call("avc_nearest_point", q, M, r, K, idx)
     return idx
 
 
@@ -188,8 +186,7 @@ def skin_apply(xf, idx, points, out=None):
     if M and T:
         if int(idx.min()) < 0 or int(idx.max()) >= K:
             raise ValueError("skin_apply: a template index outside [0, %d)" % K)
-        L.check(L.load().avc_skin_apply(L.ptr(xf.contiguous()), L.ptr(idx), L.ptr(points.contiguous()), M, K, T, L.ptr(out), L.stream()),
-                "avc_skin_apply")
+        L.call("avc_skin_apply", xf.contiguous(), idx, points.contiguous(), M, K, T, out)
     return out
 
 

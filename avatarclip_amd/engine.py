@@ -67,8 +67,7 @@ class Packed:
             self.w_f16 = torch.empty(n16, dtype=torch.float16, device=f.device)
             self.w_bf16 = torch.empty(n16, dtype=torch.bfloat16, device=f.device)
             self.tab = torch.empty(n32, dtype=torch.float32, device=f.device)
-            L.check(L.load().avc_pack_params(L.ptr(f), f.numel(), L.ptr(dl.idx16), L.ptr(dl.scale16), n16, L.ptr(dl.idx32), L.ptr(dl.scale32), n32,
-                                             L.ptr(self.w_f16), L.ptr(self.w_bf16), L.ptr(self.tab), L.stream()), "avc_pack_params")
+            L.call("avc_pack_params", f, f.numel(), dl.idx16, dl.scale16, n16, dl.idx32, dl.scale32, n32, self.w_f16, self.w_bf16, self.tab)
             return
         pz = torch.cat([flatP.detach().float(), flatP.new_zeros(1)])
         w = pz[dl.idx16] * dl.scale16
@@ -131,10 +130,8 @@ class DenseParamsFn(torch.autograd.Function):
         ctx.w_off = (ctypes.c_long * n)(*[o[0] for o in offs])
         ctx.b_off = (ctypes.c_long * n)(*[o[1] for o in offs])
         ctx.n = n
-        lib = L.load()
         assert all(t.is_contiguous() and t.dtype == torch.float32 for t in tensors)
-        L.check(lib.avc_dense_params_fwd(n, arr(vs), arr(gs), arr(bs), ctx.rows, ctx.cols, ctx.w_off, ctx.b_off, L.ptr(flat), L.stream()),
-                "avc_dense_params_fwd")
+        L.call("avc_dense_params_fwd", n, arr(vs), arr(gs), arr(bs), ctx.rows, ctx.cols, ctx.w_off, ctx.b_off, flat)
         ctx.save_for_backward(*tensors)
         return flat
 
@@ -147,8 +144,8 @@ class DenseParamsFn(torch.autograd.Function):
         outs = [torch.empty_like(t) for t in tensors]
         PA = ctypes.c_void_p * n
         arr = lambda ts: PA(*[(t.data_ptr() if t.numel() else None) for t in ts])
-        L.check(L.load().avc_dense_params_bwd(n, arr(vs), arr(gs), arr(outs[0::3]), arr(outs[1::3]), arr(outs[2::3]), ctx.rows, ctx.cols,
-                                              ctx.w_off, ctx.b_off, L.ptr(dflat), L.stream()), "avc_dense_params_bwd")
+        L.call("avc_dense_params_bwd", n, arr(vs), arr(gs), arr(outs[0::3]), arr(outs[1::3]), arr(outs[2::3]), ctx.rows, ctx.cols, ctx.w_off,
+               ctx.b_off, dflat)
         return (None,) + tuple(o if t.numel() else None for o, t in zip(outs, tensors))
 
 
@@ -358,17 +355,14 @@ class Engine:
         if sdf_out is None:
             sdf_out = torch.empty(R, S, device=self.device, dtype=torch.float32)
         with Engine._Timed("avc_sdf_forward", R * S):
-            L.check(self.lib.avc_sdf_forward(self.net, None, L.ptr(rays_o), L.ptr(rays_d), L.ptr(z), S, z.stride(0), R * S,
-                                             L.ptr(pk.w_f16), L.ptr(pk.tab), self.dl.offsets, L.ptr(sdf_out),
-                                             L.ptr(slot), ld_out, L.stream()), "avc_sdf_forward")
+            L.call("avc_sdf_forward", self.net, None, rays_o, rays_d, z, S, z.stride(0), R * S, pk.w_f16, pk.tab, self.dl.offsets, sdf_out, slot,
+                   ld_out)
         return sdf_out
 
     def sdf_pts(self, pk: Packed, pts):
         pts = pts.contiguous().float()
         out = torch.empty(pts.shape[0], 1, device=self.device, dtype=torch.float32)
-        L.check(self.lib.avc_sdf_forward(self.net, L.ptr(pts), None, None, None, 1, 1, pts.shape[0], L.ptr(pk.w_f16),
-                                         L.ptr(pk.tab), self.dl.offsets, L.ptr(out), None, 0, L.stream()),
-                "avc_sdf_forward")
+        L.call("avc_sdf_forward", self.net, pts, None, None, None, 1, 1, pts.shape[0], pk.w_f16, pk.tab, self.dl.offsets, out, None, 0)
         return out
 
     def upsample_step(self, rays_o, rays_d, z, sdf, m, inv_s):
@@ -379,9 +373,7 @@ class Engine:
         slot = torch.empty(R, m, device=self.device, dtype=torch.int32)
         # AVC_UPSAMPLE_GROUP=0: one wavefront per ray for every n (A/B partner and cross-check of the grouped kernels), read HERE per call
         lanes = 64 if os.environ.get("AVC_UPSAMPLE_GROUP", "1") == "0" else 0
-        L.check(self.lib.avc_upsample_step_lanes(L.ptr(rays_o), L.ptr(rays_d), L.ptr(z), L.ptr(sdf), R, n, m, float(inv_s),
-                                                 L.ptr(z_out), L.ptr(sdf_out), L.ptr(z_new), L.ptr(slot), lanes, L.stream()),
-                "avc_upsample_step")
+        L.call("avc_upsample_step_lanes", rays_o, rays_d, z, sdf, R, n, m, float(inv_s), z_out, sdf_out, z_new, slot, lanes)
         return z_out, sdf_out, z_new, slot
 
     def points_fwd(self, pk: Packed, rays_o, rays_d, z, sample_dist):
@@ -393,10 +385,8 @@ class Engine:
         if self._fwd_scratch is None:
             self._fwd_scratch = torch.empty(self.MAX_FWD_WAVES * self.fwd_scr_bytes, dtype=torch.uint8, device=self.device)
         with Engine._Timed("avc_render_points_fwd", N):
-            L.check(self.lib.avc_render_points_fwd(self.net, None, L.ptr(rays_o), L.ptr(rays_d), L.ptr(z), S, z.stride(0),
-                                                   float(sample_dist), N, L.ptr(pk.w_f16), L.ptr(pk.tab), self.dl.offsets,
-                                                   L.ptr(sdf), L.ptr(nrm), L.ptr(rgb), self.MAX_FWD_WAVES, L.ptr(self._fwd_scratch),
-                                                   L.stream()), "avc_render_points_fwd")
+            L.call("avc_render_points_fwd", self.net, None, rays_o, rays_d, z, S, z.stride(0), float(sample_dist), N, pk.w_f16, pk.tab,
+                   self.dl.offsets, sdf, nrm, rgb, self.MAX_FWD_WAVES, self._fwd_scratch)
         return sdf, nrm, rgb
 
     def points_fwd_train(self, pk: Packed, rays_o, rays_d, z, sample_dist, r0=0, r1=None, out=None):
@@ -411,11 +401,10 @@ class Engine:
         panels, masks = self._bufs_f((npts + 31) // 32)
         esz = 4
         with Engine._Timed("avc_render_points_fwd_train", npts):
-            L.check(self.lib.avc_render_points_fwd_train(
-                self.net, None, rays_o.data_ptr() + r0 * 3 * esz, rays_d.data_ptr() + r0 * 3 * esz,
-                z.data_ptr() + r0 * z.stride(0) * esz, S, z.stride(0), float(sample_dist), npts, L.ptr(pk.w_f16), L.ptr(pk.tab),
-                self.dl.offsets, sdf.data_ptr() + r0 * S * esz, nrm.data_ptr() + r0 * S * 3 * esz, rgb.data_ptr() + r0 * S * 6 * esz,
-                self.MAX_FWD_WAVES, L.ptr(panels), L.ptr(masks), L.stream()), "avc_render_points_fwd_train")
+            L.call("avc_render_points_fwd_train", self.net, None, rays_o.data_ptr() + r0 * 3 * esz, rays_d.data_ptr() + r0 * 3 * esz,
+                   z.data_ptr() + r0 * z.stride(0) * esz, S, z.stride(0), float(sample_dist), npts, pk.w_f16, pk.tab, self.dl.offsets,
+                   sdf.data_ptr() + r0 * S * esz, nrm.data_ptr() + r0 * S * 3 * esz, rgb.data_ptr() + r0 * S * 6 * esz, self.MAX_FWD_WAVES, panels,
+                   masks)
         return out
 
     def composite_fwd(self, sdf, nrm, rgb, z, rays_o, rays_d, inv_s, sample_dist, cos_anneal, bg, bg_mode):
@@ -431,10 +420,8 @@ class Engine:
         eik = torch.empty(R, 2, device=dev, dtype=f32)
         wstat = torch.empty(2, R, device=dev, dtype=f32)
         nsum = torch.empty(R, 3, device=dev, dtype=f32)
-        L.check(self.lib.avc_composite_fwd(L.ptr(sdf), L.ptr(nrm), L.ptr(rgb), L.ptr(z), L.ptr(rays_o), L.ptr(rays_d), R, S,
-                                           L.ptr(inv_s), float(sample_dist), float(cos_anneal), L.ptr(bg), bg_mode,
-                                           L.ptr(color), L.ptr(extra), L.ptr(weights), L.ptr(cdf), L.ptr(mid_z),
-                                           L.ptr(inside), L.ptr(eik), L.ptr(wstat), L.ptr(nsum), L.stream()), "avc_composite_fwd")
+        L.call("avc_composite_fwd", sdf, nrm, rgb, z, rays_o, rays_d, R, S, inv_s, float(sample_dist), float(cos_anneal), bg, bg_mode, color, extra,
+               weights, cdf, mid_z, inside, eik, wstat, nsum)
         return color, extra, weights, cdf, mid_z, inside, eik, wstat, nsum
 
     def composite_bwd(self, sdf, nrm, rgb, z, rays_o, rays_d, inv_s, sample_dist, cos_anneal, bg, bg_mode, d_color,
@@ -445,11 +432,8 @@ class Engine:
         d_n = torch.empty(R, S, 3, device=dev, dtype=f32)
         d_rgb = torch.empty(R, S, 6, device=dev, dtype=f32)
         d_inv = torch.empty(R, device=dev, dtype=f32)
-        L.check(self.lib.avc_composite_bwd(L.ptr(sdf), L.ptr(nrm), L.ptr(rgb), L.ptr(z), L.ptr(rays_o), L.ptr(rays_d), R, S,
-                                           L.ptr(inv_s), float(sample_dist), float(cos_anneal), L.ptr(bg), bg_mode,
-                                           L.ptr(d_color), L.ptr(d_extra), L.ptr(d_w), L.ptr(d_n_up), L.ptr(d_wsum), L.ptr(d_nsum),
-                                           L.ptr(eik_scale), L.ptr(d_sdf), L.ptr(d_n), L.ptr(d_rgb), L.ptr(d_inv), L.stream()),
-                "avc_composite_bwd")
+        L.call("avc_composite_bwd", sdf, nrm, rgb, z, rays_o, rays_d, R, S, inv_s, float(sample_dist), float(cos_anneal), bg, bg_mode, d_color,
+               d_extra, d_w, d_n_up, d_wsum, d_nsum, eik_scale, d_sdf, d_n, d_rgb, d_inv)
         return d_sdf, d_n, d_rgb, d_inv
 
     # ------------------------------------------------------------------ backward of the point MLP
@@ -500,24 +484,21 @@ class Engine:
                 mptr = masks.data_ptr() + fblk0 * self.mask_u16 * 2
                 gpanels = self._bufs_g(nblk)
                 bwd_args = (self.net, None, rays_o.data_ptr() + s0 * 3 * esz, rays_d.data_ptr() + s0 * 3 * esz,
-                            z.data_ptr() + s0 * z.stride(0) * esz, S, z.stride(0), float(sample_dist), npts, L.ptr(pk.w_bf16), L.ptr(pk.tab),
+                            z.data_ptr() + s0 * z.stride(0) * esz, S, z.stride(0), float(sample_dist), npts, pk.w_bf16, pk.tab,
                             self.dl.offsets, d_sdf.data_ptr() + s0 * S * esz, d_n.data_ptr() + s0 * S * 3 * esz,
-                            d_rgb.data_ptr() + s0 * S * 6 * esz, rgb.data_ptr() + s0 * S * 6 * esz, fptr, L.ptr(gpanels), mptr, L.ptr(self._colsum))
+                            d_rgb.data_ptr() + s0 * S * 6 * esz, rgb.data_ptr() + s0 * S * 6 * esz, fptr, gpanels, mptr, self._colsum)
                 rows = int(self.lib.avc_bwd_colsum_rows(npts, self.MAX_BWD_WAVES))     # every row of the launch's grid is written
                 with Engine._Timed("avc_render_points_bwd", npts):
-                    L.check(self.lib.avc_render_points_bwd(*bwd_args, self.MAX_BWD_WAVES, st), "avc_render_points_bwd")
+                    L.call("avc_render_points_bwd", *bwd_args, self.MAX_BWD_WAVES, stream=st)
                 cs_slab = self._colsum[:rows].sum(0)      # (torch's reduction: a fixed tree, deterministic)
                 cs_total = cs_slab if cs_total is None else cs_total + cs_slab
                 ns = max(1, min(self.WG_MAX_SPLITS, nblk // self.WG_BLOCKS_PER_SPLIT, nblk))
                 with Engine._Timed("avc_weight_grad(all pairs)", npts):
-                    L.check(self.lib.avc_weight_grad_all(fptr, self.fwd_tiles, L.ptr(gpanels), self.grad_tiles, len(self._pairs_host),
-                                                         self._pairs_host.ctypes.data, nblk, L.ptr(self._partials),
-                                                         L.ptr(self._bpartials), ns, self._partials.stride(0),
-                                                         self._bpartials.stride(0), st), "avc_weight_grad_all")
+                    L.call("avc_weight_grad_all", fptr, self.fwd_tiles, gpanels, self.grad_tiles, len(self._pairs_host), self._pairs_host.ctypes.data,
+                           nblk, self._partials, self._bpartials, ns, self._partials.stride(0), self._bpartials.stride(0), stream=st)
                     if fused_tail:
-                        L.check(self.lib.avc_weight_grad_reduce(L.ptr(self._partials), L.ptr(self._bpartials), ns, self._partials.stride(0),
-                                                                self._bpartials.stride(0), lay.gout_size, lay.gbias_size, L.ptr(gacc),
-                                                                int(nslab > 0), st), "avc_weight_grad_reduce")
+                        L.call("avc_weight_grad_reduce", self._partials, self._bpartials, ns, self._partials.stride(0), self._bpartials.stride(0),
+                               lay.gout_size, lay.gbias_size, gacc, int(nslab > 0), stream=st)
                         nslab += 1
                         continue
                     po, pb_ = self._partials[:ns].sum(0), self._bpartials[:ns].sum(0)
@@ -529,8 +510,7 @@ class Engine:
             if nslab == 0:
                 grad.zero_()
             else:
-                L.check(self.lib.avc_weight_grad_unpack(L.ptr(gacc), L.ptr(self.dl.csr_off), L.ptr(self.dl.csr_src), L.ptr(self.dl.csr_scale),
-                                                        lay.nparam, L.ptr(grad), st), "avc_weight_grad_unpack")
+                L.call("avc_weight_grad_unpack", gacc, self.dl.csr_off, self.dl.csr_src, self.dl.csr_scale, lay.nparam, grad, stream=st)
         else:
             grad = torch.zeros(lay.nparam, device=self.device, dtype=torch.float32)
             grad.index_add_(0, self.dl.un_tgt, gout[self.dl.un_src] * self.dl.un_scale)
@@ -568,7 +548,7 @@ class RenderCoreFn(torch.autograd.Function):
             sdf, nrm, rgb, z_vals, rays_o, rays_d, inv_s_d, sample_dist, cos_anneal, bg, bg_mode)
         wsum, wmax = wstat[0].reshape(R, 1), wstat[1].reshape(R, 1)       # (planar: views, no copies)
         eo = torch.empty(2, device=eik.device, dtype=torch.float32)        # renderer.py:283-285 in one launch: (gradient_error, its denominator)
-        L.check(eng.lib.avc_colsum(L.ptr(eik), R, 2, 1, L.ptr(eo), L.ptr(eng.colsum_scratch()), L.stream()), "avc_colsum")
+        L.call("avc_colsum", eik, R, 2, 1, eo, eng.colsum_scratch())
         gerr, eik_den = eo[0], eo[1]
         ctx.eng, ctx.pk = eng, pk
         ctx.consts = (sample_dist, cos_anneal, bg_mode)
@@ -606,5 +586,5 @@ class RenderCoreFn(torch.autograd.Function):
         valid = ctx.panel_token is not None and eng._panel_owner is ctx.panel_token
         grad = eng.points_bwd(pk, rays_o, rays_d, z_vals, sample_dist, d_sdf, d_n, d_rgb, rgb, panels_valid=valid)
         d_inv_s = torch.empty(1, device=d_inv.device, dtype=torch.float32)
-        L.check(eng.lib.avc_colsum(L.ptr(d_inv), R, 1, 0, L.ptr(d_inv_s), L.ptr(eng.colsum_scratch()), L.stream()), "avc_colsum")
+        L.call("avc_colsum", d_inv, R, 1, 0, d_inv_s, eng.colsum_scratch())
         return grad, d_inv_s, None, None, None, None, None, None, None, None

@@ -221,7 +221,7 @@ class _InvSFn(torch.autograd.Function):
         from . import lib as L
         v = variance.detach().float().reshape(1).contiguous()
         out = torch.empty(2, device=v.device, dtype=torch.float32)       # (inv_s, 1 / inv_s)
-        L.check(L.load().avc_inv_s(L.ptr(v), None, L.ptr(out), L.stream()), "avc_inv_s")
+        L.call("avc_inv_s", v, None, out)
         ctx.save_for_backward(v)
         ctx.shape = variance.shape
         return out
@@ -232,5 +232,5 @@ class _InvSFn(torch.autograd.Function):
         (v,) = ctx.saved_tensors
         g = g.float()[:1].contiguous()        # (the second entry, 1 / inv_s, is a detached statistic)
         out = torch.empty(1, device=v.device, dtype=torch.float32)
-        L.check(L.load().avc_inv_s(L.ptr(v), L.ptr(g), L.ptr(out), L.stream()), "avc_inv_s")
+        L.call("avc_inv_s", v, g, out)
         return out.reshape(ctx.shape)

@@ -42,9 +42,8 @@ class ShadeLossFn(torch.autograd.Function):
         images = torch.empty(2, P, 3, device=dev, dtype=torch.float32)
         partial = torch.empty(lib.avc_shade_loss_blocks(P), 4, device=dev, dtype=torch.float32)
         sums = torch.empty(4, device=dev, dtype=torch.float32)
-        L.check(lib.avc_shade_loss_fwd(L.ptr(color), L.ptr(extra), L.ptr(wsum), L.ptr(nsum), L.ptr(true_rgb), L.ptr(mask), L.ptr(ray_of_pixel),
-                                       L.ptr(bg), float(bg_const), L.ptr(light), P, int(img0_is_extra), L.ptr(images), L.ptr(partial), L.ptr(sums),
-                                       L.ptr(_ticket(dev)), L.stream()), "avc_shade_loss_fwd")
+        L.call("avc_shade_loss_fwd", color, extra, wsum, nsum, true_rgb, mask, ray_of_pixel, bg, float(bg_const), light, P, int(img0_is_extra),
+               images, partial, sums, _ticket(dev))
         ctx.save_for_backward(color, extra, wsum, nsum if nsum is not None else color.new_zeros(0), true_rgb, mask,
                               ray_of_pixel if ray_of_pixel is not None else color.new_zeros(0), light if light is not None else color.new_zeros(0))
         ctx.flags = (nsum is not None, ray_of_pixel is not None, light is not None, int(img0_is_extra), P)
@@ -61,10 +60,9 @@ class ShadeLossFn(torch.autograd.Function):
         z = torch.zeros(R * (10 if has_n else 7), device=dev, dtype=torch.float32)      # (rays that own no pixel keep a zero gradient)
         dcolor, dextra, dwsum = z[:3 * R].view_as(color), z[3 * R:6 * R].view_as(extra), z[6 * R:7 * R].view_as(wsum)
         dnsum = z[7 * R:].view_as(nsum) if has_n else None
-        L.check(L.load().avc_shade_loss_bwd(L.ptr(color), L.ptr(extra), L.ptr(wsum), L.ptr(nsum) if has_n else None, L.ptr(true_rgb), L.ptr(mask),
-                                            L.ptr(rop) if has_rop else None, L.ptr(light) if has_light else None, P, img0_is_extra,
-                                            dimages[0].data_ptr(), dimages[1].data_ptr(), L.ptr(gs), L.ptr(dcolor), L.ptr(dextra), L.ptr(dwsum),
-                                            L.ptr(dnsum) if has_n else None, L.stream()), "avc_shade_loss_bwd")
+        L.call("avc_shade_loss_bwd", color, extra, wsum, nsum if has_n else None, true_rgb, mask, rop if has_rop else None,
+               light if has_light else None, P, img0_is_extra, dimages[0].data_ptr(), dimages[1].data_ptr(), gs, dcolor, dextra, dwsum,
+               dnsum if has_n else None)
         return dcolor, dextra, dwsum, dnsum, None, None, None, None, None, None, None
 
 
@@ -83,8 +81,7 @@ class LossTailFn(torch.autograd.Function):
         out = torch.empty(8, device=dev, dtype=torch.float32)
         saved = torch.empty(4 * B + 1, device=dev, dtype=torch.float32)
         w = (float(igr_w), float(mask_w), float(clip_w), float(P))
-        L.check(L.load().avc_loss_tail_fwd(L.ptr(enc), L.ptr(text), B, text.shape[0], D, L.ptr(sums), L.ptr(e1), *w, L.ptr(loss), L.ptr(out),
-                                           L.ptr(saved), L.stream()), "avc_loss_tail_fwd")
+        L.call("avc_loss_tail_fwd", enc, text, B, text.shape[0], D, sums, e1, *w, loss, out, saved)
         ctx.save_for_backward(enc, text, sums, saved)
         ctx.w, ctx.eik_shape = w, eik.shape
         ctx.mark_non_differentiable(out)
@@ -97,8 +94,7 @@ class LossTailFn(torch.autograd.Function):
         g = gloss.contiguous().float()
         d_enc = torch.empty_like(enc)
         dd = torch.empty(8, device=enc.device, dtype=torch.float32)
-        L.check(L.load().avc_loss_tail_bwd(L.ptr(g), L.ptr(enc), L.ptr(text), B, text.shape[0], D, L.ptr(sums), L.ptr(saved), *ctx.w, L.ptr(d_enc),
-                                           L.ptr(dd), L.stream()), "avc_loss_tail_bwd")
+        L.call("avc_loss_tail_bwd", g, enc, text, B, text.shape[0], D, sums, saved, *ctx.w, d_enc, dd)
         return d_enc, None, dd[:4], dd[4].reshape(ctx.eik_shape), None, None, None, None
 
 
@@ -110,7 +106,7 @@ class ResizeNormFn(torch.autograd.Function):
         images = images.contiguous().float()
         B, H, W, _ = images.shape
         out = torch.empty(B, 3, 224, 224, device=images.device, dtype=torch.float32)
-        L.check(L.load().avc_resize_norm_fwd(L.ptr(images), B, H, W, _MEAN, _STD, L.ptr(out), L.stream()), "avc_resize_norm_fwd")
+        L.call("avc_resize_norm_fwd", images, B, H, W, _MEAN, _STD, out)
         ctx.shape = (B, H, W)
         return out
 
@@ -119,7 +115,7 @@ class ResizeNormFn(torch.autograd.Function):
         B, H, W = ctx.shape
         dout = dout.contiguous().float()
         dimg = torch.empty(B, H, W, 3, device=dout.device, dtype=torch.float32)
-        L.check(L.load().avc_resize_norm_bwd(L.ptr(dout), B, H, W, _MEAN, _STD, L.ptr(dimg), L.stream()), "avc_resize_norm_bwd")
+        L.call("avc_resize_norm_bwd", dout, B, H, W, _MEAN, _STD, dimg)
         return dimg
 
 

@@ -1,98 +1,131 @@
-"""ctypes binding of libavc.so (the C ABI declared in include/avc.h).  No fallback: if the library is missing
-or a call fails, an exception is raised."""
+"""ctypes binding of libavc.so.  include/avc.h is the one declaration of the C ABI: load() parses it and derives every
+restype / argtypes from it, and call() checks each tensor against the element type the header gives its parameter.  No
+fallback: if the library is missing or a call fails, an exception is raised."""
+import collections
 import ctypes
 import os
+import re
 
 import torch
 
 from . import build as _build
 
 _lib = None
-ABI_VERSION = 4          # AVC_ABI_VERSION of include/avc.h this binding was written against
+_launches = {}           # name -> the launcher bind() made, one per launch entry point (filled by load())
+ABI_VERSION = None       # AVC_ABI_VERSION of include/avc.h (set by load())
+HEADER = os.path.normpath(os.path.join(_build.CSRC, _build.HEADERS[-1]))
 
-c_int, c_long, c_float, c_double, c_void_p = ctypes.c_int, ctypes.c_long, ctypes.c_float, ctypes.c_double, ctypes.c_void_p
-P = c_void_p
+c_int, c_long, c_float, c_double, c_void_p, c_char_p = (ctypes.c_int, ctypes.c_long, ctypes.c_float, ctypes.c_double,
+                                                        ctypes.c_void_p, ctypes.c_char_p)
 
-_SIGS = {
-    "avc_version": (c_int, []),
-    "avc_num_offsets": (c_int, []),
-    "avc_sdf_forward": (c_int, [c_int, P, P, P, P, c_int, c_int, c_long, P, P, P, P, P, c_int, P]),
-    "avc_upsample_step": (c_int, [P, P, P, P, c_int, c_int, c_int, c_float, P, P, P, P, P]),
-    "avc_upsample_step_lanes": (c_int, [P, P, P, P, c_int, c_int, c_int, c_float, P, P, P, P, c_int, P]),
-    "avc_render_points_fwd": (c_int, [c_int, P, P, P, P, c_int, c_int, c_float, c_long, P, P, P, P, P, P, c_long, P, P]),
-    "avc_fwd_scratch_bytes_per_wave": (c_long, [c_int]),
-    "avc_composite_fwd": (c_int, [P, P, P, P, P, P, c_int, c_int, P, c_float, c_float, P, c_int, P, P, P, P, P, P, P, P, P, P]),
-    "avc_composite_bwd": (c_int, [P, P, P, P, P, P, c_int, c_int, P, c_float, c_float, P, c_int, P, P, P, P, P, P, P,
-                                  P, P, P, P, P]),
-    "avc_render_points_fwd_train": (c_int, [c_int, P, P, P, P, c_int, c_int, c_float, c_long, P, P, P, P, P, P, c_long, P, P, P]),
-    "avc_fwd_panel_tiles": (c_int, [c_int]),
-    "avc_grad_panel_tiles": (c_int, [c_int]),
-    "avc_mask_u16_per_block": (c_int, [c_int]),
-    "avc_render_points_bwd": (c_int, [c_int, P, P, P, P, c_int, c_int, c_float, c_long, P, P, P, P, P, P, P, P, P, P, P, c_long, P]),
-    "avc_bwd_colsum_floats": (c_int, [c_int]),
-    "avc_bwd_colsum_rows": (c_long, [c_long, c_long]),
-    "avc_mc_classify": (c_int, [P, c_int, c_int, c_int, c_float, P, P, P, P]),
-    "avc_mc_emit": (c_int, [P, c_int, c_int, c_int, c_float, P, P, P, P, P, P, P, P, P]),
-    "avc_text_attention_fwd": (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, P]),
-    "avc_vit_linear": (c_int, [P, P, P, P, P, P, c_int, c_int, c_int, c_int, P, P]),
-    "avc_vit_linear_bwd_gelu": (c_int, [P, P, P, P, c_int, c_int, c_int, P, P]),
-    "avc_vit_workspace_bytes": (c_long, [c_int, c_int]),
-    "avc_vit_ln_pack": (c_int, [P, P, P, c_float, c_int, c_int, P, P]),
-    "avc_vit_linear_packed": (c_int, [P, P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, P]),
-    "avc_vit_pack": (c_int, [P, P, P, c_int, c_int, P]),
-    "avc_vit_attention_bwd_packed": (c_int, [P, P, P, c_int, c_int, c_int, c_int, P]),
-    "avc_vit_ln_bwd": (c_int, [P, P, P, c_float, P, P, P, c_int, c_int, P]),
-    "avc_vit_attention_fwd_packed": (c_int, [P, P, c_int, c_int, c_int, c_int, P]),
-    "avc_vit_attention_fwd": (c_int, [P, P, c_int, c_int, c_int, c_int, P]),
-    "avc_vit_attention_bwd": (c_int, [P, P, P, c_int, c_int, c_int, c_int, P]),
-    "avc_probe_mfma": (c_int, [P, P, P, P, P, P, P]),
-    "avc_rasterize_faces": (c_int, [P, P, c_int, c_int, c_float, c_float, P, P, P]),
-    "avc_rasterize_scratch_bytes": (c_long, [c_int, c_int]),
-    "avc_rasterize_mesh": (c_int, [P, c_int, P, c_int, P, c_float, P, c_int, c_float, c_float, P, P, c_int, c_int, P, P]),
-    "avc_rasterize_mesh_save": (c_int, [P, c_int, c_int, P, c_int, P, c_float, P, c_int, c_float, c_float, P, P, P, P, P]),
-    "avc_rasterize_mesh_grad": (c_int, [P, P, c_int, c_int, P, c_int, P, P, c_int, c_float, P, P, P, P, P, P]),
-    "avc_dense_params_fwd": (c_int, [c_int, P, P, P, P, P, P, P, P, P]),
-    "avc_dense_params_bwd": (c_int, [c_int, P, P, P, P, P, P, P, P, P, P, P]),
-    "avc_weight_grad_all": (c_int, [P, c_int, P, c_int, c_int, P, c_long, P, P, c_int, c_int, c_int, P]),
-    "avc_weight_grad_reduce": (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, P, c_int, P]),
-    "avc_weight_grad_unpack": (c_int, [P, P, P, P, c_int, P, P]),
-    "avc_shade_loss_blocks": (c_int, [c_int]),
-    "avc_shade_loss_fwd": (c_int, [P, P, P, P, P, P, P, P, c_float, P, c_int, c_int, P, P, P, P, P]),
-    "avc_colsum": (c_int, [P, c_long, c_int, c_int, P, P, P]),
-    "avc_colsum_scratch_bytes": (c_long, []),
-    "avc_inv_s": (c_int, [P, P, P, P]),
-    "avc_pack_params": (c_int, [P, c_int, P, P, c_int, P, P, c_int, P, P, P, P]),
-    "avc_coarse_z": (c_int, [P, P, P, c_int, c_int, P, P]),
-    "avc_loss_tail_fwd": (c_int, [P, P, c_int, c_int, c_int, P, P, c_float, c_float, c_float, c_float, P, P, P, P]),
-    "avc_loss_tail_bwd": (c_int, [P, P, P, c_int, c_int, c_int, P, P, c_float, c_float, c_float, c_float, P, P, P]),
-    "avc_shade_loss_bwd": (c_int, [P, P, P, P, P, P, P, P, c_int, c_int, P, P, P, P, P, P, P, P]),
-    "avc_resize_norm_fwd": (c_int, [P, c_int, c_int, c_int, P, P, P, P]),
-    "avc_resize_norm_bwd": (c_int, [P, c_int, c_int, c_int, P, P, P, P]),
-    "avc_gen_rays": (c_int, [P, P, P, c_int, c_int, c_float, c_float, c_float, c_int, c_int, c_int, P, P, P, P, P, P, P]),
-    "avc_chess_background": (c_int, [P, c_int, c_int, c_int, P, P]),
-    "avc_nearest_point": (c_int, [P, c_int, P, c_int, P, P]),
-    "avc_mesh_components": (c_int, [P, c_int, c_int, P, P]),
-    "avc_mesh_largest_island": (c_int, [P, c_int, c_int, P, P, P, P, P, P]),
-    "avc_mesh_compact": (c_int, [P, P, P, c_int, c_int, P, P, P, P, P, P, P, P]),
-    "avc_skin_apply": (c_int, [P, P, P, c_int, c_int, c_int, P, P]),
-    "avc_rig_cell_keys": (c_int, [P, c_int, c_double, c_double, c_double, c_double, c_int, P, P]),
-    "avc_rig_cluster_heads": (c_int, [P, c_int, P, P]),
-    "avc_rig_cluster_average": (c_int, [P, c_int, P, P, c_int, P, c_int, P, P, P, P]),
-    "avc_rig_tri_keys": (c_int, [P, c_int, c_int, P, c_int, P, P, P]),
-    "avc_rig_tri_unique": (c_int, [P, P, c_int, P, P]),
-    "avc_rig_tri_compact": (c_int, [P, c_int, P, P, c_int, P, P]),
-    "avc_skin_sort_template": (c_int, [P, c_int, c_int, P, P, P, P]),
-    "avc_skin_pack": (c_int, [P, P, P, c_int, P, c_int, c_int, P, P, P, P]),
-    "avc_rot_to_quat": (c_int, [P, c_long, P, P]),
-    "avc_preview_scratch_bytes": (c_long, [c_int, c_int]),
-    "avc_preview_project": (c_int, [P, c_int, c_int, P, c_float, c_float, c_float, c_int, P, P]),
-    "avc_preview_raster": (c_int, [P, c_int, c_int, P, c_int, c_int, P, P]),
-    "avc_preview_shade": (c_int, [P, P, c_int, c_int, P, c_int, P, c_int, P, c_float, c_float, c_float, c_float, c_float, c_int, c_int, P, P, P, P]),
-    "avc_skin_blend4": (c_int, [P, P, P, P, c_int, c_int, c_int, P, P]),
-    "avc_smpl_joint_mats": (c_int, [P, P, P, c_int, P, P, P]),
-    "avc_smpl_pose": (c_int, [P, P, P, P, P, c_int, c_int, P, P]),
-}
-_OPTIONAL = {}
+_SCALARS = {"int": c_int, "long": c_long, "float": c_float, "double": c_double}
+_RETURNS = {"int": c_int, "long": c_long, "const char*": c_char_p}
+_INTS = [getattr(torch, n) for n in ("bool", "int8", "uint8", "int16", "uint16", "int32", "uint32", "int64", "uint64") if hasattr(torch, n)]
+_FLOAT32 = frozenset([torch.float32])
+_INT1, _INT4, _INT8 = (frozenset(d for d in _INTS if d.itemsize == n) for n in (1, 4, 8))
+# element type of a pointer parameter -> the tensor dtypes it takes (None: any).  "void*" is the element of the host arrays of pointers.
+_ELEMENTS = {"float": _FLOAT32, "int": _INT4, "unsigned": _INT4, "long": _INT8, "long long": _INT8, "unsigned long long": _INT8,
+             "void*": _INT8, "signed char": _INT1, "unsigned char": _INT1, "void": None}
+_TYPE_WORDS = {"const", "void", "char", "short", "int", "long", "float", "double", "signed", "unsigned"}
+
+# a parameter: its name, ctypes type and C type as declared; for a pointer also the element type and whether that is const
+Param = collections.namedtuple("Param", "name ctype decl elem const")
+
+
+class Proto(collections.namedtuple("Proto", "name restype params")):
+    @property
+    def argtypes(self):
+        return [p.ctype for p in self.params]
+
+    @property
+    def launch(self):
+        """a launch returns a status and ends in `void* stream`; everything else is a query"""
+        return self.restype is c_int and bool(self.params) and self.params[-1][:3:2] == ("stream", "void*")
+
+
+def _spell(tokens):
+    return " ".join(tokens).replace(" *", "*")
+
+
+def parse_header(text):
+    """(the prototypes of a C header in the style of include/avc.h as {name: Proto}, its AVC_ABI_VERSION or None).  A declaration
+    this cannot map raises ValueError."""
+    abi = re.search(r"^\s*#\s*define\s+AVC_ABI_VERSION\s+(\d+)\s*$", text, flags=re.M)
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    text = re.sub(r"//[^\n]*", " ", text)
+    text = re.sub(r"^\s*#[^\n]*", " ", text, flags=re.M)
+    text = re.sub(r'extern\s+"C"\s*\{', " ", text)
+    protos = {}
+    for stmt in text.split(";"):
+        stmt = " ".join(stmt.split())
+        if stmt in ("", "}"):
+            continue
+        m = re.fullmatch(r"(.+?)\b(\w+) ?\((.*)\)", stmt)
+        if not m:
+            raise ValueError("cannot parse the declaration %r" % stmt)
+        name = m.group(2)
+        ret = _spell(m.group(1).replace("*", " * ").split())
+        if ret not in _RETURNS:
+            raise ValueError("%s: unknown return type `%s`" % (name, ret))
+        params = []
+        plist = m.group(3).strip()
+        for i, p in enumerate([] if plist in ("", "void") else plist.split(",")):
+            if "(" in p or ")" in p or "[" in p:
+                raise ValueError("%s: parameter %d `%s` is a function pointer or an array" % (name, i + 1, p.strip()))
+            tok = p.replace("*", " * ").split()
+            if len(tok) < 2 or tok[-1] == "*" or tok[-1] in _TYPE_WORDS or not re.fullmatch(r"[A-Za-z_]\w*", tok[-1]):
+                raise ValueError("%s: parameter %d `%s` has no name" % (name, i + 1, p.strip()))
+            pname, tok = tok[-1], tok[:-1]
+            decl = _spell(tok)
+            if "*" in tok:
+                pointee = tok[:len(tok) - 1 - tok[::-1].index("*")]
+                elem = _spell([t for t in pointee if t != "const"])
+                if elem not in _ELEMENTS:
+                    raise ValueError("%s: parameter `%s` points to the unknown type `%s`" % (name, pname, elem))
+                params.append(Param(pname, c_void_p, decl, elem, "const" in pointee))
+            elif decl in _SCALARS:
+                params.append(Param(pname, _SCALARS[decl], decl, None, False))
+            else:
+                raise ValueError("%s: parameter `%s` has the unknown type `%s`" % (name, pname, decl))
+        protos[name] = Proto(name, _RETURNS[ret], tuple(params))
+    return protos, int(abi.group(1)) if abi else None
+
+
+# One argument of a generated launcher.  A tensor is checked (dtype, device, contiguity) and gives its address; None, an int and a ctypes
+# object go to ctypes as they are.
+_POINTER = "({a}.data_ptr() if {dtype}{a}.is_cuda and {a}.is_contiguous() else _refuse({i}, {a})) if isinstance({a}, Tensor) else {a}"
+
+
+def bind(proto, fn):
+    """The launcher of one launch entry point, `avc_x(<the header's parameters before the stream>, *, stream=None)`, written out and compiled
+    here, once: one expression per argument, so that a call runs no loop and makes no Python call per argument, and Python itself refuses a
+    wrong argument count.  This is the cost of a launch on the host (profiles/abi_one_declaration.md)."""
+    params = proto.params[:-1]
+
+    def _refuse(i, v):
+        q, ok = params[i], _ELEMENTS[params[i].elem]
+        if ok is not None and v.dtype not in ok:
+            raise TypeError("libavc %s: `%s` is declared `%s`, got a %s tensor" % (proto.name, q.name, q.decl, v.dtype))
+        raise ValueError("libavc %s: `%s` (`%s`) needs a contiguous device tensor, got a %s tensor on %s with strides %s"
+                         % (proto.name, q.name, q.decl, v.dtype, v.device, tuple(v.stride())))
+
+    def _failed():
+        raise RuntimeError("libavc %s failed: %s" % (proto.name, load().avc_last_error().decode()))
+
+    env = {"_fn": fn, "_refuse": _refuse, "_failed": _failed, "Tensor": torch.Tensor, "_current_stream": torch.cuda.current_stream}
+    names, exprs = [], []
+    for i, q in enumerate(params):
+        a = q.name + "_"                       # (never a Python keyword, never one of the names above)
+        names.append(a)
+        if q.ctype is c_void_p:
+            env["_ok%d" % i] = _ELEMENTS[q.elem]
+            exprs.append(_POINTER.format(a=a, i=i, dtype="" if _ELEMENTS[q.elem] is None else "%s.dtype in _ok%d and " % (a, i)))
+        else:
+            exprs.append(a)
+    exprs.append("_current_stream().cuda_stream if stream is None else stream")
+    exec("def %s(%s*, stream=None):\n    if _fn(%s) != 0:\n        _failed()\n"
+         % (proto.name, "".join(n + ", " for n in names), ",\n           ".join(exprs)), env)
+    return env[proto.name]
 
 
 def lib_path():
@@ -100,30 +133,39 @@ def lib_path():
 
 
 def load():
-    global _lib
+    global _lib, ABI_VERSION
     if _lib is not None:
         return _lib
     path = lib_path()
     if not os.path.exists(path):
         raise RuntimeError("libavc.so is not built (run `python -c 'import __graft_entry__ as g; g.build()'`); "
                            "there is no CPU fallback for the HIP hot path")
+    with open(HEADER) as f:
+        protos, ABI_VERSION = parse_header(f.read())
     lib = ctypes.CDLL(path)
-    lib.avc_last_error.restype = ctypes.c_char_p
-    lib.avc_last_error.argtypes = []
-    for name, (res, args) in list(_SIGS.items()) + list(_OPTIONAL.items()):
+    for name, proto in protos.items():
         fn = getattr(lib, name)
-        fn.restype = res
-        fn.argtypes = args
+        fn.restype = proto.restype
+        fn.argtypes = proto.argtypes
     got = lib.avc_version()
     if got != ABI_VERSION:
-        raise RuntimeError("%s implements revision %d of include/avc.h, this binding expects %d: rebuild the library "
+        raise RuntimeError("%s implements revision %d of include/avc.h, this binding expects %s: rebuild the library "
                            "(python -m avatarclip_amd.build --force)" % (path, got, ABI_VERSION))
+    _launches.update((name, bind(proto, getattr(lib, name))) for name, proto in protos.items() if proto.launch)
     _lib = lib
     return lib
 
 
-def register_optional(sigs):
-    _OPTIONAL.update(sigs)
+def call(name, *args, stream=None):
+    """Launch entry point `name` with `args` in the header's order, without the trailing stream (None: torch's current stream).  A
+    non-zero status raises with avc_last_error()."""
+    if _lib is None:
+        load()
+    try:
+        launch = _launches[name]
+    except KeyError:
+        raise AttributeError("include/avc.h declares no launch entry point %s" % name) from None
+    launch(*args, stream=stream)
 
 
 def ptr(t):

@@ -49,12 +49,10 @@ def marching_cubes(u: torch.Tensor, iso: float):
     nx, ny, nz = u.shape
     n = nx * ny * nz
     assert 3 * n < 2 ** 31, "int32 vertex ids: at most ~894^3 grid points"
-    lib = L.load()
     ntri, tab, etab = _tables(u.device)
     vflag = torch.empty(3 * n, device=u.device, dtype=torch.int32)
     ccount = torch.empty(n, device=u.device, dtype=torch.int32)
-    L.check(lib.avc_mc_classify(L.ptr(u), nx, ny, nz, float(iso), L.ptr(ntri), L.ptr(vflag), L.ptr(ccount), L.stream()),
-            "avc_mc_classify")
+    L.call("avc_mc_classify", u, nx, ny, nz, float(iso), ntri, vflag, ccount)
     vinc = torch.cumsum(vflag, 0, dtype=torch.int32)
     cinc = torch.cumsum(ccount, 0, dtype=torch.int32)
     nv, nt = int(vinc[-1].item()), int(cinc[-1].item())
@@ -63,8 +61,7 @@ def marching_cubes(u: torch.Tensor, iso: float):
     verts = torch.empty(nv, 3, device=u.device, dtype=torch.float32)
     tris = torch.empty(nt, 3, device=u.device, dtype=torch.int32)
     if nv and nt:
-        L.check(lib.avc_mc_emit(L.ptr(u), nx, ny, nz, float(iso), L.ptr(vflag), L.ptr(vid), L.ptr(ccount), L.ptr(coff),
-                                L.ptr(tab), L.ptr(etab), L.ptr(verts), L.ptr(tris), L.stream()), "avc_mc_emit")
+        L.call("avc_mc_emit", u, nx, ny, nz, float(iso), vflag, vid, ccount, coff, tab, etab, verts, tris)
     return verts, tris
 
 

@@ -72,14 +72,12 @@ class _RasterFn(torch.autograd.Function):
         N, V = v_world.shape[:2]
         F2 = faces2.shape[0]
         dev = v_world.device
-        lib = L.load()
         vw, lt = v_world.detach().float().contiguous(), light2.detach().float().contiguous()
         ndc = torch.empty(N, V, 3, device=dev, dtype=torch.float32)
         image = torch.empty(N, S, S, device=dev, dtype=torch.float32)
         fidx = torch.empty(N, 2 * S, 2 * S, device=dev, dtype=torch.int32)
-        scratch = _scratch_for(dev, (N, F2, S), N * lib.avc_rasterize_scratch_bytes(F2, 2 * S))
-        _checked(lib.avc_rasterize_mesh_save(L.ptr(vw), N, V, L.ptr(faces2), F2, L.ptr(cam), width, L.ptr(lt), S, NEAR, FAR, L.ptr(ndc),
-                                             L.ptr(image), L.ptr(fidx), L.ptr(scratch), L.stream()), "avc_rasterize_mesh_save")
+        scratch = _scratch_for(dev, (N, F2, S), N * L.load().avc_rasterize_scratch_bytes(F2, 2 * S))
+        _checked("avc_rasterize_mesh_save", vw, N, V, faces2, F2, cam, width, lt, S, NEAR, FAR, ndc, image, fidx, scratch)
         ctx.save_for_backward(vw, lt, cam, faces2, vf_ptr, vf_ent, ndc, fidx)
         ctx.S, ctx.width, ctx.eps = S, width, eps
         ctx.mark_non_differentiable(ndc, fidx)
@@ -90,13 +88,11 @@ class _RasterFn(torch.autograd.Function):
         vw, lt, cam, faces2, vf_ptr, vf_ent, ndc, fidx = ctx.saved_tensors
         N, V = vw.shape[:2]
         F2 = faces2.shape[0]
-        lib = L.load()
         g = g_image.float().contiguous()
         face_grad = torch.empty(N, F2, 6, device=vw.device, dtype=torch.float32)
         grad_ndc = torch.empty(N, V, 3, device=vw.device, dtype=torch.float32)
         grad_light = torch.empty(N, F2, device=vw.device, dtype=torch.float32)
-        L.check(lib.avc_rasterize_mesh_grad(L.ptr(g), L.ptr(ndc), N, V, L.ptr(faces2), F2, L.ptr(lt), L.ptr(fidx), ctx.S, ctx.eps, L.ptr(vf_ptr),
-                                            L.ptr(vf_ent), L.ptr(face_grad), L.ptr(grad_ndc), L.ptr(grad_light), L.stream()), "avc_rasterize_mesh_grad")
+        L.call("avc_rasterize_mesh_grad", g, ndc, N, V, faces2, F2, lt, fidx, ctx.S, ctx.eps, vf_ptr, vf_ent, face_grad, grad_ndc, grad_light)
         gv = project_vjp(vw, cam, ctx.width, grad_ndc) if ctx.needs_input_grad[0] else None
         return gv, grad_light, None, None, None, None, None, None, None
 

@@ -182,11 +182,10 @@ def render_frames(vertices, triangles, colors=None, eyes=None, ats=None, up="y",
         k = min(n, N - f0)
         vk = (v[f0:f0 + k] if v.shape[0] == N else v.expand(k, -1, -1)).contiguous()
         if V:
-            L.check(lib.avc_preview_project(L.ptr(vk), k, V, L.ptr(cams_d[f0:f0 + k]), width, near, far, R, L.ptr(proj), s), "avc_preview_project")
-            L.check(lib.avc_preview_raster(L.ptr(proj), k, V, L.ptr(t) if F else None, F, R, L.ptr(scratch), s), "avc_preview_raster")
-        L.check(lib.avc_preview_shade(L.ptr(proj), L.ptr(vk) if V else None, k, V, L.ptr(t) if F else None, F, L.ptr(c), c.shape[1] if c is not None else 0,
-                                      L.ptr(lights_d[f0:f0 + k]), float(ambient), bg[0], bg[1], bg[2], GREY, S, ss, L.ptr(scratch),
-                                      L.ptr(images[f0:f0 + k]), L.ptr(ids[f0:f0 + k]) if ids is not None else None, s), "avc_preview_shade")
+            L.call("avc_preview_project", vk, k, V, cams_d[f0:f0 + k], width, near, far, R, proj, stream=s)
+            L.call("avc_preview_raster", proj, k, V, t if F else None, F, R, scratch, stream=s)
+        L.call("avc_preview_shade", proj, vk if V else None, k, V, t if F else None, F, c, c.shape[1] if c is not None else 0, lights_d[f0:f0 + k],
+               float(ambient), bg[0], bg[1], bg[2], GREY, S, ss, scratch, images[f0:f0 + k], ids[f0:f0 + k] if ids is not None else None, stream=s)
     return (images, ids) if return_face_ids else images
 
 
@@ -209,8 +208,7 @@ def skin_blend4(joints, weights, joint_mats, rest):
     out = None
     for k in range(j.shape[0]):
         o = torch.empty(T, M, 3, device=dev, dtype=torch.float32)
-        L.check(L.load().avc_skin_blend4(L.ptr(j[k].contiguous()), L.ptr(w[k].contiguous()), L.ptr(m), L.ptr(r), M, J, T, L.ptr(o), L.stream()),
-                "avc_skin_blend4")
+        L.call("avc_skin_blend4", j[k].contiguous(), w[k].contiguous(), m, r, M, J, T, o)
         out = o if out is None else out + o
     return out
 

@@ -61,7 +61,7 @@ class NeuSRenderer:
             near_c, far_c = near.reshape(R).contiguous().float(), far.reshape(R).contiguous().float()
             jit = jitter.reshape(R).contiguous().float() if perturb > 0 else None
             z = torch.empty(R, self.n_samples, device=dev, dtype=torch.float32)
-            L.check(L.load().avc_coarse_z(L.ptr(near_c), L.ptr(far_c), L.ptr(jit), R, self.n_samples, L.ptr(z), L.stream()), "avc_coarse_z")
+            L.call("avc_coarse_z", near_c, far_c, jit, R, self.n_samples, z)
         else:
             z = torch.linspace(0.0, 1.0, self.n_samples, device=dev)
             z = near + (far - near) * z[None, :]

@@ -85,21 +85,19 @@ def simplify_mesh(vertices, triangles, colors=None, voxel_divisor=256, return_ma
     voxel, origin = voxel_grid(mn.cpu().numpy(), mx.cpu().numpy(), int(voxel_divisor))
     if not voxel > 0.0:
         raise ValueError("simplify_mesh: the mesh has no extent")
-    lib, s = L.load(), L.stream()
+    s = L.stream()
     keyed = torch.empty(N, device=device, dtype=torch.int64)
-    L.check(lib.avc_rig_cell_keys(L.ptr(v), N, float(origin[0]), float(origin[1]), float(origin[2]), voxel, int(voxel_divisor), L.ptr(keyed), s),
-            "avc_rig_cell_keys")
+    L.call("avc_rig_cell_keys", v, N, float(origin[0]), float(origin[1]), float(origin[2]), voxel, int(voxel_divisor), keyed, stream=s)
     keyed = torch.sort(keyed).values                       # distinct words: a cell is a run, its vertices ascending
     first = torch.empty(N, device=device, dtype=torch.int32)
-    L.check(lib.avc_rig_cluster_heads(L.ptr(keyed), N, L.ptr(first), s), "avc_rig_cluster_heads")
+    L.call("avc_rig_cluster_heads", keyed, N, first, stream=s)
     finc = torch.cumsum(first, 0, dtype=torch.int32)
     M = int(finc[-1].item())
     rank = finc - first                                    # exclusive scan: the cell's rank by its first vertex
     v_out = torch.empty(M, 3, device=device, dtype=torch.float32)
     c_out = torch.empty(M, 3, device=device, dtype=torch.float32) if c is not None else None
     vmap = torch.empty(N, device=device, dtype=torch.int32)
-    L.check(lib.avc_rig_cluster_average(L.ptr(keyed), N, L.ptr(v), L.ptr(c), c.shape[1] if c is not None else 0, L.ptr(rank), M, L.ptr(v_out),
-                                        L.ptr(c_out), L.ptr(vmap), s), "avc_rig_cluster_average")
+    L.call("avc_rig_cluster_average", keyed, N, v, c, c.shape[1] if c is not None else 0, rank, M, v_out, c_out, vmap, stream=s)
     del keyed, first, finc, rank
     t_out = torch.empty(0, 3, device=device, dtype=torch.int32)
     if F:
@@ -108,16 +106,16 @@ def simplify_mesh(vertices, triangles, colors=None, voxel_divisor=256, return_ma
                              "voxel_divisor)" % (M, MAX_KEYED_VERTICES))
         tri = torch.empty(F, 3, device=device, dtype=torch.int32)
         key = torch.empty(F, device=device, dtype=torch.int64)
-        L.check(lib.avc_rig_tri_keys(L.ptr(t), F, N, L.ptr(vmap), M, L.ptr(tri), L.ptr(key), s), "avc_rig_tri_keys")
+        L.call("avc_rig_tri_keys", t, F, N, vmap, M, tri, key, stream=s)
         skey, order = torch.sort(key, stable=True)         # stable: among equal keys the first input occurrence leads
         tflag = torch.empty(F, device=device, dtype=torch.int32)
-        L.check(lib.avc_rig_tri_unique(L.ptr(skey), L.ptr(order.contiguous()), F, L.ptr(tflag), s), "avc_rig_tri_unique")
+        L.call("avc_rig_tri_unique", skey, order.contiguous(), F, tflag, stream=s)
         tinc = torch.cumsum(tflag, 0, dtype=torch.int32)
         n_t = int(tinc[-1].item())
         tid = tinc - tflag
         t_out = torch.empty(n_t, 3, device=device, dtype=torch.int32)
         if n_t:
-            L.check(lib.avc_rig_tri_compact(L.ptr(tri), F, L.ptr(tflag), L.ptr(tid), n_t, L.ptr(t_out), s), "avc_rig_tri_compact")
+            L.call("avc_rig_tri_compact", tri, F, tflag, tid, n_t, t_out, stream=s)
     return (v_out, t_out, c_out, vmap) if return_map else (v_out, t_out, c_out)
 
 
@@ -140,17 +138,16 @@ def skin_pack(lbs_weights, nearest, max_influences=0):
         raise ValueError("skin_pack: a template index outside [0, %d)" % K)
     if max_influences < 0:
         raise ValueError("max_influences must be >= 0")
-    dev, lib, s = w.device, L.load(), L.stream()
+    dev, s = w.device, L.stream()
     tj = torch.empty(K, NUM_JOINTS, device=dev, dtype=torch.uint8)
     tw = torch.empty(K, NUM_JOINTS, device=dev, dtype=torch.float32)
     count = torch.empty(K, device=dev, dtype=torch.int32)
-    L.check(lib.avc_skin_sort_template(L.ptr(w), K, int(max_influences), L.ptr(tj), L.ptr(tw), L.ptr(count), s), "avc_skin_sort_template")
+    L.call("avc_skin_sort_template", w, K, int(max_influences), tj, tw, count, stream=s)
     sets = (int(count[nearest.long()].max().item()) + 3) // 4
     joints = torch.empty(sets, M, 4, device=dev, dtype=torch.uint8)
     weights = torch.empty(sets, M, 4, device=dev, dtype=torch.float32)
     blend = torch.empty(NUM_JOINTS, M, device=dev, dtype=torch.float32)
-    L.check(lib.avc_skin_pack(L.ptr(w), L.ptr(tj), L.ptr(tw), K, L.ptr(nearest.contiguous()), M, sets, L.ptr(joints) if sets else None,
-                              L.ptr(weights) if sets else None, L.ptr(blend), s), "avc_skin_pack")
+    L.call("avc_skin_pack", w, tj, tw, K, nearest.contiguous(), M, sets, joints if sets else None, weights if sets else None, blend, stream=s)
     return joints, weights, blend
 
 
@@ -162,7 +159,7 @@ def rot_to_quat(rot_mats):
     q = torch.empty(r.shape[:-2] + (4,), device=r.device, dtype=torch.float32)
     n = q.numel() // 4
     if n:
-        L.check(L.load().avc_rot_to_quat(L.ptr(r), n, L.ptr(q), L.stream()), "avc_rot_to_quat")
+        L.call("avc_rot_to_quat", r, n, q)
     return q
 
 

@@ -938,7 +938,7 @@ def chess_background_fused(H, W, chess_length, sigma, device):
         return w / w.sum(dtype=np.float32)
     taps = h2d.upload(np.concatenate([k1d(5), k1d(9)]), device)
     out = torch.empty(H * W, 1, device=device, dtype=torch.float32)
-    L.check(L.load().avc_chess_background(L.ptr(out), H, W, int(chess_length), L.ptr(taps), L.stream()), "avc_chess_background")
+    L.call("avc_chess_background", out, H, W, int(chess_length), taps)
     return out
 
 

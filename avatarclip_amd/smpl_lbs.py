@@ -114,9 +114,9 @@ def pose_hip(smpl_arrays, pose, v_shaped=None):
     A = torch.empty(T, 24, 12, device=dev, dtype=torch.float32)
     # (every operand has a name that lives to the end of the function: memory a launch reads is not handed back before it is enqueued)
     pose_d, posedirs, weights = f32(pose).reshape(T, 72), f32(a["posedirs"]), f32(a["lbs_weights"])
-    lib, s = L.load(), L.stream()
-    L.check(lib.avc_smpl_joint_mats(L.ptr(pose_d), L.ptr(joints), L.ptr(parents), T, L.ptr(feat), L.ptr(A), s), "avc_smpl_joint_mats")
-    L.check(lib.avc_smpl_pose(L.ptr(vs), L.ptr(posedirs), L.ptr(weights), L.ptr(feat), L.ptr(A), V, T, L.ptr(out), s), "avc_smpl_pose")
+    s = L.stream()
+    L.call("avc_smpl_joint_mats", pose_d, joints, parents, T, feat, A, stream=s)
+    L.call("avc_smpl_pose", vs, posedirs, weights, feat, A, V, T, out, stream=s)
     return out
 
 

@@ -54,11 +54,11 @@ def _scratch_for(device, layout, need):
     return z
 
 
-def _checked(status, what):
-    """L.check; when a launch of the sequence reports an error every scratch is dropped (and refilled on its next use), so that stale keys of
+def _checked(name, *args):
+    """L.call; when a launch of the sequence reports an error every scratch is dropped (and refilled on its next use), so that stale keys of
     an interrupted render cannot leak into later priors and silhouette masks"""
     try:
-        L.check(status, what)
+        L.call(name, *args)
     except Exception:
         _scratch.clear()
         raise
@@ -124,9 +124,8 @@ class MeshPrior:
         cam = h2d.upload(camera_frame(eye, direction), dev)
         out = torch.empty((S, S, 3) if rgb_flipped else (S, S), device=dev, dtype=torch.float32)
         zbuf = _scratch_for(dev, (1, F2, S), self.lib.avc_rasterize_scratch_bytes(F2, 2 * S))
-        _checked(self.lib.avc_rasterize_mesh(L.ptr(self.v_world), self.v_world.shape[0], L.ptr(self._faces2_i32), F2, L.ptr(cam), self.width,
-                                             L.ptr(self.light2), S, self.near, self.far, L.ptr(self._ndc), L.ptr(out), int(rgb_flipped),
-                                             3 if rgb_flipped else 1, L.ptr(zbuf), L.stream()), "avc_rasterize_mesh")
+        _checked("avc_rasterize_mesh", self.v_world, self.v_world.shape[0], self._faces2_i32, F2, cam, self.width, self.light2, S, self.near,
+                 self.far, self._ndc, out, int(rgb_flipped), 3 if rgb_flipped else 1, zbuf)
         return out
 
     def __call__(self, eye, at):

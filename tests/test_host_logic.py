@@ -163,6 +163,14 @@ def test_c_abi_exports_every_declared_symbol():
         assert hasattr(lib, n), n
     lib.avc_version.restype = ctypes.c_int
     assert lib.avc_version() >= 1
+    # the binding derives itself from the same header: it binds every declared name, with one argtype per declared parameter
+    from avatarclip_amd import lib as L
+    hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "avc.h")).read(), flags=re.S)
+    bound = L.load()
+    for n, params in re.findall(r"\b(avc_\w+)\s*\(([^)]*)\)\s*;", hdr):
+        count = 0 if params.strip() in ("", "void") else len(params.split(","))
+        assert len(getattr(bound, n).argtypes) == count, n
+    assert len(re.findall(r"\b(avc_\w+)\s*\(([^)]*)\)\s*;", hdr)) == len(names)
     # the entry points of the retired role-specialised backward (profiles/r04_ring_handoff.md) are gone from the library
     for n in ("avc_bwd_ring_ctl_bytes", "avc_bwd_ring_payload_bytes", "avc_bwd_ring_types", "avc_render_points_bwd_ring"):
         assert not hasattr(lib, n), n

@@ -110,15 +110,22 @@ def test_preview_wants_exactly_one_source(tmp_path):
 
 
 def test_lib_lists_the_two_entry_points_with_the_headers_argument_counts():
+    from ctypes import c_int, c_void_p as P
     from avatarclip_amd import build, lib
-    hdr = open(os.path.join(ROOT, "include", "avc.h")).read()
-    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
+    raw = open(os.path.join(ROOT, "include", "avc.h")).read()
+    hdr = re.sub(r"/\*.*?\*/", "", raw, flags=re.S)
+    protos, _ = lib.parse_header(raw)
+    bound = lib.load()
+    want = {"avc_smpl_joint_mats": [P, P, P, c_int, P, P, P],
+            "avc_smpl_pose": [P, P, P, P, P, c_int, c_int, P, P]}
     for name in ("avc_smpl_joint_mats", "avc_smpl_pose"):
         m = re.search(r"\bint\s+%s\s*\(([^)]*)\)\s*;" % name, hdr)
         assert m, "%s is not declared in include/avc.h" % name
-        assert name in lib._SIGS
-        res, args = lib._SIGS[name]
+        assert name in protos
+        res, args = protos[name].restype, protos[name].argtypes
         assert res is lib.c_int and len(args) == len(m.group(1).split(",")), name
-        assert args[-1] is lib.P                                        # the stream
+        assert args[-1] is P                                            # the stream
+        assert args == want[name], name
+        assert getattr(bound, name).restype is c_int and list(getattr(bound, name).argtypes) == want[name], name
     assert "avc_smpl.hip" in build.SOURCES and os.path.exists(os.path.join(build.CSRC, "avc_smpl.hip"))
     assert lib.ABI_VERSION == 4 and re.search(r"#define\s+AVC_ABI_VERSION\s+4\b", hdr)
