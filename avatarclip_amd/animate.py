@@ -22,6 +22,10 @@ confs/base.conf) differentiate the CLIP score with respect to the POSE through t
 approximate gradient of Kato, Ushiku and Harada (CVPR 2018), restated and unpinned (mesh_render.py, csrc/avc_raster_grad.hip).
 `AnimateContext(renderer_gradient=True)` (CLI: --renderer_gradient) makes the default render differentiable and lets them run; without it they
 raise NotImplementedError as before, and a user-supplied `render_fn` combined with the switch is taken to be differentiable.
+
+The posing on HIP is OPT-IN as well: `AnimateContext(posing="hip")` (CLI: --hip_posing) poses every body, scored or optimised, with
+`smpl_lbs.pose_hip_grad` (two launches forward, three backward: csrc/avc_smpl.hip, csrc/avc_smpl_grad.hip) instead of `smpl_lbs.lbs` and
+autograd.  The two agree to fp32 rounding, not bit for bit; the pinned scores of tests/golden/animate*.npz belong to the default, "torch".
 """
 import math
 import os
@@ -109,9 +113,16 @@ class AnimateContext:
                     (None: the HIP rasteriser below; the reference textures the body with data/smpl_uv.obj, which its repository does not hold)
       renderer_gradient False (default): render_fn's images carry no gradient and the generators that need one refuse to run; True: the default
                     render_fn is the differentiable HIP path (mesh_render.render_grey_batch), a given render_fn is taken to be differentiable
+      posing        "torch" (default): posed_vertices is smpl_lbs.lbs, differentiated by autograd -- the arithmetic the pinned scores were
+                    taken with; "hip": smpl_lbs.pose_hip_grad, the same vertices to fp32 rounding (not bit for bit) and their gradient to the
+                    pose from csrc/avc_smpl_grad.hip
     """
+    POSINGS = ("torch", "hip")
 
-    def __init__(self, perceptor, text_feature, smpl, vposer, render_fn=None, device=None, image_size=256, renderer_gradient=False):
+    def __init__(self, perceptor, text_feature, smpl, vposer, render_fn=None, device=None, image_size=256, renderer_gradient=False, posing="torch"):
+        if posing not in self.POSINGS:
+            raise ValueError("AnimateContext: posing is \"torch\" (smpl_lbs.lbs) or \"hip\" (smpl_lbs.pose_hip_grad), got %r" % (posing,))
+        self.posing = posing
         self.perceptor, self.text_feature, self.smpl, self.vp = perceptor, text_feature, smpl, vposer
         self.device = torch.device(device) if device is not None else smpl["v_template"].device
         self.image_size = image_size
@@ -124,13 +135,16 @@ class AnimateContext:
             return self.text_feature(text).reshape(-1).float().to(self.device)
 
     def posed_vertices(self, pose):
-        """SMPL vertices of body poses [bs, 63 | 69] with the root turned by pi/2 about x (pose_generation.py:70-75)"""
+        """SMPL vertices of body poses [bs, 63 | 69] with the root turned by pi/2 about x (pose_generation.py:70-75); posing="hip": the same
+        [bs,24,3] axis-angle through smpl_lbs.pose_hip_grad (equal to fp32 rounding, not bit for bit)"""
         from . import smpl_lbs
         pose = pose_padding(pose.reshape(-1, pose.shape[-1]).float().to(self.device))
         bs = pose.shape[0]
         root = pose.new_zeros(bs, 1, 3)
         root[:, 0, 0] = math.pi / 2
         full = torch.cat([root, pose.reshape(bs, 23, 3)], dim=1)
+        if self.posing == "hip":
+            return smpl_lbs.pose_hip_grad(self.smpl, full)
         rot = smpl_lbs.batch_rodrigues(full.reshape(-1, 3)).reshape(bs, 24, 3, 3)
         s = self.smpl
         v, _ = smpl_lbs.lbs(s["v_template"][None].expand(bs, -1, -1), rot, s["posedirs"], s["J_regressor"], s["parents"], s["lbs_weights"])
@@ -566,7 +580,7 @@ def run(conf, ctx, pose_assets=None, motion_assets=None, preview=False, preview_
 
 
 def main(argv=None):
-    """python -m avatarclip_amd.animate [--renderer_gradient] [--preview] --conf confs/base.conf --clip_weights ViT-B-32.pt --bpe bpe_simple_vocab_16e6.txt.gz --smpl SMPL_NEUTRAL.pkl
+    """python -m avatarclip_amd.animate [--renderer_gradient] [--hip_posing] [--preview] --conf confs/base.conf --clip_weights ViT-B-32.pt --bpe bpe_simple_vocab_16e6.txt.gz --smpl SMPL_NEUTRAL.pkl
     --vposer data/vposer [--codebook data/codebook.pth] [--realnvp data/pose_realnvp.pth] [--motion_vae data/motion_vae.pth]
     (AvatarAnimate/main.py with the assets its constructors load named on the command line; VPoser itself comes from the `human_body_prior` package)"""
     import argparse
@@ -578,6 +592,9 @@ def main(argv=None):
     ap.add_argument("--renderer_gradient", action="store_true",
                     help="differentiate the renders (neural_renderer's approximate backward, restated): PoseOptimizer, VPoserOptimizer and "
                          "MotionOptimizer with clip_coef > 0 (the reference's confs/base.conf) need it")
+    ap.add_argument("--hip_posing", action="store_true",
+                    help="pose the body with smpl_lbs.pose_hip_grad (HIP, forward and backward) instead of smpl_lbs.lbs: equal to fp32 rounding, "
+                         "not bit for bit")
     ap.add_argument("--preview", action="store_true", help="also write candidate_<i>.png and, in motion mode, motion.gif: the SMPL body in those poses")
     ap.add_argument("--preview_size", type=int, default=512)
     for name in ("clip_weights", "bpe", "smpl", "vposer"):
@@ -596,7 +613,7 @@ def main(argv=None):
     tk = tokenizer.SimpleTokenizer(args.bpe)
     text_feature = lambda text: perceptor.encode_text(tokenizer.tokenize([text], tk))[0]
     ctx = AnimateContext(perceptor, text_feature, smpl_lbs.load_smpl_arrays(args.smpl, dev), vp.to(dev).eval(), device=dev,
-                         renderer_gradient=args.renderer_gradient)
+                         renderer_gradient=args.renderer_gradient, posing="hip" if args.hip_posing else "torch")
     with open(args.conf) as fh:
         conf = ConfigFactory.parse_string(fh.read())
     pose_assets = {"codebook_path": args.codebook} if args.codebook else ({"ckpt_path": args.realnvp} if args.realnvp else {})

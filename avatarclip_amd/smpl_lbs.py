@@ -90,8 +90,9 @@ def _check_pose_hip(smpl_arrays, pose, v_shaped):
 def pose_hip(smpl_arrays, pose, v_shaped=None):
     """SMPL vertices float32 [T,V,3] (a device tensor) of axis-angle poses [T,72] or [T,24,3], FORWARD ONLY: two HIP launches
     (csrc/avc_smpl.hip: avc_smpl_joint_mats, avc_smpl_pose) instead of lbs's hundred small kernels, no [T,V,4,4] tensor, no gradient.
-    `lbs` remains the differentiable path, and the one whose arithmetic the pinned scores were taken with (the two agree to fp32
-    rounding, not bit for bit).  v_shaped [V,3] defaults to v_template (betas = 0); the rest joints are J_regressor v_shaped, in torch.
+    pose_hip_grad is the same with a gradient to the pose; `lbs` remains the default differentiable path, and the one whose arithmetic the
+    pinned scores were taken with (the two agree to fp32 rounding, not bit for bit).  v_shaped [V,3] defaults to v_template (betas = 0); the
+    rest joints are J_regressor v_shaped, in torch.
     smpl_arrays: load_smpl_arrays' dict.  The device is the arrays' when they live on one, else the current cuda device."""
     as_t = lambda x: x if torch.is_tensor(x) else torch.as_tensor(np.asarray(x))
     pose = as_t(pose)
@@ -118,6 +119,70 @@ def pose_hip(smpl_arrays, pose, v_shaped=None):
     L.call("avc_smpl_joint_mats", pose_d, joints, parents, T, feat, A, stream=s)
     L.call("avc_smpl_pose", vs, posedirs, weights, feat, A, V, T, out, stream=s)
     return out
+
+
+class _PoseHipGrad(torch.autograd.Function):
+    """pose_hip's two launches, and csrc/avc_smpl_grad.hip's three as their backward; every operand is device float32 (int32), contiguous"""
+
+    @staticmethod
+    def forward(ctx, pose, vs, joints, parents, posedirs, weights):
+        from . import lib as L
+        T, V = pose.shape[0], vs.shape[0]
+        out = torch.empty(T, V, 3, device=pose.device, dtype=torch.float32)
+        feat = torch.empty(T, 207, device=pose.device, dtype=torch.float32)
+        A = torch.empty(T, 24, 12, device=pose.device, dtype=torch.float32)
+        if T > 0 and V > 0:
+            s = L.stream()
+            L.call("avc_smpl_joint_mats", pose, joints, parents, T, feat, A, stream=s)
+            L.call("avc_smpl_pose", vs, posedirs, weights, feat, A, V, T, out, stream=s)
+        ctx.save_for_backward(pose, vs, joints, parents, posedirs, weights, feat, A)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        from . import lib as L
+        pose, vs, joints, parents, posedirs, weights, feat, A = ctx.saved_tensors
+        T, V = pose.shape[0], vs.shape[0]
+        dpose = torch.zeros_like(pose)
+        if T > 0 and V > 0:
+            g = g.to(dtype=torch.float32).contiguous()      # autograd hands over expanded and strided gradients
+            scratch = torch.empty(L.load().avc_smpl_grad_scratch_bytes(V, T) // 4, device=pose.device, dtype=torch.float32)
+            dA = torch.empty(T, 24, 12, device=pose.device, dtype=torch.float32)
+            dfeat = torch.empty(T, 207, device=pose.device, dtype=torch.float32)
+            s = L.stream()                                  # torch's current stream, the one the caching allocator frees these buffers on
+            L.call("avc_smpl_grad_tiles", vs, posedirs, weights, feat, A, g, V, T, None, scratch, stream=s)
+            L.call("avc_smpl_grad_reduce", scratch, V, T, dA, dfeat, stream=s)
+            L.call("avc_smpl_grad_chain", pose, joints, parents, dA, dfeat, T, dpose, stream=s)
+        return dpose, None, None, None, None, None
+
+
+def pose_hip_grad(smpl_arrays, pose, v_shaped=None):
+    """pose_hip WITH a gradient to the pose: the same checks, the same two launches and the same float32 [T,V,3] bit for bit, returned from
+    an autograd.Function whose backward is csrc/avc_smpl_grad.hip (include/avc_smpl_grad.h: avc_smpl_grad_tiles, _reduce, _chain, on torch's
+    current stream) instead of the few hundred kernels autograd issues behind `lbs`.  The gradient goes to `pose` ONLY, in its own dtype and
+    on its own device (the cast and the move are ordinary torch ops outside the Function): v_shaped, the rest joints and the SMPL arrays are
+    constants, and a v_shaped that requires grad is refused.  No double backward.  The backward recomputes the blend-shaped vertices per
+    tile, so the forward saves nothing of size [T,V,..].  `lbs` remains the default of AnimateContext and the path whose arithmetic the
+    pinned scores were taken with: the two agree to fp32 rounding, forward and backward, not bit for bit."""
+    as_t = lambda x: x if torch.is_tensor(x) else torch.as_tensor(np.asarray(x))
+    pose = as_t(pose)
+    v_shaped = None if v_shaped is None else as_t(v_shaped)
+    a = dict(smpl_arrays)
+    for k in ("v_template", "posedirs", "J_regressor", "lbs_weights"):
+        if k in a:
+            a[k] = as_t(a[k])
+    T, V = _check_pose_hip(a, pose, v_shaped)
+    if v_shaped is not None and v_shaped.requires_grad:
+        raise ValueError("pose_hip_grad: v_shaped requires grad, but the gradient goes to the pose only (v_shaped, the rest joints and the "
+                         "SMPL arrays are constants); detach it, or pose with smpl_lbs.lbs")
+    dev = a["v_template"].device if a["v_template"].is_cuda else torch.device("cuda")
+    f32 = lambda x: x.detach().to(device=dev, dtype=torch.float32).contiguous()
+    vs = f32(a["v_template"] if v_shaped is None else v_shaped)
+    joints = torch.matmul(f32(a["J_regressor"]), vs).contiguous()
+    parents = torch.as_tensor(np.asarray(as_t(a["parents"]).cpu()).reshape(-1)).to(device=dev, dtype=torch.int32).contiguous()
+    pose_d = pose.to(device=dev, dtype=torch.float32).reshape(T, 72).contiguous()     # differentiable: the gradient returns the same way
+    return _PoseHipGrad.apply(pose_d, vs, joints, parents, f32(a["posedirs"]), f32(a["lbs_weights"]))
 
 
 def load_smpl_arrays(path, device="cpu"):
