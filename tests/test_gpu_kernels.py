@@ -13,6 +13,9 @@ Tolerances (fp32 oracle vs f16-MFMA forward / bf16-MFMA gradient sweeps, fp32 ac
   dense grads    relative L2 error <= 3e-2 per tensor (bf16 operands), cosine >= 0.999
   weight-gradient kernel (avc_weight_grad_all / _reduce)   exact on integer panels; on real panels n 2^-23 sum |a| |b| per element of
                  a split of n points (tests/test_gpu_wgrad.py)
+  operand panels (what avc_render_points_fwd_train / _bwd store)   per tile group max(0, |err| - u |ref|) / rms(ref) <= 3 x its measured
+                 maximum, u = 2^-11 (f16) / 2^-8 (bf16): 9e-4 .. 4.5e-2 forward, 9.6e-4 .. 1.55e-1 backward, never above 0.25; masks
+                 exact against the stored r; invariances bit for bit (tests/test_gpu_panels.py)
 """
 import numpy as np
 import pytest

@@ -1,9 +1,11 @@
-"""Numpy emulation of ONE wavefront of the HIP MLP kernels at MFMA-fragment level (fp32, no 16-bit rounding).
+"""Numpy emulation of ONE wavefront of the HIP MLP kernels at MFMA-fragment level (float64, no 16-bit rounding).
 
 It mirrors csrc/avc_mlp.h / avc_mlp_bwd.hip statement by statement -- same fragment arrays, same packed blobs,
 same table indexing -- with the documented gfx950 operand/accumulator layouts of v_mfma_f32_32x32x16.  The CPU
 test-suite uses it to prove that packing.py + the kernels' index arithmetic reproduce oracle/analytic.py before
-any GPU time is spent; the hardware layouts themselves are verified by tests/test_gpu_probe.py.
+any GPU time is spent; the hardware layouts themselves are verified by test_mfma_layout_probe (tests/test_gpu_kernels.py).
+It is also the reference of the GPU panel test: tests/test_gpu_panels.py compares every operand tile, ReLU mask and column sum
+that avc_render_points_fwd_train / avc_render_points_bwd store with what backward_wave returns (tests/panel_restatement.py).
 TEST INFRASTRUCTURE ONLY.
 """
 import numpy as np
@@ -228,8 +230,13 @@ def panel_store(panels, tile, f0, f1):
     panels[tile] = (acc[:, :8].copy(), acc[:, 8:].copy())
 
 
-def backward_wave(spec: PK.NetSpec, blob: Blob, x, d_sdf, d_n, d_rgb):
-    """mirrors mlp_bwd_kernel for one 32-point block; returns the panel dict {tile: (k0,k1)}."""
+def backward_wave(spec: PK.NetSpec, blob: Blob, x, d_sdf, d_n, d_rgb, relu_pattern=None):
+    """mirrors mlp_bwd_kernel for one 32-point block; returns the panel dict {tile: (k0,k1)} (+ "colsum", and "colsum_abs" = the same
+    sums over the points of the terms' magnitudes).
+    relu_pattern (optional): [colour ReLU layer][2 t + e] -> bool [64, 8], the > 0 pattern of r1 (/ r2) in the shape of their
+    fragments.  The colour backward then selects with it instead of with this forward's own `r > 0` -- what the kernel does with
+    the masks its forward stored; the forward itself is not touched.  With the kernel's own pattern imposed the backward is a smooth
+    function of its inputs: a ReLU sign that 16-bit pre-activations flip near zero no longer changes every downstream tile."""
     P = blob.lay.panel
     HT, HK, ST, SK, NM = spec.HT, spec.HK, spec.ST, spec.SK, spec.NMID
     sdf, n, rgb, st = forward_wave(spec, blob, x)
@@ -275,17 +282,21 @@ def backward_wave(spec: PK.NetSpec, blob: Blob, x, d_sdf, d_n, d_rgb):
     dof = np.zeros((64, 8))
     dof[:, :4] = delta_o
     panel_store(panels, P["DO"], dof, z8)
-    r_last = st["rs"][-1]
+    if relu_pattern is None:
+        on_last, on_first = [f > 0 for f in st["rs"][-1]], [f > 0 for f in st["rs"][0]]
+    else:
+        assert len(relu_pattern) == spec.NCMID + 1 and all(len(pl) == 2 * HT for pl in relu_pattern)
+        on_last, on_first = relu_pattern[-1], relu_pattern[0]
     dl = []
     for t in range(HT):
         acc = tile_gemm(blob, "OFF_CHT", 1, t, [dof])
-        dl += [np.where(r_last[2 * t] > 0, acc[:, :8], 0), np.where(r_last[2 * t + 1] > 0, acc[:, 8:], 0)]
+        dl += [np.where(on_last[2 * t], acc[:, :8], 0), np.where(on_last[2 * t + 1], acc[:, 8:], 0)]
     store_act(P["D2"] if spec.NCMID == 1 else P["D1"], dl, HT)
     if spec.NCMID == 1:
         d1 = []
         for t in range(HT):
             acc = tile_gemm(blob, "OFF_CM0T", HK, t, dl)
-            d1 += [np.where(st["rs"][0][2 * t] > 0, acc[:, :8], 0), np.where(st["rs"][0][2 * t + 1] > 0, acc[:, 8:], 0)]
+            d1 += [np.where(on_first[2 * t], acc[:, :8], 0), np.where(on_first[2 * t + 1], acc[:, 8:], 0)]
         store_act(P["D1"], d1, HT)
         dl = d1
     dfeat = []
@@ -322,9 +333,11 @@ def backward_wave(spec: PK.NetSpec, blob: Blob, x, d_sdf, d_n, d_rgb):
     # column sums over the block's points (csrc/avc_bwd_body.h: col_sums): [ST tiles][half][16 acc registers] of gbar_hs, then
     # [3 fragments][half][8 slots] of gbar_h0 -- the half-wave of lanes 32 h .. 32 h + 31 holds the 32 points
     colsum = np.zeros(lay_cs_size(spec))
+    colsum_abs = np.zeros(lay_cs_size(spec))
     for s_ in range(3):
         for h in range(2):
             colsum[ST * 32 + (s_ * 2 + h) * 8: ST * 32 + (s_ * 2 + h) * 8 + 8] = gb0[s_][32 * h:32 * h + 32].sum(0)
+            colsum_abs[ST * 32 + (s_ * 2 + h) * 8: ST * 32 + (s_ * 2 + h) * 8 + 8] = np.abs(gb0[s_][32 * h:32 * h + 32]).sum(0)
 
     def second(offw, KS, NT, gin, hfr, qfr, ptile):
         gout, ap = [], []
@@ -348,6 +361,7 @@ def backward_wave(spec: PK.NetSpec, blob: Blob, x, d_sdf, d_n, d_rgb):
         for h in range(2):
             for half_regs, fr in ((0, gbs[2 * t]), (8, gbs[2 * t + 1])):
                 colsum[(t * 2 + h) * 16 + half_regs: (t * 2 + h) * 16 + half_regs + 8] = fr[32 * h:32 * h + 32].sum(0)
+                colsum_abs[(t * 2 + h) * 16 + half_regs: (t * 2 + h) * 16 + half_regs + 8] = np.abs(fr[32 * h:32 * h + 32]).sum(0)
     # phase F
     as_ = []
     for t in range(ST):
@@ -369,6 +383,7 @@ def backward_wave(spec: PK.NetSpec, blob: Blob, x, d_sdf, d_n, d_rgb):
         am = reverse("OFF_WM1T", HK, HT, am, st["hm"][0], apm[0], P["ABM"])
     reverse("OFF_WM0T", HK, HT, am, st["h1"], ap1, P["AB1"])
     panels["colsum"] = colsum
+    panels["colsum_abs"] = colsum_abs
     return panels, (sdf, n, rgb)
 
 
