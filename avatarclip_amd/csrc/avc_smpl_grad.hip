@@ -1,18 +1,20 @@
 // The gradient of posing the SMPL body with respect to the POSE (avatarclip_amd/smpl_lbs.py pose_hip_grad): the exact adjoint of the two
-// launches of csrc/avc_smpl.hip, whose header states the forward arithmetic.  v_shaped, the rest joints and the SMPL arrays are constants.
-// Everything is fp32, every multiply-add below is ONE fused operation written as such, there is no atomic: every sum over vertices is a
-// fixed tree that depends on V only, so a frame's gradient is the same bits in every run, in every batch and at every place in a batch.
+// launches of csrc/avc_smpl.hip.  What it rebuilds of the forward (Rodrigues, the chain's rotations, the tile's staging, the pose blend
+// shapes, the blended transform) it rebuilds by calling the forward's own functions in avc_smpl.h, whose header states that arithmetic.
+// v_shaped, the rest joints and the SMPL arrays are constants.  Everything is fp32, every multiply-add below is ONE fused operation written as
+// such, there is no atomic: every sum over vertices is a fixed tree that depends on V only, so a frame's gradient is the same bits in every
+// run, in every batch and at every place in a batch.
 // Notation: g = dL/d out [T,V,3]; vp = the blend-shaped vertex (v_posed); M[t,v] = sum_j w[v,j] A[t,j] (3 x 4); j_i = the rest joints.
 //
-// 1. avc_smpl_grad_tiles: a workgroup owns SG_VT = 256 vertices x SG_FT = 8 frames, the forward's tile.
-//    a. vp is RECOMPUTED in the tile, by the forward's own loop (nothing of [T,V,..] is saved by the forward): the first of the two
-//       passes over posedirs.
+// 1. avc_smpl_grad_tiles: a workgroup owns SMPL_VT = 256 vertices x SMPL_FT = 8 frames, the forward's tile.
+//    a. vp is RECOMPUTED in the tile, by the forward's own loop, smpl_blend_shapes (nothing of [T,V,..] is saved by the forward): the
+//       first of the two passes over posedirs.
 //    b. the lane that owns a vertex takes its 24 weights into registers and lays its g beside vp in LDS.
 //    c. dA[t,j][r][q] = sum_v (w[v,j] g[t,v][r]) (vp[t,v], 1)[q]: a 24 x 256 by 256 x 12 product per frame, with lanes owning OUTPUTS.
 //       Lane (frame, joint) -- wavefront w takes frames 2 w and 2 w + 1, one per half, lanes 24..31 of a half idle -- runs over the tile's
 //       vertices in index order with 12 accumulators; g and vp are broadcast reads, the weights come from a 64-vertex chunk the owning
 //       wavefront lays out in LDS ([vertex][25]: conflict-free both ways).  A vertex past V contributes fma(0, ., acc): nothing.
-//    d. the lane that owns a vertex rebuilds M as the forward does and takes  g_vp[c] = (M[0][c] g[0] + M[1][c] g[1]) + M[2][c] g[2]
+//    d. the lane that owns a vertex rebuilds M.R by smpl_blend_transform and takes  g_vp[c] = (M[0][c] g[0] + M[1][c] g[1]) + M[2][c] g[2]
 //       (lbs's verts = M.R vp + M.t, transposed), which replaces vp in LDS.
 //       dfeat[t,k] = sum_e posedirs[k,e] g_vp[t,e], the second pass over posedirs: lane l owns elements l, l + 256, l + 512 of the tile
 //       (contiguous loads, as in the forward) and holds their g_vp for the 8 frames.  For SG_KU = 8 rows at a time a lane forms the 64
@@ -33,96 +35,58 @@
 //    s = sin a, c1 = 1 - cos a, R = I + s K + c1 K^2):
 //      ds = <G, K>;  dc1 = <G, K^2>;  dK = s G + c1 (G K^T + K^T G);  dd = (dK21 - dK12, dK02 - dK20, dK10 - dK01)
 //      da = ds cos a + dc1 sin a - (dd . r) / a^2;   dr = dd / a + da e / a.
-#include "avc_common.h"
-#include "../../include/avc_smpl_grad.h"
+#include "avc_smpl.h"
+#include "../../include/avc.h"
 
-#define SG_VT 256         // vertices per tile = threads
-#define SG_FT 8           // frames per tile
-#define SG_KU 8           // posedirs rows per butterfly (SG_KU x SG_FT = the 64 lanes of a wavefront)
+#define SG_KU 8           // posedirs rows per butterfly (SG_KU x SMPL_FT = the 64 lanes of a wavefront)
 #define SG_FS 772         // floats between two frames of a tile in LDS (768 elements + 4: consecutive frames in different banks)
 #define SG_WS 25          // floats between two vertices of the weight chunk
 #define SG_LANES 16       // frames per workgroup of the chain kernel
-#define SMPL_J 24
-#define SMPL_K 207
 #define SG_OUT (SMPL_J * 12 + SMPL_K)         // floats of a frame's partial sums: dA [24][12], then dfeat [207]
 #define SG_GROUPS ((SMPL_K + SG_KU - 1) / SG_KU)
-#define SG_MAX_FRAMES (65535 * SG_FT)         // frames one launch's grid takes
-#define SG_HEAD (SMPL_K * SG_FT + SG_FT * SMPL_J * 12)      // feat | A
+#define SG_HEAD (SMPL_K * SMPL_FT + SMPL_FT * SMPL_J * 12)      // feat | A
 
-static_assert(SG_FT == 8 && SG_KU * SG_FT == 64 && SG_VT == 256, "one butterfly value per lane; the feat tile is read as two f4 per row");
-static_assert(64 * SG_WS <= SMPL_K * SG_FT, "the weight chunk lies over the feat tile");
-static_assert(4 * SG_GROUPS * 64 <= 2 * SG_FT * SG_FS, "the wavefronts' dfeat sums lie over vp and g");
-static_assert((SG_HEAD + 2 * SG_FT * SG_FS) * 4 <= 65536 && (SMPL_K * SG_FT) % 4 == 0 && SG_HEAD % 4 == 0, "LDS");
+static_assert(SG_KU * SMPL_FT == 64 && SMPL_VT == 256, "one butterfly value per lane");
+static_assert(64 * SG_WS <= SMPL_K * SMPL_FT, "the weight chunk lies over the feat tile");
+static_assert(4 * SG_GROUPS * 64 <= 2 * SMPL_FT * SG_FS, "the wavefronts' dfeat sums lie over vp and g");
+static_assert((SG_HEAD + 2 * SMPL_FT * SG_FS) * 4 <= 65536 && (SMPL_K * SMPL_FT) % 4 == 0 && SG_HEAD % 4 == 0, "LDS");
 
 // ------------------------------------------------------------------------------------------------------------- skinning and blend shapes
 // feat / A / g / g_vp point at frame tbase of the call; T = the frames of this launch, Tall = the frames of the call (the scratch's stride)
-__global__ __launch_bounds__(SG_VT) void smpl_grad_tiles_kernel(const float* __restrict__ v_shaped, const float* __restrict__ posedirs,
-                                                                const f4* __restrict__ weights, const float* __restrict__ feat,
-                                                                const f4* __restrict__ A, const float* __restrict__ g, int V, int T, long Tall,
-                                                                long tbase, float* __restrict__ g_vp, float* __restrict__ part) {
-  __shared__ f4 s_all[(SG_HEAD + 2 * SG_FT * SG_FS) / 4];
+__global__ __launch_bounds__(SMPL_VT) void smpl_grad_tiles_kernel(const float* __restrict__ v_shaped, const float* __restrict__ posedirs,
+                                                                  const f4* __restrict__ weights, const float* __restrict__ feat,
+                                                                  const f4* __restrict__ A, const float* __restrict__ g, int V, int T, long Tall,
+                                                                  long tbase, float* __restrict__ g_vp, float* __restrict__ part) {
+  __shared__ f4 s_all[(SG_HEAD + 2 * SMPL_FT * SG_FS) / 4];
   float* const s_base = reinterpret_cast<float*>(s_all);
   f4* const s_feat = s_all;                                     // [k][frame of the tile]
-  f4* const s_A = s_all + SMPL_K * SG_FT / 4;                   // [frame][joint][row]
+  f4* const s_A = s_all + SMPL_K * SMPL_FT / 4;                 // [frame][joint][row]
   float* const s_wc = s_base;                                   // [vertex of the chunk][SG_WS]   (over feat, once a. is done)
   float* const s_vp = s_base + SG_HEAD;                         // [frame][element of the tile], frames SG_FS apart
-  float* const s_g = s_vp + SG_FT * SG_FS;                      // the same for g
+  float* const s_g = s_vp + SMPL_FT * SG_FS;                    // the same for g
   float* const s_red = s_vp;                                    // [wavefront][k][frame]          (over vp and g, once c. is done)
   const int tid = threadIdx.x;
-  const long v0 = (long)blockIdx.x * SG_VT;
-  const long t0 = (long)blockIdx.y * SG_FT;
-  const int nf = (int)min((long)SG_FT, (long)T - t0);           // frames of this tile that exist (>= 1)
+  const long v0 = (long)blockIdx.x * SMPL_VT;
+  const long t0 = (long)blockIdx.y * SMPL_FT;
+  const int nf = (int)min((long)SMPL_FT, (long)T - t0);         // frames of this tile that exist (>= 1)
   const long E = 3L * V;                                        // elements of a posedirs row
   const long e0 = 3 * v0;
 
-  {
-    float* sf = reinterpret_cast<float*>(s_feat);
-    for (int i = tid; i < SMPL_K * SG_FT; i += SG_VT) {
-      const int k = i / SG_FT, f = i - k * SG_FT;
-      sf[i] = f < nf ? feat[(t0 + f) * SMPL_K + k] : 0.f;
-    }
-    for (int i = tid; i < SG_FT * SMPL_J * 3; i += SG_VT) {
-      const int f = i / (SMPL_J * 3);
-      s_A[i] = f < nf ? A[t0 * (SMPL_J * 3) + i] : f4{0.f, 0.f, 0.f, 0.f};
-    }
-  }
+  smpl_stage_tile(feat, A, t0, nf, s_feat, s_A);
   __syncthreads();
 
   // a. vp of elements e0 + tid + 256 c, c = 0..2: the forward's loop
   bool ok[3];
   const float* pd[3];
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    const long e = e0 + tid + SG_VT * c;
-    ok[c] = e < E;
-    pd[c] = posedirs + (ok[c] ? e : 0);
-  }
+  smpl_blend_lanes(posedirs, e0, E, ok, pd);
   {
-    float acc[SG_FT][3];
-#pragma unroll
-    for (int f = 0; f < SG_FT; ++f) acc[f][0] = acc[f][1] = acc[f][2] = 0.f;
-    for (int k0 = 0; k0 < SMPL_K; k0 += 9) {
-      float p[9][3];
-#pragma unroll
-      for (int u = 0; u < 9; ++u)
-#pragma unroll
-        for (int c = 0; c < 3; ++c) p[u][c] = ok[c] ? pd[c][(k0 + u) * E] : 0.f;
-#pragma unroll
-      for (int u = 0; u < 9; ++u) {
-        const f4 fa = s_feat[2 * (k0 + u)], fb = s_feat[2 * (k0 + u) + 1];
-#pragma unroll
-        for (int f = 0; f < SG_FT; ++f) {
-          const float x = f < 4 ? fa[f & 3] : fb[f & 3];
-#pragma unroll
-          for (int c = 0; c < 3; ++c) acc[f][c] = __builtin_fmaf(x, p[u][c], acc[f][c]);
-        }
-      }
-    }
+    float acc[SMPL_FT][3];
+    smpl_blend_shapes(ok, pd, E, s_feat, acc);
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
-      const float vs = ok[c] ? v_shaped[e0 + tid + SG_VT * c] : 0.f;
+      const float vs = ok[c] ? v_shaped[e0 + tid + SMPL_VT * c] : 0.f;
 #pragma unroll
-      for (int f = 0; f < SG_FT; ++f) s_vp[f * SG_FS + tid + SG_VT * c] = acc[f][c] + vs;      // (an element past the end: 0)
+      for (int f = 0; f < SMPL_FT; ++f) s_vp[f * SG_FS + tid + SMPL_VT * c] = acc[f][c] + vs;      // (an element past the end: 0)
     }
   }
 
@@ -130,16 +94,12 @@ __global__ __launch_bounds__(SG_VT) void smpl_grad_tiles_kernel(const float* __r
   const long v = v0 + tid;
   float wv[SMPL_J];
   if (v < V) {
-#pragma unroll
-    for (int q = 0; q < SMPL_J / 4; ++q) {
-      const f4 w4 = weights[v * (SMPL_J / 4) + q];
-      wv[4 * q] = w4[0]; wv[4 * q + 1] = w4[1]; wv[4 * q + 2] = w4[2]; wv[4 * q + 3] = w4[3];
-    }
+    smpl_vertex_weights(weights, v, wv);
   } else {
 #pragma unroll
     for (int j = 0; j < SMPL_J; ++j) wv[j] = 0.f;
   }
-  for (int f = 0; f < SG_FT; ++f) {
+  for (int f = 0; f < SMPL_FT; ++f) {
     const bool live = v < V && f < nf;
 #pragma unroll
     for (int r = 0; r < 3; ++r) s_g[f * SG_FS + 3 * tid + r] = live ? g[(t0 + f) * E + 3 * v + r] : 0.f;
@@ -152,7 +112,7 @@ __global__ __launch_bounds__(SG_VT) void smpl_grad_tiles_kernel(const float* __r
   float dacc[12];
 #pragma unroll
   for (int i = 0; i < 12; ++i) dacc[i] = 0.f;
-  for (int c = 0; c < SG_VT / 64; ++c) {
+  for (int c = 0; c < SMPL_VT / 64; ++c) {
     __syncthreads();                                            // vp, g (and the previous chunk's readers) are through
     if (wave == c) {
 #pragma unroll
@@ -186,36 +146,26 @@ __global__ __launch_bounds__(SG_VT) void smpl_grad_tiles_kernel(const float* __r
 
   // d. g_vp = M.R^T g with M as the forward blends it, through LDS into element order, then dfeat
 #pragma unroll 2
-  for (int f = 0; f < SG_FT; ++f) {
+  for (int f = 0; f < SMPL_FT; ++f) {
     float M[3][3];
-#pragma unroll
-    for (int r = 0; r < 3; ++r) M[r][0] = M[r][1] = M[r][2] = 0.f;
-#pragma unroll
-    for (int j = 0; j < SMPL_J; ++j) {
-#pragma unroll
-      for (int r = 0; r < 3; ++r) {
-        const f4 a = s_A[(f * SMPL_J + j) * 3 + r];
-#pragma unroll
-        for (int q = 0; q < 3; ++q) M[r][q] = __builtin_fmaf(wv[j], a[q], M[r][q]);
-      }
-    }
+    smpl_blend_transform(s_A, f, wv, M);
     const float* gp = s_g + f * SG_FS + 3 * tid;               // only this lane reads or writes these three of g and of vp
     const float g0 = gp[0], g1 = gp[1], g2 = gp[2];
 #pragma unroll
     for (int c = 0; c < 3; ++c) s_vp[f * SG_FS + 3 * tid + c] = __builtin_fmaf(M[2][c], g2, __builtin_fmaf(M[1][c], g1, M[0][c] * g0));
   }
   __syncthreads();
-  float gv[SG_FT][3];
+  float gv[SMPL_FT][3];
 #pragma unroll
-  for (int f = 0; f < SG_FT; ++f)
+  for (int f = 0; f < SMPL_FT; ++f)
 #pragma unroll
-    for (int c = 0; c < 3; ++c) gv[f][c] = s_vp[f * SG_FS + tid + SG_VT * c];
+    for (int c = 0; c < 3; ++c) gv[f][c] = s_vp[f * SG_FS + tid + SMPL_VT * c];
   if (g_vp) {
     for (int f = 0; f < nf; ++f) {
       float* o = g_vp + (t0 + f) * E + e0;
 #pragma unroll
       for (int c = 0; c < 3; ++c)
-        if (ok[c]) o[tid + SG_VT * c] = gv[f][c];
+        if (ok[c]) o[tid + SMPL_VT * c] = gv[f][c];
     }
   }
   __syncthreads();                                              // s_red lies over what was just read
@@ -226,12 +176,12 @@ __global__ __launch_bounds__(SG_VT) void smpl_grad_tiles_kernel(const float* __r
     for (int u = 0; u < SG_KU; ++u)
 #pragma unroll
       for (int c = 0; c < 3; ++c) p[u][c] = (ok[c] && k0 + u < SMPL_K) ? pd[c][(k0 + u) * E] : 0.f;
-    float val[SG_KU * SG_FT];
+    float val[SG_KU * SMPL_FT];
 #pragma unroll
     for (int u = 0; u < SG_KU; ++u)
 #pragma unroll
-      for (int f = 0; f < SG_FT; ++f)
-        val[u * SG_FT + f] = __builtin_fmaf(p[u][2], gv[f][2], __builtin_fmaf(p[u][1], gv[f][1], p[u][0] * gv[f][0]));
+      for (int f = 0; f < SMPL_FT; ++f)
+        val[u * SMPL_FT + f] = __builtin_fmaf(p[u][2], gv[f][2], __builtin_fmaf(p[u][1], gv[f][1], p[u][0] * gv[f][0]));
 #pragma unroll
     for (int s = 32; s >= 1; s >>= 1) {
       const bool up = (lane & s) != 0;
@@ -245,8 +195,8 @@ __global__ __launch_bounds__(SG_VT) void smpl_grad_tiles_kernel(const float* __r
     s_red[(wave * SG_GROUPS + grp) * 64 + lane] = val[0];        // value lane = 8 (k - k0) + frame: [wavefront][k][frame]
   }
   __syncthreads();
-  for (int i = tid; i < SMPL_K * SG_FT; i += SG_VT) {
-    const int k = i / SG_FT, f = i - k * SG_FT;
+  for (int i = tid; i < SMPL_K * SMPL_FT; i += SMPL_VT) {
+    const int k = i / SMPL_FT, f = i - k * SMPL_FT;
     if (f < nf) {
       const float sum = ((s_red[i] + s_red[SG_GROUPS * 64 + i]) + s_red[2 * SG_GROUPS * 64 + i]) + s_red[3 * SG_GROUPS * 64 + i];
       part[((long)blockIdx.x * Tall + tbase + t0 + f) * SG_OUT + SMPL_J * 12 + k] = sum;
@@ -254,11 +204,9 @@ __global__ __launch_bounds__(SG_VT) void smpl_grad_tiles_kernel(const float* __r
   }
 }
 
-static inline long sg_tiles(int V) { return ((long)V + SG_VT - 1) / SG_VT; }
-
 extern "C" long avc_smpl_grad_scratch_bytes(int V, int T) {
   if (V <= 0 || T <= 0) return 0;
-  return sg_tiles(V) * (long)T * SG_OUT * (long)sizeof(float);
+  return smpl_vertex_tiles(V) * (long)T * SG_OUT * (long)sizeof(float);
 }
 
 extern "C" int avc_smpl_grad_tiles(const float* v_shaped, const float* posedirs, const float* weights, const float* feat, const float* A,
@@ -272,13 +220,11 @@ extern "C" int avc_smpl_grad_tiles(const float* v_shaped, const float* posedirs,
     avc_set_error("avc_smpl_grad_tiles: weights / A not 16-byte or v_shaped / posedirs / feat / g / g_vp / scratch not 4-byte aligned");
     return 1;
   }
-  const unsigned gx = (unsigned)sg_tiles(V);
-  for (long t0 = 0; t0 < T; t0 += SG_MAX_FRAMES) {              // a launch's grid takes 65535 frame tiles
-    const int n = (int)min((long)SG_MAX_FRAMES, (long)T - t0);
-    hipLaunchKernelGGL(smpl_grad_tiles_kernel, dim3(gx, (unsigned)((n + SG_FT - 1) / SG_FT)), dim3(SG_VT), 0, (hipStream_t)stream, v_shaped,
-                       posedirs, (const f4*)weights, feat + t0 * SMPL_K, (const f4*)(A + t0 * (SMPL_J * 12)), g + t0 * 3L * V, V, n, (long)T, t0,
+  smpl_split_frames(V, T, [&](dim3 grid, long t0, int n) {
+    hipLaunchKernelGGL(smpl_grad_tiles_kernel, grid, dim3(SMPL_VT), 0, (hipStream_t)stream, v_shaped, posedirs, (const f4*)weights,
+                       feat + t0 * SMPL_K, (const f4*)(A + t0 * (SMPL_J * 12)), g + t0 * 3L * V, V, n, (long)T, t0,
                        g_vp ? g_vp + t0 * 3L * V : (float*)nullptr, scratch);
-  }
+  });
   return avc_check_launch("avc_smpl_grad_tiles");
 }
 
@@ -302,36 +248,13 @@ extern "C" int avc_smpl_grad_reduce(const float* scratch, int V, int T, float* d
     avc_set_error("avc_smpl_grad_reduce: dA not 16-byte or scratch / dfeat not 4-byte aligned");
     return 1;
   }
-  hipLaunchKernelGGL(smpl_grad_reduce_kernel, dim3((unsigned)T), dim3(256), 0, (hipStream_t)stream, scratch, (int)sg_tiles(V), (long)T, dA, dfeat);
+  hipLaunchKernelGGL(smpl_grad_reduce_kernel, dim3((unsigned)T), dim3(256), 0, (hipStream_t)stream, scratch, (int)smpl_vertex_tiles(V), (long)T, dA, dfeat);
   return avc_check_launch("avc_smpl_grad_reduce");
 }
 
 // ------------------------------------------------------------------------------------------------------------- joint chain and Rodrigues
-struct SgRot {
-  float K[3][3], R[3][3];
-  float angle, s, c, c1;
-};
-// batch_rodrigues in the forward's own operations
-__device__ __forceinline__ void sg_rodrigues(float rx, float ry, float rz, SgRot& o) {
-  const float ex = rx + 1e-8f, ey = ry + 1e-8f, ez = rz + 1e-8f;
-  o.angle = __builtin_sqrtf(__builtin_fmaf(ez, ez, __builtin_fmaf(ey, ey, ex * ex)));
-  const float dx = rx / o.angle, dy = ry / o.angle, dz = rz / o.angle;
-  o.s = sinf(o.angle);
-  o.c = cosf(o.angle);
-  o.c1 = 1.f - o.c;
-  o.K[0][0] = 0.f; o.K[0][1] = -dz; o.K[0][2] = dy;
-  o.K[1][0] = dz;  o.K[1][1] = 0.f; o.K[1][2] = -dx;
-  o.K[2][0] = -dy; o.K[2][1] = dx;  o.K[2][2] = 0.f;
-#pragma unroll
-  for (int a = 0; a < 3; ++a)
-#pragma unroll
-    for (int b = 0; b < 3; ++b) {
-      const float k2 = __builtin_fmaf(o.K[a][2], o.K[2][b], __builtin_fmaf(o.K[a][1], o.K[1][b], o.K[a][0] * o.K[0][b]));
-      o.R[a][b] = __builtin_fmaf(o.c1, k2, __builtin_fmaf(o.s, o.K[a][b], a == b ? 1.f : 0.f));
-    }
-}
-// G = dL/dR -> dL/dr
-__device__ __forceinline__ void sg_rodrigues_adjoint(const SgRot& o, const float (&G)[3][3], float rx, float ry, float rz, float* dr) {
+// G = dL/dR -> dL/dr, o = smpl_rodrigues of r
+__device__ __forceinline__ void sg_rodrigues_adjoint(const SmplRot& o, const float (&G)[3][3], float rx, float ry, float rz, float* dr) {
   float ds = 0.f, dc1 = 0.f, dK[3][3];
 #pragma unroll
   for (int a = 0; a < 3; ++a)
@@ -371,25 +294,10 @@ __global__ __launch_bounds__(SG_LANES) void smpl_grad_chain_kernel(const float* 
   float* wd = s_d + lane;
   // the forward chain (rotations only) and the seeds of dW
   for (int i = 0; i < SMPL_J; ++i) {
-    SgRot o;
-    sg_rodrigues(r[3 * i], r[3 * i + 1], r[3 * i + 2], o);
-    const int p = s_p[i];
+    SmplRot o;
+    smpl_rodrigues(r[3 * i], r[3 * i + 1], r[3 * i + 2], o);
     float W[3][3];
-    if (i == 0) {
-#pragma unroll
-      for (int a = 0; a < 3; ++a) { W[a][0] = o.R[a][0]; W[a][1] = o.R[a][1]; W[a][2] = o.R[a][2]; }
-    } else if ((unsigned)p < (unsigned)i) {
-      const float* pw = wr + 9 * p * SG_LANES;
-#pragma unroll
-      for (int a = 0; a < 3; ++a) {
-        const float p0 = pw[(3 * a) * SG_LANES], p1 = pw[(3 * a + 1) * SG_LANES], p2 = pw[(3 * a + 2) * SG_LANES];
-#pragma unroll
-        for (int b = 0; b < 3; ++b) W[a][b] = __builtin_fmaf(p2, o.R[2][b], __builtin_fmaf(p1, o.R[1][b], p0 * o.R[0][b]));
-      }
-    } else {                                                    // (the caller checks the tree: a parent that does not come first reads nothing)
-#pragma unroll
-      for (int a = 0; a < 3; ++a) W[a][0] = W[a][1] = W[a][2] = __uint_as_float(0x7FC00000u);
-    }
+    smpl_world_rot<SG_LANES, 3>(wr, i, s_p[i], o.R, W);
     const float jx = s_j[3 * i], jy = s_j[3 * i + 1], jz = s_j[3 * i + 2];
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
@@ -405,8 +313,8 @@ __global__ __launch_bounds__(SG_LANES) void smpl_grad_chain_kernel(const float* 
   // back along the chain
   for (int i = SMPL_J - 1; i >= 0; --i) {
     const float rx = r[3 * i], ry = r[3 * i + 1], rz = r[3 * i + 2];
-    SgRot o;
-    sg_rodrigues(rx, ry, rz, o);
+    SmplRot o;
+    smpl_rodrigues(rx, ry, rz, o);
     float D[3][4], G[3][3];
 #pragma unroll
     for (int a = 0; a < 3; ++a)

@@ -1,7 +1,6 @@
 """ctypes binding of libavc.so.  include/avc.h is the one declaration of the C ABI: load() parses it and derives every
 restype / argtypes from it, and call() checks each tensor against the element type the header gives its parameter.  No
-fallback: if the library is missing or a call fails, an exception is raised.  include/avc_smpl_grad.h (the posing gradient) is a
-second header in the same style, parsed after avc.h and bound into the same table; it has no revision number of its own."""
+fallback: if the library is missing, lacks a symbol the header declares, or a call fails, an exception is raised."""
 import collections
 import ctypes
 import os
@@ -14,7 +13,7 @@ from . import build as _build
 _lib = None
 _launches = {}           # name -> the launcher bind() made, one per launch entry point (filled by load())
 ABI_VERSION = None       # AVC_ABI_VERSION of include/avc.h (set by load())
-HEADER, SMPL_GRAD_HEADER = (os.path.normpath(os.path.join(_build.CSRC, h)) for h in _build.HEADERS[-2:])
+HEADER = os.path.normpath(os.path.join(_build.CSRC, _build.ABI_HEADER))
 
 c_int, c_long, c_float, c_double, c_void_p, c_char_p = (ctypes.c_int, ctypes.c_long, ctypes.c_float, ctypes.c_double,
                                                         ctypes.c_void_p, ctypes.c_char_p)
@@ -143,25 +142,18 @@ def load():
                            "there is no CPU fallback for the HIP hot path")
     with open(HEADER) as f:
         protos, ABI_VERSION = parse_header(f.read())
-    with open(SMPL_GRAD_HEADER) as f:
-        more = parse_header(f.read())[0]
     lib = ctypes.CDLL(path)
-    for name, proto in protos.items():
-        fn = getattr(lib, name)
-        fn.restype = proto.restype
-        fn.argtypes = proto.argtypes
     got = lib.avc_version()
     if got != ABI_VERSION:
         raise RuntimeError("%s implements revision %d of include/avc.h, this binding expects %s: rebuild the library "
                            "(python -m avatarclip_amd.build --force)" % (path, got, ABI_VERSION))
-    for name, proto in more.items():
+    for name, proto in protos.items():
         fn = getattr(lib, name, None)
-        if fn is None:                                   # a library from before the second header
+        if fn is None:                                   # an added entry point does not change the revision: a library from before it
             raise RuntimeError("%s implements revision %d of include/avc.h but lacks %s of include/%s: rebuild the library "
-                               "(python -m avatarclip_amd.build --force)" % (path, got, name, os.path.basename(SMPL_GRAD_HEADER)))
+                               "(python -m avatarclip_amd.build --force)" % (path, got, name, os.path.basename(HEADER)))
         fn.restype = proto.restype
         fn.argtypes = proto.argtypes
-    protos.update(more)
     _launches.update((name, bind(proto, getattr(lib, name))) for name, proto in protos.items() if proto.launch)
     _lib = lib
     return lib
@@ -175,7 +167,7 @@ def call(name, *args, stream=None):
     try:
         launch = _launches[name]
     except KeyError:
-        raise AttributeError("include/avc.h and include/avc_smpl_grad.h declare no launch entry point %s" % name) from None
+        raise AttributeError("include/avc.h declares no launch entry point %s" % name) from None
     launch(*args, stream=stream)
 
 

@@ -87,13 +87,15 @@ def _check_pose_hip(smpl_arrays, pose, v_shaped):
     return pose.shape[0], V
 
 
-def pose_hip(smpl_arrays, pose, v_shaped=None):
-    """SMPL vertices float32 [T,V,3] (a device tensor) of axis-angle poses [T,72] or [T,24,3], FORWARD ONLY: two HIP launches
-    (csrc/avc_smpl.hip: avc_smpl_joint_mats, avc_smpl_pose) instead of lbs's hundred small kernels, no [T,V,4,4] tensor, no gradient.
-    pose_hip_grad is the same with a gradient to the pose; `lbs` remains the default differentiable path, and the one whose arithmetic the
-    pinned scores were taken with (the two agree to fp32 rounding, not bit for bit).  v_shaped [V,3] defaults to v_template (betas = 0); the
-    rest joints are J_regressor v_shaped, in torch.
-    smpl_arrays: load_smpl_arrays' dict.  The device is the arrays' when they live on one, else the current cuda device."""
+def _hip_device(v_template):
+    """the arrays' device when they live on one, else the current cuda device"""
+    return v_template.device if v_template.is_cuda else torch.device("cuda")
+
+
+def _pose_hip_operands(smpl_arrays, pose, v_shaped, grad):
+    """What pose_hip and pose_hip_grad do before a launch, the checks first (they need no library): the operands of the launches, every one
+    a contiguous device tensor, float32 (parents int32): (pose [T,72], v_shaped, rest joints, parents, posedirs, weights).  With `grad` the
+    pose is cast and moved by ordinary differentiable torch ops, so its gradient returns the same way."""
     as_t = lambda x: x if torch.is_tensor(x) else torch.as_tensor(np.asarray(x))
     pose = as_t(pose)
     v_shaped = None if v_shaped is None else as_t(v_shaped)
@@ -102,23 +104,39 @@ def pose_hip(smpl_arrays, pose, v_shaped=None):
         if k in a:
             a[k] = as_t(a[k])
     T, V = _check_pose_hip(a, pose, v_shaped)
-    from . import lib as L                                  # (after the checks: they need no library)
-    dev = a["v_template"].device if a["v_template"].is_cuda else torch.device("cuda")
+    if grad and v_shaped is not None and v_shaped.requires_grad:
+        raise ValueError("pose_hip_grad: v_shaped requires grad, but the gradient goes to the pose only (v_shaped, the rest joints and the "
+                         "SMPL arrays are constants); detach it, or pose with smpl_lbs.lbs")
+    dev = _hip_device(a["v_template"])
     f32 = lambda x: x.detach().to(device=dev, dtype=torch.float32).contiguous()
-    out = torch.empty(T, V, 3, device=dev, dtype=torch.float32)
-    if T == 0 or V == 0:
-        return out
     vs = f32(a["v_template"] if v_shaped is None else v_shaped)
     joints = torch.matmul(f32(a["J_regressor"]), vs).contiguous()
     parents = torch.as_tensor(np.asarray(as_t(a["parents"]).cpu()).reshape(-1)).to(device=dev, dtype=torch.int32).contiguous()
-    feat = torch.empty(T, 207, device=dev, dtype=torch.float32)
-    A = torch.empty(T, 24, 12, device=dev, dtype=torch.float32)
-    # (every operand has a name that lives to the end of the function: memory a launch reads is not handed back before it is enqueued)
-    pose_d, posedirs, weights = f32(pose).reshape(T, 72), f32(a["posedirs"]), f32(a["lbs_weights"])
-    s = L.stream()
-    L.call("avc_smpl_joint_mats", pose_d, joints, parents, T, feat, A, stream=s)
-    L.call("avc_smpl_pose", vs, posedirs, weights, feat, A, V, T, out, stream=s)
-    return out
+    pose_d = (pose if grad else pose.detach()).to(device=dev, dtype=torch.float32).reshape(T, 72).contiguous()
+    return pose_d, vs, joints, parents, f32(a["posedirs"]), f32(a["lbs_weights"])
+
+
+def _pose_hip_launch(pose, vs, joints, parents, posedirs, weights):
+    """csrc/avc_smpl.hip's two launches on _pose_hip_operands' operands, into fresh (out [T,V,3], feat [T,207], A [T,24,12]); an empty batch
+    launches nothing.  (every operand is an argument, alive to the end: memory a launch reads is not handed back before it is enqueued)"""
+    from . import lib as L
+    T, V = pose.shape[0], vs.shape[0]
+    out, feat, A = (torch.empty(T, *shape, device=pose.device, dtype=torch.float32) for shape in ((V, 3), (207,), (24, 12)))
+    if T > 0 and V > 0:
+        s = L.stream()
+        L.call("avc_smpl_joint_mats", pose, joints, parents, T, feat, A, stream=s)
+        L.call("avc_smpl_pose", vs, posedirs, weights, feat, A, V, T, out, stream=s)
+    return out, feat, A
+
+
+def pose_hip(smpl_arrays, pose, v_shaped=None):
+    """SMPL vertices float32 [T,V,3] (a device tensor) of axis-angle poses [T,72] or [T,24,3], FORWARD ONLY: two HIP launches
+    (csrc/avc_smpl.hip: avc_smpl_joint_mats, avc_smpl_pose) instead of lbs's hundred small kernels, no [T,V,4,4] tensor, no gradient.
+    pose_hip_grad is the same with a gradient to the pose; `lbs` remains the default differentiable path, and the one whose arithmetic the
+    pinned scores were taken with (the two agree to fp32 rounding, not bit for bit).  v_shaped [V,3] defaults to v_template (betas = 0); the
+    rest joints are J_regressor v_shaped, in torch.
+    smpl_arrays: load_smpl_arrays' dict.  The device is the arrays' when they live on one, else the current cuda device."""
+    return _pose_hip_launch(*_pose_hip_operands(smpl_arrays, pose, v_shaped, grad=False))[0]
 
 
 class _PoseHipGrad(torch.autograd.Function):
@@ -126,15 +144,7 @@ class _PoseHipGrad(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, pose, vs, joints, parents, posedirs, weights):
-        from . import lib as L
-        T, V = pose.shape[0], vs.shape[0]
-        out = torch.empty(T, V, 3, device=pose.device, dtype=torch.float32)
-        feat = torch.empty(T, 207, device=pose.device, dtype=torch.float32)
-        A = torch.empty(T, 24, 12, device=pose.device, dtype=torch.float32)
-        if T > 0 and V > 0:
-            s = L.stream()
-            L.call("avc_smpl_joint_mats", pose, joints, parents, T, feat, A, stream=s)
-            L.call("avc_smpl_pose", vs, posedirs, weights, feat, A, V, T, out, stream=s)
+        out, feat, A = _pose_hip_launch(pose, vs, joints, parents, posedirs, weights)
         ctx.save_for_backward(pose, vs, joints, parents, posedirs, weights, feat, A)
         return out
 
@@ -159,30 +169,13 @@ class _PoseHipGrad(torch.autograd.Function):
 
 def pose_hip_grad(smpl_arrays, pose, v_shaped=None):
     """pose_hip WITH a gradient to the pose: the same checks, the same two launches and the same float32 [T,V,3] bit for bit, returned from
-    an autograd.Function whose backward is csrc/avc_smpl_grad.hip (include/avc_smpl_grad.h: avc_smpl_grad_tiles, _reduce, _chain, on torch's
+    an autograd.Function whose backward is csrc/avc_smpl_grad.hip (include/avc.h: avc_smpl_grad_tiles, _reduce, _chain, on torch's
     current stream) instead of the few hundred kernels autograd issues behind `lbs`.  The gradient goes to `pose` ONLY, in its own dtype and
     on its own device (the cast and the move are ordinary torch ops outside the Function): v_shaped, the rest joints and the SMPL arrays are
     constants, and a v_shaped that requires grad is refused.  No double backward.  The backward recomputes the blend-shaped vertices per
     tile, so the forward saves nothing of size [T,V,..].  `lbs` remains the default of AnimateContext and the path whose arithmetic the
     pinned scores were taken with: the two agree to fp32 rounding, forward and backward, not bit for bit."""
-    as_t = lambda x: x if torch.is_tensor(x) else torch.as_tensor(np.asarray(x))
-    pose = as_t(pose)
-    v_shaped = None if v_shaped is None else as_t(v_shaped)
-    a = dict(smpl_arrays)
-    for k in ("v_template", "posedirs", "J_regressor", "lbs_weights"):
-        if k in a:
-            a[k] = as_t(a[k])
-    T, V = _check_pose_hip(a, pose, v_shaped)
-    if v_shaped is not None and v_shaped.requires_grad:
-        raise ValueError("pose_hip_grad: v_shaped requires grad, but the gradient goes to the pose only (v_shaped, the rest joints and the "
-                         "SMPL arrays are constants); detach it, or pose with smpl_lbs.lbs")
-    dev = a["v_template"].device if a["v_template"].is_cuda else torch.device("cuda")
-    f32 = lambda x: x.detach().to(device=dev, dtype=torch.float32).contiguous()
-    vs = f32(a["v_template"] if v_shaped is None else v_shaped)
-    joints = torch.matmul(f32(a["J_regressor"]), vs).contiguous()
-    parents = torch.as_tensor(np.asarray(as_t(a["parents"]).cpu()).reshape(-1)).to(device=dev, dtype=torch.int32).contiguous()
-    pose_d = pose.to(device=dev, dtype=torch.float32).reshape(T, 72).contiguous()     # differentiable: the gradient returns the same way
-    return _PoseHipGrad.apply(pose_d, vs, joints, parents, f32(a["posedirs"]), f32(a["lbs_weights"]))
+    return _PoseHipGrad.apply(*_pose_hip_operands(smpl_arrays, pose, v_shaped, grad=True))
 
 
 def load_smpl_arrays(path, device="cpu"):

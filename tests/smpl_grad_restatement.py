@@ -1,5 +1,5 @@
-"""The gradient of SMPL posing with respect to the pose, restated in numpy float64 from the comments of include/avc_smpl_grad.h (and of
-include/avc.h for the forward it differentiates), not from the kernels: test infrastructure for tests/test_pose_grad_cpu.py, which checks
+"""The gradient of SMPL posing with respect to the pose, restated in numpy float64 from the comments of include/avc.h (its
+posing-gradient section, and the posing section for the forward it differentiates), not from the kernels: test infrastructure for tests/test_pose_grad_cpu.py, which checks
 it against float64 autograd of smpl_lbs.batch_rodrigues + smpl_lbs.lbs, and for tests/test_gpu_pose_grad.py, which checks every launch of
 csrc/avc_smpl_grad.hip against it.  Notation: g = dL/d out [T,V,3]; vp = the blend-shaped vertex; M[t,v] = sum_j w[v,j] A[t,j] (3 x 4)."""
 import numpy as np

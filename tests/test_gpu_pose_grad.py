@@ -1,4 +1,4 @@
-"""smpl_lbs.pose_hip_grad and the launches of csrc/avc_smpl_grad.hip (include/avc_smpl_grad.h) on the device: the forward bit for bit
+"""smpl_lbs.pose_hip_grad and the launches of csrc/avc_smpl_grad.hip (include/avc.h) on the device: the forward bit for bit
 against pose_hip, the gradient against float64 autograd of smpl_lbs's own torch functions from the same float32 inputs, every launch on its
 own against the numpy restatement (tests/smpl_grad_restatement.py), the bitwise properties, the gradients autograd really sends, and the
 switch of AnimateContext.  Stand-ins, poses and bound are test_gpu_pose_preview's: V and T sit on the edges of the 256 x 8 tile and of the

@@ -35,7 +35,7 @@ EXPECTED = {
 QUERIES = {"avc_version", "avc_num_offsets", "avc_fwd_panel_tiles", "avc_grad_panel_tiles", "avc_mask_u16_per_block", "avc_bwd_colsum_floats",
            "avc_shade_loss_blocks"}
 SIZES = {"avc_fwd_scratch_bytes_per_wave", "avc_bwd_colsum_rows", "avc_colsum_scratch_bytes", "avc_vit_workspace_bytes",
-         "avc_rasterize_scratch_bytes", "avc_preview_scratch_bytes"}
+         "avc_rasterize_scratch_bytes", "avc_preview_scratch_bytes", "avc_smpl_grad_scratch_bytes"}
 
 
 @pytest.fixture(scope="module")
@@ -46,7 +46,7 @@ def protos():
 
 def test_parser_on_the_real_header(protos):
     protos, abi = protos
-    assert abi == 4 and len(protos) == 77
+    assert abi == 4 and len(protos) == 81
     for name, (res, args, elems) in EXPECTED.items():
         p = protos[name]
         assert p.restype is res and p.argtypes == args and [q.elem for q in p.params] == elems, name

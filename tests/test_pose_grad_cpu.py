@@ -1,6 +1,6 @@
-"""The posing gradient without a device: the numpy restatement of include/avc_smpl_grad.h's rules (tests/smpl_grad_restatement.py) against
-float64 autograd of smpl_lbs.batch_rodrigues + smpl_lbs.lbs; the second header; pose_hip_grad's argument errors; AnimateContext's posing
-switch."""
+"""The posing gradient without a device: the numpy restatement of the rules of include/avc.h's posing-gradient section
+(tests/smpl_grad_restatement.py) against float64 autograd of smpl_lbs.batch_rodrigues + smpl_lbs.lbs; that section of the header and its
+binding; pose_hip_grad's argument errors; the operands the two host entry points hand the forward launches; AnimateContext's posing switch."""
 import os
 import re
 
@@ -13,7 +13,7 @@ from tests import smpl_grad_restatement as R
 from tests.test_gpu_pose_preview import _lbs64, _poses, _template
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "avc_smpl_grad.h")
+HEADER = os.path.join(ROOT, "include", "avc.h")
 LAUNCHES = ("avc_smpl_grad_tiles", "avc_smpl_grad_reduce", "avc_smpl_grad_chain")
 
 
@@ -69,34 +69,33 @@ def test_restated_intermediates_against_autograd_of_lbs():
         assert np.abs(got - want).max() <= 1e-12 * np.abs(want).max(), name
 
 
-def test_the_second_header_parses_and_is_listed():
+def test_the_posing_gradient_section_of_avc_h_parses_and_is_listed():
     from avatarclip_amd import build, lib
-    protos, abi = lib.parse_header(open(HEADER).read())
-    assert abi is None                                                  # no revision number of its own
-    assert sorted(protos) == sorted(LAUNCHES + ("avc_smpl_grad_scratch_bytes",))
-    for name, p in protos.items():
-        assert name.startswith("avc_smpl_"), name
-        if name in LAUNCHES:
-            assert p.launch and p.restype is lib.c_int and p.params[-1] == lib.Param("stream", lib.c_void_p, "void*", "void", False), name
+    raw = open(HEADER).read()
+    protos, abi = lib.parse_header(raw)
+    assert len(protos) == 81 and abi == 4                               # added entry points do not change the revision
+    assert sorted(n for n in protos if n.startswith("avc_smpl_grad")) == sorted(LAUNCHES + ("avc_smpl_grad_scratch_bytes",))
+    for name in LAUNCHES:
+        p = protos[name]
+        assert p.launch and p.restype is lib.c_int and p.params[-1] == lib.Param("stream", lib.c_void_p, "void*", "void", False), name
     q = protos["avc_smpl_grad_scratch_bytes"]
     assert not q.launch and q.restype is lib.c_long and q.argtypes == [lib.c_int, lib.c_int]
     assert [x.name for x in protos["avc_smpl_grad_tiles"].params] == ["v_shaped", "posedirs", "weights", "feat", "A", "g", "V", "T", "g_vp", "scratch", "stream"]
     assert [x.name for x in protos["avc_smpl_grad_reduce"].params] == ["scratch", "V", "T", "dA", "dfeat", "stream"]
     assert [x.name for x in protos["avc_smpl_grad_chain"].params] == ["pose", "joints", "parents", "dA", "dfeat", "T", "dpose", "stream"]
     assert protos["avc_smpl_grad_chain"].params[2].elem == "int"
-    raw = open(HEADER).read()
-    assert "AVC_ABI_VERSION" not in re.sub(r"/\*.*?\*/", "", raw, flags=re.S)
     for name in LAUNCHES:                                               # each cites the smpl_lbs lines it differentiates
         comment = raw[:raw.index("int %s(" % name)].rsplit("/*", 1)[1]
         assert re.search(r"smpl_lbs\.py:\d+", comment), name
-    first, first_abi = lib.parse_header(open(os.path.join(ROOT, "include", "avc.h")).read())
-    assert len(first) == 77 and first_abi == 4 and not set(first) & set(protos)
-    assert "avc_smpl_grad.hip" in build.SOURCES and os.path.exists(os.path.join(build.CSRC, "avc_smpl_grad.hip"))
-    assert [os.path.basename(h) for h in build.HEADERS[-2:]] == ["avc.h", "avc_smpl_grad.h"]
-    assert os.path.samefile(lib.SMPL_GRAD_HEADER, HEADER) and os.path.samefile(lib.HEADER, os.path.join(ROOT, "include", "avc.h"))
+    assert not os.path.exists(os.path.join(ROOT, "include", "avc_smpl_grad.h")) and os.listdir(os.path.join(ROOT, "include")) == ["avc.h"]
+    for src in ("avc_smpl.hip", "avc_smpl_grad.hip"):
+        assert src in build.SOURCES and os.path.exists(os.path.join(build.CSRC, src)), src
+    assert "avc_smpl.h" in build.HEADERS and build.ABI_HEADER in build.HEADERS and os.path.exists(os.path.join(build.CSRC, "avc_smpl.h"))
+    assert os.path.samefile(os.path.join(build.CSRC, build.ABI_HEADER), HEADER) and os.path.samefile(lib.HEADER, HEADER)
+    assert not hasattr(lib, "SMPL_GRAD_HEADER")
 
 
-def test_load_binds_the_second_header_and_names_a_library_that_lacks_it(monkeypatch, tmp_path):
+def test_load_binds_the_posing_gradient_and_names_a_library_that_lacks_a_symbol(monkeypatch, tmp_path):
     from avatarclip_amd import lib
     bound = lib.load()
     for name in LAUNCHES:
@@ -104,14 +103,18 @@ def test_load_binds_the_second_header_and_names_a_library_that_lacks_it(monkeypa
     assert bound.avc_smpl_grad_scratch_bytes.restype is lib.c_long
     assert bound.avc_smpl_grad_scratch_bytes(257, 9) == 2 * 9 * (24 * 12 + 207) * 4 and bound.avc_smpl_grad_scratch_bytes(0, 9) == 0
     assert bound.avc_smpl_grad_scratch_bytes(256, 1) == (24 * 12 + 207) * 4
-    # a library from before the header has every symbol of avc.h and the right revision, and none of these: the header of a later day stands in for it
-    later = tmp_path / "avc_smpl_later.h"
-    later.write_text("int avc_smpl_grad_of_a_later_day(const float* pose, int T, void* stream);\n")
+    # a library from before an entry point was added has the right revision and lacks the symbol: the header of a later day stands in for it
+    later = tmp_path / "avc.h"
+    head, tail = open(HEADER).read().rsplit("#ifdef __cplusplus", 1)    # (after the last declaration, inside the extern "C" block)
+    later.write_text(head + "int avc_smpl_grad_of_a_later_day(const float* pose, int T, void* stream);\n\n#ifdef __cplusplus" + tail)
     monkeypatch.setattr(lib, "_lib", None)
-    monkeypatch.setattr(lib, "SMPL_GRAD_HEADER", str(later))
-    with pytest.raises(RuntimeError, match="lacks avc_smpl_grad_of_a_later_day of include/avc_smpl_later.h: rebuild the library"):
+    monkeypatch.setattr(lib, "HEADER", str(later))
+    with pytest.raises(RuntimeError, match="lacks avc_smpl_grad_of_a_later_day of include/.*: rebuild the library") as e:
         lib.load()
     assert lib._lib is None
+    text = str(e.value)
+    assert lib.lib_path() in text and "revision 4" in text and "include/avc.h" in text
+    assert text.endswith("rebuild the library (python -m avatarclip_amd.build --force)")
 
 
 def test_pose_hip_grad_checks_its_arguments_before_it_loads_anything(monkeypatch):
@@ -138,6 +141,50 @@ def test_pose_hip_grad_checks_its_arguments_before_it_loads_anything(monkeypatch
         smpl_lbs.pose_hip_grad(b, pose)
     doc = smpl_lbs.pose_hip_grad.__doc__
     assert "bit for bit" in doc and "pose" in doc and "double backward" in doc.lower()
+
+
+def test_both_entry_points_hand_the_forward_launches_the_same_operands(monkeypatch):
+    """the host path has no bitwise pin on the device: with the launches recorded and the operands kept on the CPU, pose_hip issues exactly
+    the two forward launches, and pose_hip_grad hands the same two the same shapes, dtypes and values"""
+    from avatarclip_amd import lib, smpl_lbs
+    calls = []
+    monkeypatch.setattr(smpl_lbs, "_hip_device", lambda v_template: torch.device("cpu"))
+    monkeypatch.setattr(lib, "stream", lambda: 0)
+    monkeypatch.setattr(lib, "call", lambda name, *args, stream=None: calls.append((name, args, stream)))
+    a = _template(65)
+    pose = _poses()[:2].double().reshape(2, 24, 3)                      # a dtype and a shape the operands are not handed over in
+    v_shaped = a["v_template"].double() * 1.25
+    out = smpl_lbs.pose_hip(a, pose.clone().requires_grad_(True), v_shaped=v_shaped)
+    assert [c[0] for c in calls] == ["avc_smpl_joint_mats", "avc_smpl_pose"]
+    assert out.shape == (2, 65, 3) and out.dtype == torch.float32 and not out.requires_grad and out.grad_fn is None
+    leaf = pose.clone().requires_grad_(True)
+    out_g = smpl_lbs.pose_hip_grad(a, leaf, v_shaped=v_shaped)
+    assert [c[0] for c in calls[2:]] == ["avc_smpl_joint_mats", "avc_smpl_pose"]
+    assert out_g.shape == (2, 65, 3) and out_g.dtype == torch.float32 and out_g.requires_grad
+    for (name, plain, s0), (_, graded, s1) in zip(calls[:2], calls[2:]):
+        assert len(plain) == len(graded) and s0 == s1 == 0, name
+        for i, (x, y) in enumerate(zip(plain, graded)):
+            if torch.is_tensor(x):
+                assert torch.is_tensor(y) and x.shape == y.shape and x.dtype == y.dtype and x.is_contiguous() and y.is_contiguous(), (name, i)
+            else:
+                assert type(x) is type(y) is int and x == y, (name, i)
+    # the inputs of the two launches by value (their outputs are fresh, uninitialised buffers here: nothing ran)
+    (p0, j0, par0, T0, feat0, A0), (p1, j1, par1, T1, feat1, A1) = calls[0][1], calls[2][1]
+    assert T0 == 2 and p0.shape == (2, 72) and torch.equal(p0, pose.float().reshape(2, 72)) and torch.equal(p0, p1)
+    assert torch.equal(j0, j1) and torch.equal(j0, a["J_regressor"] @ v_shaped.float())
+    assert par0.dtype == torch.int32 and torch.equal(par0, par1) and par0.tolist() == [int(x) for x in a["parents"]]
+    assert feat0.shape == (2, 207) and A0.shape == (2, 24, 12)
+    for i in (0, 1, 2):                                                 # v_shaped, posedirs, weights
+        assert torch.equal(calls[1][1][i], calls[3][1][i]), i
+    assert torch.equal(calls[1][1][0], v_shaped.float()) and calls[1][1][5:7] == (65, 2) == calls[3][1][5:7]
+    assert calls[1][1][3] is feat0 and calls[1][1][4] is A0 and calls[1][1][7] is out
+    # an empty batch launches nothing, in either direction
+    del calls[:]
+    empty = torch.zeros(0, 72, requires_grad=True)
+    assert smpl_lbs.pose_hip(a, empty).shape == (0, 65, 3)
+    out_e = smpl_lbs.pose_hip_grad(a, empty)
+    out_e.sum().backward()
+    assert out_e.shape == (0, 65, 3) and empty.grad.shape == (0, 72) and calls == []
 
 
 def test_context_posing_switch(monkeypatch):
