@@ -1,5 +1,5 @@
-"""View-sharded data parallelism: one process per GPU, every rank renders its own camera view(s),
-ONE flat-bucket all-reduce of the ~400k fp32 gradients per step (1.6 MB: latency-bound on xGMI, so a single bucket
+"""View-sharded data parallelism: one process per GPU, rank r of W renders the views {r, r+W, ...} of
+a step's train.views_per_iter (default W: one each), ONE flat-bucket all-reduce of the ~400k fp32 gradients per step (1.6 MB: latency-bound on xGMI, so a single bucket
 and no overlap machinery), identical Adam step on every rank.  backend "nccl" is RCCL on ROCm; "gloo" is used by
 the CPU tests."""
 import os
@@ -174,7 +174,11 @@ class GradBucket:
     """One persistent flat fp32 buffer that backs the .grad of every trainable tensor (a single
     bucket of 400 065 floats = 1.6 MB for the full nets).  The gradients are views into the bucket, so the per-step
     collective is exactly one all-reduce on memory autograd already wrote -- no per-step cat / copy-back of 28 tensors.
-    A parameter that received no gradient this step contributes zeros (identical layout on every rank)."""
+    A parameter that received no gradient this step contributes zeros (identical layout on every rank).
+
+    A step may run several backward passes before the collective (train.views_per_iter > world): autograd accumulates them
+    where .grad points -- the bucket's view, or the tensor it put in place of it in the first pass -- and allreduce_mean
+    brings the SUM home once; a parameter without a gradient in some of the passes simply adds nothing in those."""
 
     def __init__(self, params):
         self.params = list(params)
@@ -190,19 +194,22 @@ class GradBucket:
         for p, v in zip(self.params, self.views):
             p.grad = v
 
-    def allreduce_mean(self):
+    def allreduce_mean(self, views=None):
+        """ONE all-reduce (SUM) of the flat buffer, then the mean over `views` = the backward passes that went into it on all
+        ranks together (default: one per rank, the world size).  Without a process group: the division alone."""
         world = rank_world()[1]
+        n = world if views is None else int(views)
         for p, v in zip(self.params, self.views):
             g = p.grad
             if g is None:            # optimizer.zero_grad(set_to_none=True) and no gradient this step
                 v.zero_()
-            elif g.data_ptr() != v.data_ptr():   # autograd replaced the tensor: bring it home (first step only)
+            elif g.data_ptr() != v.data_ptr():   # autograd replaced the tensor (first pass of the first step): bring the accumulated sum home
                 v.copy_(g)
             p.grad = v
         if is_on():
             dist.all_reduce(self.flat, op=dist.ReduceOp.SUM)
-            if world > 1:
-                self.flat.div_(world)
+        if n > 1 and (is_on() or views is not None):
+            self.flat.div_(n)
 
 
 def allreduce_grads(params, world=None):

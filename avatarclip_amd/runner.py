@@ -4,7 +4,8 @@ format (AvatarGen/AppearanceGen/main.py:30-632), running its per-iteration hot p
 Differences that are deliberate and documented:
   * view-sharded data parallelism (not in the reference, which is single-GPU): when torch.distributed is
     initialised every rank draws its own camera and ONE flat-bucket all-reduce (RCCL over xGMI) averages the
-    gradients before the identical Adam step (SURVEY.md §8e);
+    gradients before the identical Adam step; `train.views_per_iter = V` sets the number of views per step
+    independently of the number of ranks (rank r of W renders the views r, r + W, ... one after the other; DESIGN.md section 6);
   * the SMPL silhouette prior (smplx + neural_renderer, main.py:290-335,360) is rendered by the HIP rasteriser of
     smpl_prior.py from a posed mesh (`general.smpl_mesh`, an .obj, or `init_smpl(prior_renderer=...)`); the licensed SMPL
     pickles stay an input.  Seeded CLIP weights, seeded text embeddings, the procedural ellipsoid prior and a missing
@@ -86,7 +87,7 @@ class ScalarLog:
 
 class Runner:
     def __init__(self, conf_path, mode="train", case="CASE_NAME", is_continue=False, is_colab=False, conf=None,
-                 device=None, data_root=None, allow_standins=None):
+                 device=None, data_root=None, allow_standins=None, views_per_iter=None):
         if device is None:
             if not torch.cuda.is_available():
                 raise RuntimeError("avatarclip_amd.Runner needs an MI355X (torch.cuda) -- the hot path has no CPU fallback")
@@ -99,6 +100,15 @@ class Runner:
             with open(self.conf_path) as f:
                 self.conf = ConfigFactory.parse_string(f.read())
         self.rank, self.world = parallel.rank_world()
+        # train.views_per_iter: camera views per optimisation step over ALL ranks (default: one per rank).  The argument overrides the conf.
+        V = self.conf.get_int("train.views_per_iter", default=None) if views_per_iter is None else views_per_iter
+        self.views_per_iter = self.world if V is None else int(V)
+        if self.views_per_iter <= 0 or self.views_per_iter % self.world != 0:
+            raise ValueError("train.views_per_iter = %d must be a positive multiple of the world size %d (rank r renders the views r, r + %d, ...)"
+                             % (self.views_per_iter, self.world, self.world))
+        if mode == "train" and self.views_per_iter != self.world:
+            raise ValueError("train.views_per_iter = %d with world size %d: mode 'train' draws pixels of stored images, not camera views; "
+                             "the key applies to mode 'train_clip' only" % (self.views_per_iter, self.world))
         self.allow_standins = bool(self.conf.get_bool("general.allow_standins", default=False)
                                    if allow_standins is None else allow_standins)
         self.base_exp_dir = self.conf["general.base_exp_dir"]
@@ -157,10 +167,14 @@ class Runner:
         params_to_train = list(self.sdf_network.parameters()) + list(self.deviation_network.parameters()) + \
             list(self.color_network.parameters())
         self.params_to_train = params_to_train
+        several = self.views_per_iter != self.world     # more than one view per rank and step
         if parallel.is_on():
             parallel.broadcast_params(params_to_train)
+        if parallel.is_on() or several:
             self.seed_data_rngs()
-        self.grad_bucket = parallel.GradBucket(params_to_train) if parallel.is_on() else None
+        self._view_rngs = self._fresh_view_rngs() if several else []
+        self.last_views, self.last_view_losses = [], []      # this rank's views of the last step in render order, and their losses
+        self.grad_bucket = parallel.GradBucket(params_to_train) if parallel.is_on() or several else None
         # main.py:145; fused = the same update in ONE launch for all 28 tensors instead of a dozen multi-tensor launches
         self.optimizer = torch.optim.Adam(params_to_train, lr=self.learning_rate, fused=(self.device.type == "cuda"))
         self.renderer = NeuSRenderer(self.nerf_outside, self.sdf_network, self.deviation_network, self.color_network,
@@ -196,18 +210,46 @@ class Runner:
         reference seeds numpy / random / torch once (main.py:104-116); with that alone every rank would draw the same
         cameras, backgrounds, lights, image permutations, pixels and z-jitter and the all-reduce would average N identical
         gradients.  Rank r > 0 re-seeds its data RNGs with seed + r (rank 0 keeps the single-GPU stream); without
-        train.seed a base seed is drawn on rank 0 and broadcast."""
+        train.seed a base seed is drawn on rank 0 and broadcast (without a process group: drawn here).  With train.views_per_iter = V
+        the streams belong to the VIEWS: view j of a step draws from the streams seeded base + j, whichever rank renders it; the
+        process's own streams are those of its first view, j = rank (_fresh_view_rngs makes the others)."""
         base = self.seed
         if base is None:
             t = torch.tensor([int(np.random.randint(0, 2 ** 31 - 1))], dtype=torch.int64, device=self.device)
             parallel.broadcast_tensor(t)
             base = int(t.item())
+        self.base_seed = base
         self.data_seed = base + self.rank
         if self.rank > 0 or self.seed is None:
             np.random.seed(self.data_seed); random.seed(self.data_seed)
             torch.manual_seed(self.data_seed)
             if self.device.type == "cuda":
                 torch.cuda.manual_seed(self.data_seed)
+
+    def _data_rng_state(self):
+        """the four data streams of a view (numpy, random, torch on the host, torch on this device).  Host work only: the device
+        generator's state is a seed and an offset kept on the host, so neither direction waits for the GPU."""
+        return (np.random.get_state(), random.getstate(), torch.get_rng_state(),
+                torch.cuda.get_rng_state(self.device) if self.device.type == "cuda" else None)
+
+    def _set_data_rng_state(self, state):
+        np.random.set_state(state[0]); random.setstate(state[1]); torch.set_rng_state(state[2])
+        if state[3] is not None:
+            torch.cuda.set_rng_state(state[3], self.device)
+
+    def _fresh_view_rngs(self):
+        """stream sets of this rank's views after its first, j = rank + k * world (k >= 1): freshly seeded with base + j by the calls
+        seed_data_rngs makes, taken as states, the process's own streams put back"""
+        mine = self._data_rng_state()
+        out = []
+        for j in range(self.rank + self.world, self.views_per_iter, self.world):
+            np.random.seed(self.base_seed + j); random.seed(self.base_seed + j)
+            torch.manual_seed(self.base_seed + j)
+            if self.device.type == "cuda":
+                torch.cuda.manual_seed(self.base_seed + j)
+            out.append(self._data_rng_state())
+        self._set_data_rng_state(mine)
+        return out
 
     def _validation_hooks(self, clip_stage):
         """main.py:247-251 / 556-561: periodic images and meshes (rank 0)."""
@@ -232,14 +274,21 @@ class Runner:
         self._validation_hooks(clip_stage)
         self.update_learning_rate()
 
-    def _optimizer_step(self, loss):
-        """main.py:226-230 / 536-540: backward, one RCCL all-reduce of the flat gradient bucket (K17), the Adam step"""
+    def _zero_grad(self):
         self.optimizer.zero_grad(set_to_none=self.grad_bucket is None)
-        loss.backward()
+
+    def _reduce_and_step(self, views=None):
+        """one RCCL all-reduce of the flat gradient bucket (K17) and the mean over the step's views, the Adam step"""
         if self.grad_bucket is not None:
-            self.grad_bucket.allreduce_mean()
+            self.grad_bucket.allreduce_mean(views)
         self.optimizer.step()
         self.iter_step += 1
+
+    def _optimizer_step(self, loss):
+        """main.py:226-230 / 536-540: backward, the all-reduce, the Adam step"""
+        self._zero_grad()
+        loss.backward()
+        self._reduce_and_step()
 
     def _white_background(self):
         return torch.ones([1, 3], device=self.device)
@@ -653,20 +702,60 @@ class Runner:
         return loss, parts
 
     def train_clip_iteration(self, iter_i, camera=None):
+        """One optimisation step: this rank's views_per_iter / world views (global index j = rank, rank + world, ...; all with the same
+        iter_i, so the face camera and face prompt hold for the whole step), one after the other -- the operand panels belong to one
+        ray set, so a view's forward AND backward are enqueued before the next view is built and no autograd graph outlives its
+        view -- then one all-reduce, the mean over all views_per_iter views, one Adam step.  Every view after the rank's first draws
+        from its own streams (_fresh_view_rngs), swapped in around its clip_loss and kept for the next step; the rank's first view
+        draws from the process's streams, which are back in place when the step returns.  `camera`: one camera for the one view of a
+        rank, or a list of one camera per view."""
+        n = self.views_per_iter // self.world
+        if camera is not None and n > 1 and len(camera) != n:
+            raise ValueError("%d views per rank and step: `camera` must be a list of %d cameras" % (n, n))
         release = getattr(self.perceptor, "release_graphs", None)
-        if release is not None:
-            release()     # a graph-replayed encode_image of an earlier iteration that never reached backward (exception, probe call) does not hold its instance
-        loss, parts = self.clip_loss(iter_i, camera)
-        self._optimizer_step(loss)
-        self.last_stats = dict(loss=loss.detach(), color=parts["color"].detach(), eikonal=parts["eikonal"].detach(),
-                               cosine=parts["cosine"].detach(), rays=self.last_view.rays_o.shape[0], s_val=parts["s_val"], psnr=parts["psnr"])
+        losses, parts_of, views, mine = [], [], [], None
+        try:
+            for k in range(n):
+                if release is not None:
+                    release()     # a graph-replayed encode_image of an earlier view that never reached backward (exception, probe call) does not hold its instance
+                if k > 0:         # (host work only: generator states are host data, nothing here waits for the GPU)
+                    if mine is None:
+                        mine = self._data_rng_state()
+                    self._set_data_rng_state(self._view_rngs[k - 1])
+                try:
+                    loss, parts = self.clip_loss(iter_i, camera if camera is None or n == 1 else camera[k])
+                finally:
+                    if k > 0:
+                        self._view_rngs[k - 1] = self._data_rng_state()
+                if k == 0:
+                    self._zero_grad()
+                loss.backward()       # (draws nothing: the next view's streams replace this view's directly)
+                losses.append(loss.detach())
+                # (one view: the statistics as they always were kept; several: detached, no autograd graph outlives its view)
+                parts_of.append(parts if n == 1 else {key: None if v is None else v.detach() for key, v in parts.items()})
+                views.append(self.last_view)
+                del loss, parts
+        finally:
+            if mine is not None:      # an exception included: the process's streams are never left swapped out
+                self._set_data_rng_state(mine)
+        self._reduce_and_step(None if n == 1 else self.views_per_iter)
+        self.last_views, self.last_view_losses = views, losses
+        if n == 1:
+            loss, p = losses[0], parts_of[0]
+            parts = dict(color=p["color"].detach(), eikonal=p["eikonal"].detach(), cosine=p["cosine"].detach(), s_val=p["s_val"], psnr=p["psnr"])
+        else:                         # the means over this rank's views: one stack and one reduction for all of them
+            keys = [key for key in ("color", "eikonal", "cosine", "s_val", "psnr") if parts_of[0][key] is not None]
+            m = torch.stack([v.reshape(()) for l, p in zip(losses, parts_of) for v in [l] + [p[key] for key in keys]]).reshape(n, -1).mean(0)
+            loss, parts = m[0], dict({"psnr": None}, **{key: m[1 + i] for i, key in enumerate(keys)})
+        self.last_stats = dict(loss=loss, color=parts["color"], eikonal=parts["eikonal"], cosine=parts["cosine"],
+                               rays=sum(v.rays_o.shape[0] for v in views), s_val=parts["s_val"], psnr=parts["psnr"])
         if self.writer is not None:   # main.py:542-547
             for tag, v in (("Loss/loss", loss), ("Loss/color_loss", parts["color"]), ("Loss/eikonal_loss", parts["eikonal"]),
                            ("Loss/cosine", parts["cosine"]), ("Statistics/s_val", parts["s_val"]), ("Statistics/psnr", parts["psnr"])):
                 self.writer.add_scalar(tag, v, self.iter_step)
             if self.iter_step % self.report_freq == 0:
                 self.writer.flush()
-        return loss.detach()
+        return loss
 
     # ------------------------------------------------------------------ schedule / checkpoints (main.py:568-632)
     def get_image_perm(self):
