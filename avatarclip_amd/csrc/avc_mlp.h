@@ -8,7 +8,7 @@
 
 template <int H_, int NMID_, int NCMID_>
 struct NetT {
-  static constexpr int H = H_;          // hidden width: 256 (confs/examples) or 128 (confs/examples_small)
+  static constexpr int H = H_;          // hidden width: 256 (confs/examples), 128 (confs/examples_small) or 64
   static constexpr int NMID = NMID_;    // HxH middle SDF layers: 2 | 1
   static constexpr int NCMID = NCMID_;  // HxH middle colour layers: 1 | 0
   static constexpr int HT = H / 32;     // 32-row output tiles of an H-wide layer
@@ -16,9 +16,36 @@ struct NetT {
   static constexpr int SKIP = H - 39;   // width of the layer feeding the skip concat (fields.py:36-39)
   static constexpr int ST = (SKIP + 31) / 32;
   static constexpr int SK = 2 * ST;
+  // whole 32-row tiles, and a skip layer left after the 39 PE inputs: the narrowest shape, H = 64, has HT = 2, ST = 1, SK = 2
+  static_assert(H % 32 == 0 && SKIP > 0 && ST <= HT, "hidden width: a multiple of 32 above 39");
 };
 typedef NetT<256, 2, 1> NetFull;
 typedef NetT<128, 1, 0> NetSmall;
+typedef NetT<128, 2, 1> NetH128Deep;
+typedef NetT<256, 1, 0> NetH256Shallow;
+typedef NetT<64, 2, 1> NetH64Deep;
+typedef NetT<64, 1, 0> NetH64Shallow;
+// THE list of instantiated shapes: net id (include/avc.h: AVC_NET_*) -> type.  with_net(id, f) calls f(NetTag<N>{}) for the id's
+// shape and returns its result, or `unknown` for an id outside the list; for_each_net(f) calls f for every shape (the launchers
+// raise every instantiation's LDS limit once per device).  avatarclip_amd/packing.py: NET_IDS is the host's copy of this list
+// and scripts/gen_offsets.py writes one Off<> per entry.
+template <class N> struct NetTag { typedef N type; };
+template <typename R, typename F>
+static inline R with_net(int net, R unknown, F&& f) {
+  switch (net) {
+    case 0: return f(NetTag<NetFull>{});          // AVC_NET_FULL
+    case 1: return f(NetTag<NetSmall>{});         // AVC_NET_SMALL
+    case 2: return f(NetTag<NetH128Deep>{});      // AVC_NET_H128_DEEP
+    case 3: return f(NetTag<NetH256Shallow>{});   // AVC_NET_H256_SHALLOW
+    case 4: return f(NetTag<NetH64Deep>{});       // AVC_NET_H64_DEEP
+    case 5: return f(NetTag<NetH64Shallow>{});    // AVC_NET_H64_SHALLOW
+    default: return unknown;
+  }
+}
+template <typename F>
+static inline void for_each_net(F&& f) {
+  for (int id = 0; with_net(id, false, [&](auto tag) { f(tag); return true; }); ++id) {}
+}
 #include "avc_offsets_gen.h"
 // the launchers verify the table that came through the C ABI against the compiled-in one
 template <class N> static inline bool offsets_match(const int* offs) {
@@ -77,6 +104,9 @@ __device__ __forceinline__ Next nxt(const ST&, const void* blob, const AvcOffset
   Next n;
   n.ptr = reinterpret_cast<const char*>(blob) + (long)o.v[OFF] * 2;
   constexpr int G = ST::template group<TI::KS>();
+  // a group is 1 .. G whole tiles and fits one staging buffer, whatever the shape: thin layers (KS = 1 .. 5 at H = 64) do not get more
+  // than ST::G tiles per group, layers with fewer tiles than a group (HT = 2, ST = 1) stage exactly their tiles
+  static_assert(G >= 1 && G <= ST::G && TI::KS * 1024 * G <= ST::BUF_BYTES && TI::NT >= 1, "staging group of this layer");
   n.chunks = TI::KS * (TI::NT < G ? TI::NT : G);
   return n;
 }

@@ -40,7 +40,9 @@ __global__ __launch_bounds__(64 * BWD_WPB) void mlp_bwd_kernel(BwdArgs a) {
 }
 
 // rows x floats of the colsum buffer a launch with `max_waves` fills: one row per wavefront of the (persistent) grid
-extern "C" int avc_bwd_colsum_floats(int net) { return net == AVC_NET_FULL ? PanelLayout<NetFull>::CS_FLOATS : PanelLayout<NetSmall>::CS_FLOATS; }
+extern "C" int avc_bwd_colsum_floats(int net) {
+  return with_net<int>(net, 0, [](auto tag) -> int { return PanelLayout<typename decltype(tag)::type>::CS_FLOATS; });   // 0: an id outside the list
+}
 extern "C" long avc_bwd_colsum_rows(long npts, long max_waves) {
   const long nblk = (npts + 31) / 32;
   long ngroups = (nblk + BWD_WPB - 1) / BWD_WPB, maxg = max_waves / BWD_WPB;
@@ -57,10 +59,9 @@ extern "C" int avc_render_points_bwd(int net, const float* pts, const float* ray
                                      long max_waves, void* stream) {
   if (npts <= 0) return 0;
   if (!fpanels || !gpanels || !masks || !rgb_fwd || !colsum) { avc_set_error("avc_render_points_bwd: fpanels / gpanels / masks / rgb_fwd / colsum == NULL"); return 1; }
-  if (!(net == AVC_NET_FULL ? offsets_match<NetFull>(offs) : offsets_match<NetSmall>(offs))) {
-    avc_set_error("packed-blob offsets differ from the compiled-in table (regenerate csrc/avc_offsets_gen.h)");
-    return 1;
-  }
+  const int bad = with_net<int>(net, 2, [&](auto tag) -> int { return offsets_match<typename decltype(tag)::type>(offs) ? 0 : 1; });
+  if (bad == 1) { avc_set_error("packed-blob offsets differ from the compiled-in table (regenerate csrc/avc_offsets_gen.h)"); return 1; }
+  if (bad == 2) { avc_set_error("unknown net id"); return 1; }
   PointSrc ps{pts, rays_o, rays_d, z, S, ldz, pts ? 0 : 1, sample_dist};
   const long nblk = (npts + 31) / 32;
   long ngroups = (nblk + BWD_WPB - 1) / BWD_WPB;
@@ -69,19 +70,21 @@ extern "C" int avc_render_points_bwd(int net, const float* pts, const float* ray
   int grid = (int)(ngroups < maxg ? ngroups : maxg);
   if (grid < 1) grid = 1;
   hipStream_t s = (hipStream_t)stream;
-  const int lds_bytes = StageT<BWD_G>::LDS_BYTES + AVC_TAB_LDS_BYTES + ColSum<NetFull>::LDS_BYTES;
+  // one LDS size for every shape: the widest skip layer's column-sum slots (ST = 7 at H = 256)
+  int cs_bytes = 0;
+  for_each_net([&](auto tag) { const int b = ColSum<typename decltype(tag)::type>::LDS_BYTES; if (b > cs_bytes) cs_bytes = b; });
+  const int lds_bytes = StageT<BWD_G>::LDS_BYTES + AVC_TAB_LDS_BYTES + cs_bytes;
   if (offs[OFF_TAB_END] * 4 > AVC_TAB_LDS_BYTES) { avc_set_error("fp32 table does not fit its LDS window"); return 1; }
   static unsigned long long attr_seen = 0;
-  if (avc_first_use_on_device(attr_seen)) {
-    (void)hipFuncSetAttribute((const void*)mlp_bwd_kernel<NetFull>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-    (void)hipFuncSetAttribute((const void*)mlp_bwd_kernel<NetSmall>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-  }
+  if (avc_first_use_on_device(attr_seen))
+    for_each_net([&](auto tag) {
+      (void)hipFuncSetAttribute((const void*)mlp_bwd_kernel<typename decltype(tag)::type>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
+    });
   const BwdArgs args{ps, npts, (const b8*)wbf16, tab, d_sdf, d_normal, d_rgb, rgb_fwd, (const char*)fpanels, (char*)gpanels,
                      (const unsigned short*)masks, colsum};
-  if (net == AVC_NET_FULL)
-    hipLaunchKernelGGL((mlp_bwd_kernel<NetFull>), dim3(grid), dim3(64 * BWD_WPB), lds_bytes, s, args);
-  else if (net == AVC_NET_SMALL)
-    hipLaunchKernelGGL((mlp_bwd_kernel<NetSmall>), dim3(grid), dim3(64 * BWD_WPB), lds_bytes, s, args);
-  else { avc_set_error("unknown net id"); return 1; }
+  with_net<bool>(net, false, [&](auto tag) -> bool {
+    hipLaunchKernelGGL((mlp_bwd_kernel<typename decltype(tag)::type>), dim3(grid), dim3(64 * BWD_WPB), lds_bytes, s, args);
+    return true;
+  });
   return avc_check_launch("avc_render_points_bwd");
 }

@@ -286,18 +286,13 @@ __global__ __launch_bounds__(64 * FWD_WPB) void mlp_render_kernel(PointSrc ps, l
   }
 }
 
-extern "C" long avc_fwd_scratch_bytes_per_wave(int net) {
-  return (long)(net == AVC_NET_FULL ? ScratchLayout<NetFull>::P_TILES : ScratchLayout<NetSmall>::P_TILES) * 2048;
-}
-extern "C" int avc_fwd_panel_tiles(int net) {
-  return net == AVC_NET_FULL ? PanelLayout<NetFull>::P_TILES : PanelLayout<NetSmall>::P_TILES;
-}
-extern "C" int avc_grad_panel_tiles(int net) {
-  return net == AVC_NET_FULL ? PanelLayout<NetFull>::G_TILES : PanelLayout<NetSmall>::G_TILES;
-}
-extern "C" int avc_mask_u16_per_block(int net) {
-  return net == AVC_NET_FULL ? PanelLayout<NetFull>::MASK_U16 : PanelLayout<NetSmall>::MASK_U16;
-}
+// the sizes a caller allocates by; an id outside the list of shapes (avc_mlp.h: with_net) has none: 0, and the launchers refuse it
+#define AVC_NET_CONST(R, EXPR) with_net<R>(net, 0, [](auto tag) -> R { typedef typename decltype(tag)::type N; return EXPR; })
+extern "C" long avc_fwd_scratch_bytes_per_wave(int net) { return AVC_NET_CONST(long, (long)ScratchLayout<N>::P_TILES * 2048); }
+extern "C" int avc_fwd_panel_tiles(int net) { return AVC_NET_CONST(int, PanelLayout<N>::P_TILES); }
+extern "C" int avc_grad_panel_tiles(int net) { return AVC_NET_CONST(int, PanelLayout<N>::G_TILES); }
+extern "C" int avc_mask_u16_per_block(int net) { return AVC_NET_CONST(int, PanelLayout<N>::MASK_U16); }
+#undef AVC_NET_CONST
 
 static int grid_for(long npts, int waves_per_block, int max_blocks) {
   long nblk = (npts + 31) / 32;
@@ -311,34 +306,34 @@ static int check_tab(const int* offs) {
   if (offs[OFF_TAB_END] * 4 > AVC_TAB_LDS_BYTES) { avc_set_error("fp32 table does not fit its LDS window"); return 1; }
   return 0;
 }
+// 0 = the table that came through the C ABI is the compiled-in one of shape `net`
+static int check_offsets(int net, const int* offs) {
+  const int r = with_net<int>(net, 2, [&](auto tag) -> int { return offsets_match<typename decltype(tag)::type>(offs) ? 0 : 1; });
+  if (r == 1) avc_set_error("packed-blob offsets differ from the compiled-in table (regenerate csrc/avc_offsets_gen.h)");
+  if (r == 2) avc_set_error("unknown net id");
+  return r;
+}
 
 static int launch_sdf(int net, PointSrc ps, long npts, const void* wf, const float* tab, const int* offs,
                       float* sdf_out, const int* slot, int ld_out, void* stream) {
   if (npts <= 0) return 0;
   if (check_tab(offs)) return 1;
-  if (!(net == AVC_NET_FULL ? offsets_match<NetFull>(offs) : offsets_match<NetSmall>(offs))) {
-    avc_set_error("packed-blob offsets differ from the compiled-in table (regenerate csrc/avc_offsets_gen.h)");
-    return 1;
-  }
+  if (check_offsets(net, offs)) return 1;
   hipStream_t s = (hipStream_t)stream;
   const int lds_bytes = StageT<FWD_G>::LDS_BYTES + AVC_TAB_LDS_BYTES;
   static unsigned long long attr_seen = 0;
-  if (avc_first_use_on_device(attr_seen)) {
-    hipFuncSetAttribute((const void*)mlp_sdf_kernel<NetFull>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-    hipFuncSetAttribute((const void*)mlp_sdf_kernel<NetSmall>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-  }
+  if (avc_first_use_on_device(attr_seen))
+    for_each_net([&](auto tag) {
+      (void)hipFuncSetAttribute((const void*)mlp_sdf_kernel<typename decltype(tag)::type>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
+    });
   const int wpb = SDF_WPB;   // wavefronts per workgroup
   const int grid = grid_for(npts, wpb, 0x7fffffff);
-  if (net == AVC_NET_FULL)
-    hipLaunchKernelGGL((mlp_sdf_kernel<NetFull>), dim3(grid), dim3(64 * wpb), lds_bytes, s, ps, npts, (const h8*)wf, tab,
+  const bool known = with_net<bool>(net, false, [&](auto tag) -> bool {
+    hipLaunchKernelGGL((mlp_sdf_kernel<typename decltype(tag)::type>), dim3(grid), dim3(64 * wpb), lds_bytes, s, ps, npts, (const h8*)wf, tab,
                        sdf_out, slot, ld_out);
-  else if (net == AVC_NET_SMALL)
-    hipLaunchKernelGGL((mlp_sdf_kernel<NetSmall>), dim3(grid), dim3(64 * wpb), lds_bytes, s, ps, npts, (const h8*)wf, tab,
-                       sdf_out, slot, ld_out);
-  else {
-    avc_set_error("unknown net id");
-    return 1;
-  }
+    return true;
+  });
+  if (!known) { avc_set_error("unknown net id"); return 1; }
   return avc_check_launch("avc_sdf_forward");
 }
 
@@ -354,30 +349,23 @@ static int launch_render(int net, PointSrc ps, long npts, const void* wf16, cons
                          float* normal_out, float* rgb_out, long max_waves, void* store, void* masks, void* stream,
                          const char* what) {
   if (check_tab(offs)) return 1;
-  if (!(net == AVC_NET_FULL ? offsets_match<NetFull>(offs) : offsets_match<NetSmall>(offs))) {
-    avc_set_error("packed-blob offsets differ from the compiled-in table (regenerate csrc/avc_offsets_gen.h)");
-    return 1;
-  }
+  if (check_offsets(net, offs)) return 1;
   long maxg = max_waves / FWD_WPB;
   if (maxg < 1) maxg = 1;
   const int grid = grid_for(npts, FWD_WPB, (int)(maxg < 0x7fffffff ? maxg : 0x7fffffff));
   const int lds_bytes = StageT<FWD_G>::LDS_BYTES + AVC_TAB_LDS_BYTES;
   hipStream_t s = (hipStream_t)stream;
   static unsigned long long attr_seen = 0;
-  if (avc_first_use_on_device(attr_seen)) {
-    (void)hipFuncSetAttribute((const void*)mlp_render_kernel<NetFull, TRAIN>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-    (void)hipFuncSetAttribute((const void*)mlp_render_kernel<NetSmall, TRAIN>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-  }
-  if (net == AVC_NET_FULL)
-    hipLaunchKernelGGL((mlp_render_kernel<NetFull, TRAIN>), dim3(grid), dim3(64 * FWD_WPB), lds_bytes, s, ps, npts, (const h8*)wf16, tab,
+  if (avc_first_use_on_device(attr_seen))
+    for_each_net([&](auto tag) {
+      (void)hipFuncSetAttribute((const void*)mlp_render_kernel<typename decltype(tag)::type, TRAIN>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
+    });
+  const bool known = with_net<bool>(net, false, [&](auto tag) -> bool {
+    hipLaunchKernelGGL((mlp_render_kernel<typename decltype(tag)::type, TRAIN>), dim3(grid), dim3(64 * FWD_WPB), lds_bytes, s, ps, npts, (const h8*)wf16, tab,
                        sdf_out, normal_out, rgb_out, (char*)store, (unsigned short*)masks);
-  else if (net == AVC_NET_SMALL)
-    hipLaunchKernelGGL((mlp_render_kernel<NetSmall, TRAIN>), dim3(grid), dim3(64 * FWD_WPB), lds_bytes, s, ps, npts, (const h8*)wf16, tab,
-                       sdf_out, normal_out, rgb_out, (char*)store, (unsigned short*)masks);
-  else {
-    avc_set_error("unknown net id");
-    return 1;
-  }
+    return true;
+  });
+  if (!known) { avc_set_error("unknown net id"); return 1; }
   return avc_check_launch(what);
 }
 

@@ -254,7 +254,7 @@ class Engine:
         eng = cls._by_net.get(sdf_net)
         if eng is None:
             col_conf = col_net.conf if col_net is not None else dict(
-                d_hidden=sdf_net.conf["d_hidden"], n_layers=2 if sdf_net.conf["d_hidden"] == 256 else 1,
+                d_hidden=sdf_net.conf["d_hidden"], n_layers=int(sdf_net.conf["n_layers"]) - 2,   # the colour depth that goes with the SDF depth in every supported shape (packing.SUPPORTED): 4 + 2 or 3 + 1
                 mode="no_view_dir", multires_view=0)
             spec = PK.spec_from_conf(sdf_net.conf, col_conf)
             eng = cls(spec, next(sdf_net.parameters()).device)

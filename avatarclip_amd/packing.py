@@ -109,7 +109,8 @@ class NetSpec:
 
     @property
     def net_id(self):
-        return 0 if self.H == 256 else 1
+        """the shape's id in the C ABI (include/avc.h: AVC_NET_*); only the shapes of NET_IDS have one"""
+        return NET_IDS[(self.H, self.NMID, self.NCMID)]
 
     @property
     def HT(self): return self.H // 32
@@ -129,13 +130,30 @@ class NetSpec:
 
 FULL = NetSpec(256, 2, 1)
 SMALL = NetSpec(128, 1, 0)
+# The supported shapes, in the order of their ids: d_hidden in {64, 128, 256} x depth in {SDF n_layers 4 + colour n_layers 2 (NMID 2,
+# NCMID 1), SDF 3 + colour 1 (NMID 1, NCMID 0)}.  The host's copy of the list in csrc/avc_mlp.h (with_net); scripts/gen_offsets.py
+# writes one Off<> specialisation per row under the C++ type name given here.
+SUPPORTED = (
+    (0, "NetFull", FULL),                          # AVC_NET_FULL
+    (1, "NetSmall", SMALL),                        # AVC_NET_SMALL
+    (2, "NetH128Deep", NetSpec(128, 2, 1)),        # AVC_NET_H128_DEEP
+    (3, "NetH256Shallow", NetSpec(256, 1, 0)),     # AVC_NET_H256_SHALLOW
+    (4, "NetH64Deep", NetSpec(64, 2, 1)),          # AVC_NET_H64_DEEP
+    (5, "NetH64Shallow", NetSpec(64, 1, 0)),       # AVC_NET_H64_SHALLOW
+)
+NET_IDS = {(sp.H, sp.NMID, sp.NCMID): i for i, _, sp in SUPPORTED}
+SPEC_OF_ID = {i: sp for i, _, sp in SUPPORTED}
+
+
+def supported_shapes_text() -> str:
+    return ", ".join("d_hidden %d with SDF n_layers %d + colour n_layers %d" % (sp.H, sp.NMID + 2, sp.NCMID + 1) for _, _, sp in SUPPORTED)
 
 
 def spec_from_conf(sdf_conf: dict, col_conf: dict) -> NetSpec:
     H = int(sdf_conf["d_hidden"])
     nl = int(sdf_conf["n_layers"])
     spec = NetSpec(H, nl - 2, int(col_conf["n_layers"]) - 1)
-    ok = (spec.H, spec.NMID, spec.NCMID) in ((256, 2, 1), (128, 1, 0))
+    ok = (spec.H, spec.NMID, spec.NCMID) in NET_IDS
     ok = ok and int(sdf_conf.get("multires", 0)) == 6 and list(sdf_conf.get("skip_in", [])) == [nl]
     ok = ok and int(sdf_conf["d_out"]) == H + 1 and int(col_conf["d_hidden"]) == H
     ok = ok and col_conf.get("mode") == "no_view_dir" and int(col_conf.get("multires_view", 0)) == 0
@@ -146,8 +164,9 @@ def spec_from_conf(sdf_conf: dict, col_conf: dict) -> NetSpec:
     ok = ok and int(col_conf.get("d_feature", H)) == H and bool(col_conf.get("squeeze_out", True))
     if not ok:
         raise NotImplementedError(
-            "avatarclip_amd kernels are instantiated for the two network shapes the reference ships "
-            "(confs/examples: 256-wide, confs/examples_small: 128-wide); got %r / %r" % (sdf_conf, col_conf))
+            "avatarclip_amd kernels are instantiated for six network shapes (%s; confs/examples is 256 with 4 + 2, "
+            "confs/examples_small 128 with 3 + 1), each with multires 6, skip_in [n_layers], d_out d_hidden + 1, colour mode "
+            "no_view_dir, scale 1, d_in 3 / 6 and squeeze_out; got %r / %r" % (supported_shapes_text(), sdf_conf, col_conf))
     return spec
 
 

@@ -21,6 +21,12 @@ extern "C" {
 
 #define AVC_NET_FULL 0  /* confs/examples (all 144):   SDF 39-256-256-256-217(+39)-257, colour 262-256-256-{3,3} */
 #define AVC_NET_SMALL 1 /* confs/examples_small:        SDF 39-128-128-89(+39)-129,     colour 134-128-{3,3}     */
+/* the scaled-down shapes: d_hidden in {64, 128, 256} x depth in {SDF n_layers 4 + colour n_layers 2, SDF 3 + colour 1} */
+#define AVC_NET_H128_DEEP 2    /* a full-size conf, d_hidden 128: SDF 39-128-128-128-89(+39)-129, colour 134-128-128-{3,3} */
+#define AVC_NET_H256_SHALLOW 3 /* the small conf's depth, d_hidden 256: SDF 39-256-256-217(+39)-257, colour 262-256-{3,3}  */
+#define AVC_NET_H64_DEEP 4     /* a full-size conf, d_hidden 64:  SDF 39-64-64-64-25(+39)-65,     colour 70-64-64-{3,3}    */
+#define AVC_NET_H64_SHALLOW 5  /* the small conf's depth, d_hidden 64:  SDF 39-64-64-25(+39)-65,  colour 70-64-{3,3}       */
+#define AVC_NET_COUNT 6        /* ids 0 .. AVC_NET_COUNT-1 are instantiated; every other id is refused by the launchers    */
 
 /* Interface revision of this header.  It changes whenever an existing entry point's argument list or meaning changes (2: round 5 put
  * `colsum` into avc_render_points_bwd and moved the second-order row-0 term out of the weight-gradient products; 3: the rasteriser's
