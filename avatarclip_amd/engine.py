@@ -53,27 +53,18 @@ class _DevLayout:
         return cls._cache[key]
 
 
-FUSED_PACK = os.environ.get("AVC_FUSED_PACK", "1") != "0"      # Packed / the coarse sample depths as one launch each (0: torch ops)
-
-
 class Packed:
-    """Packed parameter blobs of one optimisation step."""
+    """Packed parameter blobs of one optimisation step: one launch (csrc/avc_params.hip; tests/engine_cases.pack_statement states
+    the same gathers in torch)."""
 
     def __init__(self, dl: _DevLayout, flatP: torch.Tensor):
         self.dl = dl
-        if flatP.is_cuda and FUSED_PACK:     # one launch (csrc/avc_params.hip); below: the torch statement of the same gathers
-            f = flatP.detach().float().contiguous()
-            n16, n32 = dl.idx16.numel(), dl.idx32.numel()
-            self.w_f16 = torch.empty(n16, dtype=torch.float16, device=f.device)
-            self.w_bf16 = torch.empty(n16, dtype=torch.bfloat16, device=f.device)
-            self.tab = torch.empty(n32, dtype=torch.float32, device=f.device)
-            L.call("avc_pack_params", f, f.numel(), dl.idx16, dl.scale16, n16, dl.idx32, dl.scale32, n32, self.w_f16, self.w_bf16, self.tab)
-            return
-        pz = torch.cat([flatP.detach().float(), flatP.new_zeros(1)])
-        w = pz[dl.idx16] * dl.scale16
-        self.w_f16 = w.to(torch.float16).contiguous()
-        self.w_bf16 = w.to(torch.bfloat16).contiguous()
-        self.tab = (pz[dl.idx32] * dl.scale32).contiguous()
+        f = flatP.detach().float().contiguous()
+        n16, n32 = dl.idx16.numel(), dl.idx32.numel()
+        self.w_f16 = torch.empty(n16, dtype=torch.float16, device=f.device)
+        self.w_bf16 = torch.empty(n16, dtype=torch.bfloat16, device=f.device)
+        self.tab = torch.empty(n32, dtype=torch.float32, device=f.device)
+        L.call("avc_pack_params", f, f.numel(), dl.idx16, dl.scale16, n16, dl.idx32, dl.scale32, n32, self.w_f16, self.w_bf16, self.tab)
 
 
 def flatten_dense_torch(sdf_net, col_net, spec: PK.NetSpec) -> torch.Tensor:
@@ -194,11 +185,10 @@ class Engine:
     _by_net = weakref.WeakKeyDictionary()
     PROFILE = False               # bench.py: record (name, points, start_event, end_event) per kernel launch group
     prof_events = []
-    WG_BLOCKS_PER_SPLIT = int(os.environ.get("AVC_WG_BLOCKS_PER_SPLIT", "256"))     # split-K of the weight-gradient launch: blocks per workgroup (nsplit = blocks / this, 1..256).  A
+    WG_BLOCKS_PER_SPLIT = 256     # split-K of the weight-gradient launch: blocks per workgroup (nsplit = blocks / this, 1..256).  A
                                   # 512^2 x 64 spp slab (262144 blocks) has its 256 splits either way; smaller point sets want the finer deal -- at 224^2 (100352
                                   # blocks) 256 splits x 17 pairs instead of 98 x 17 workgroups over 256 CUs: 8.52 -> 8.08 ms (profiles/r03_ab_kernels.txt)
-    WG_MAX_SPLITS = int(os.environ.get("AVC_WG_MAX_SPLITS", "256"))   # (<= 256: the size of the split buffers)
-    FUSED_WG_TAIL = os.environ.get("AVC_FUSED_WG_TAIL", "1") != "0"    # split sums + un-packing of the dense gradient as 1 + 1 launches
+    WG_MAX_SPLITS = 256           # (<= 256: the size of the split buffers)
     MAX_FWD_WAVES = 2048          # persistent grid of avc_render_points_fwd: 256 CUs x one 8-wave workgroup
     MAX_BWD_WAVES = 2048          # 256 CUs x one 8-wave workgroup
     # Operand panels (csrc/avc_mlp.h: PanelLayout).  F region: 89 tiles = 5.6 KiB per point (full nets), written by the training
@@ -214,8 +204,8 @@ class Engine:
     # the sdf-bias gradient (= sum of d_sdf over all points, a heavily cancelling sum: the eikonal term pulls both ways) from the fp32
     # cotangent tensor instead of from the hi + lo bf16 tile: ONE reduction per backward.  The tile path measured 0.03 % on the 512^2
     # fixture, but a cancelling sum's relative error grows as the sum approaches zero (late in training, when eikonal and mask terms
-    # balance), and the reference accumulates this gradient in fp32 -- so the override is ON; AVC_SDF_BIAS_FP32=0 for the A/B.
-    SDF_BIAS_FP32 = os.environ.get("AVC_SDF_BIAS_FP32", "1") != "0"
+    # balance), and the reference accumulates this gradient in fp32 -- so the override is ON (False: the products' value).
+    SDF_BIAS_FP32 = True
     PANEL_BYTES_BUDGET = int(os.environ.get("AVC_PANEL_GIB", "224")) << 30
     SLAB_BLOCKS = int(os.environ.get("AVC_SLAB_BLOCKS", str(512 * 1024)))
     MIN_SLAB_BLOCKS = 32 * 1024
@@ -248,6 +238,10 @@ class Engine:
         self._packed_key = None
         self._packed = None
         self._panel_owner = None      # token of the RenderCoreFn.forward whose operand panels the buffers hold
+        self._last_pack = None        # (weak reference to the flat vector, its version, its Packed): pack()
+        self._colsum_scratch = None
+        self._plan_key = None         # plan(): the last (R, S, budget, slab blocks) and what plan_panels made of it
+        self._plan_val = None
 
     @classmethod
     def for_networks(cls, sdf_net, col_net):
@@ -281,7 +275,7 @@ class Engine:
     # ------------------------------------------------------------------ packing
     def pack(self, flatP: torch.Tensor) -> Packed:
         # (render() packs for the up-sampling passes and RenderCoreFn packs the same vector again: one launch instead of two)
-        last = getattr(self, "_last_pack", None)
+        last = self._last_pack
         if last is not None and last[0]() is flatP and last[1] == flatP._version:
             return last[2]
         pk = Packed(self.dl, flatP)
@@ -290,7 +284,7 @@ class Engine:
 
     def colsum_scratch(self):
         """the per-workgroup sums + ticket word of avc_colsum (zeroed once; calls are stream-ordered, one stream per engine)"""
-        if getattr(self, "_colsum_scratch", None) is None:
+        if self._colsum_scratch is None:
             self._colsum_scratch = torch.zeros(self.lib.avc_colsum_scratch_bytes(), dtype=torch.uint8, device=self.device)
         return self._colsum_scratch
 
@@ -328,7 +322,7 @@ class Engine:
     def plan(self, R, S):
         """(rays per chunk, rays per slab): a chunk's F panels + masks and one slab's G panels fit the budget (plan_panels)"""
         key = (R, S, self.PANEL_BYTES_BUDGET, self.SLAB_BLOCKS)
-        if getattr(self, "_plan_key", None) == key:
+        if self._plan_key == key:
             chunk, slab = self._plan_val
             if chunk < R or (self._fpanels is not None and self._fpanels.numel() >= ((R * S + 31) // 32 + 1) * self.fwd_tiles * 2048):
                 return self._plan_val  # (no driver query on the hot path: hipMemGetInfo synchronises with the device)
@@ -365,14 +359,14 @@ class Engine:
         L.call("avc_sdf_forward", self.net, pts, None, None, None, 1, 1, pts.shape[0], pk.w_f16, pk.tab, self.dl.offsets, out, None, 0)
         return out
 
-    def upsample_step(self, rays_o, rays_d, z, sdf, m, inv_s):
+    def upsample_step(self, rays_o, rays_d, z, sdf, m, inv_s, lanes=0):
+        """`lanes` = lanes per ray: 0 lets the library group 16 or 32 lanes per ray by n; 64 = one wavefront per ray for every n (the
+        cross-check of the grouped kernels, tests/test_gpu_kernels.py)"""
         R, n = z.shape
         z_out = torch.empty(R, n + m, device=self.device, dtype=torch.float32)
         sdf_out = torch.empty(R, n + m, device=self.device, dtype=torch.float32)
         z_new = torch.empty(R, m, device=self.device, dtype=torch.float32)
         slot = torch.empty(R, m, device=self.device, dtype=torch.int32)
-        # AVC_UPSAMPLE_GROUP=0: one wavefront per ray for every n (A/B partner and cross-check of the grouped kernels), read HERE per call
-        lanes = 64 if os.environ.get("AVC_UPSAMPLE_GROUP", "1") == "0" else 0
         L.call("avc_upsample_step_lanes", rays_o, rays_d, z, sdf, R, n, m, float(inv_s), z_out, sdf_out, z_new, slot, lanes)
         return z_out, sdf_out, z_new, slot
 
@@ -437,25 +431,19 @@ class Engine:
         return d_sdf, d_n, d_rgb, d_inv
 
     # ------------------------------------------------------------------ backward of the point MLP
-    def points_bwd(self, pk: Packed, rays_o, rays_d, z, sample_dist, d_sdf, d_n, d_rgb, rgb, panels_valid=False):
-        """returns the flat dense gradient [nparam] (fp32).  `rgb` = the forward's colours.  panels_valid: the F region still
-        holds the forward-type operand panels of exactly this ray set (one chunk, nothing rendered since) -- otherwise the
-        training forward is re-run per chunk.  The backward itself walks every chunk in slabs: backward kernel (writes the
-        slab's gradient-type panels) + weight-gradient kernel (contracts both regions over the slab)."""
+    def slab_walk(self, pk: Packed, rays_o, rays_d, z, sample_dist, d_sdf, d_n, d_rgb, rgb, panels_valid=False):
+        """The backward's walk over the ray set, a generator: every chunk (training forward re-run unless `panels_valid`) in slabs,
+        per slab the backward kernel (writes the slab's gradient-type panels and per-wavefront column sums) and the weight-gradient
+        kernel (contracts both regions over the slab, one partial product per split).  Yields once per slab, after that slab's
+        launches: (ns, cs_total) = the splits that self._partials / self._bpartials now hold, and the column sums over wavefronts
+        and slabs so far.  The consumer adds the splits up before it asks for the next slab (points_bwd; the torch statement of
+        tests/engine_cases.py)."""
         lay = self.dl.lay
         R, S = z.shape
         rays_per_chunk, rays_per_slab = self.plan(R, S)
         if rays_per_chunk < R:
             panels_valid = False
-        # the split sums and the way back to the dense vector: one launch per slab + one at the end (avc_weight_grad_reduce / _unpack);
-        # AVC_FUSED_WG_TAIL=0 keeps the torch statement of the same arithmetic
-        fused_tail = self.FUSED_WG_TAIL and lay.gout_size % 4 == 0 and lay.gbias_size % 4 == 0
-        if fused_tail:
-            gacc = torch.empty(lay.gout_size + lay.gbias_size, device=self.device, dtype=torch.float32)
-            nslab = 0
-        else:
-            gout = torch.zeros(lay.gout_size, device=self.device, dtype=torch.float32)
-            gbias = torch.zeros(max(lay.gbias_size, 1), device=self.device, dtype=torch.float32)
+        self._panel_owner = None      # (RenderCoreFn.backward has read it by now: `panels_valid`)
         if self._partials is None:
             self._partials = torch.empty(256, lay.gout_size, device=self.device, dtype=torch.float32)
             self._bpartials = torch.empty(256, max(lay.gbias_size, 1), device=self.device, dtype=torch.float32)
@@ -493,34 +481,35 @@ class Engine:
                 cs_slab = self._colsum[:rows].sum(0)      # (torch's reduction: a fixed tree, deterministic)
                 cs_total = cs_slab if cs_total is None else cs_total + cs_slab
                 ns = max(1, min(self.WG_MAX_SPLITS, nblk // self.WG_BLOCKS_PER_SPLIT, nblk))
-                with Engine._Timed("avc_weight_grad(all pairs)", npts):
+                with Engine._Timed("avc_weight_grad(all pairs)", npts):      # (the consumer's split sums belong to this launch group)
                     L.call("avc_weight_grad_all", fptr, self.fwd_tiles, gpanels, self.grad_tiles, len(self._pairs_host), self._pairs_host.ctypes.data,
                            nblk, self._partials, self._bpartials, ns, self._partials.stride(0), self._bpartials.stride(0), stream=st)
-                    if fused_tail:
-                        L.call("avc_weight_grad_reduce", self._partials, self._bpartials, ns, self._partials.stride(0), self._bpartials.stride(0),
-                               lay.gout_size, lay.gbias_size, gacc, int(nslab > 0), stream=st)
-                        nslab += 1
-                        continue
-                    po, pb_ = self._partials[:ns].sum(0), self._bpartials[:ns].sum(0)
-                    gout += po
-                    gbias += pb_
-        self._panel_owner = None
-        if fused_tail:
-            grad = torch.empty(lay.nparam, device=self.device, dtype=torch.float32)
-            if nslab == 0:
-                grad.zero_()
-            else:
-                L.call("avc_weight_grad_unpack", gacc, self.dl.csr_off, self.dl.csr_src, self.dl.csr_scale, lay.nparam, grad, stream=st)
+                    yield ns, cs_total
+
+    def points_bwd(self, pk: Packed, rays_o, rays_d, z, sample_dist, d_sdf, d_n, d_rgb, rgb, panels_valid=False):
+        """returns the flat dense gradient [nparam] (fp32).  `rgb` = the forward's colours.  panels_valid: the F region still
+        holds the forward-type operand panels of exactly this ray set (one chunk, nothing rendered since) -- otherwise the
+        training forward is re-run per chunk.  slab_walk launches the kernels; here the split sums and the way back to the dense
+        vector: one launch per slab + one at the end (avc_weight_grad_reduce / _unpack; both move four floats per lane, and
+        tests/test_net_shapes_cpu.py holds every supported layout to gout_size and gbias_size being multiples of 4)."""
+        lay = self.dl.lay
+        st = L.stream()
+        gacc = torch.empty(lay.gout_size + lay.gbias_size, device=self.device, dtype=torch.float32)
+        nslab, cs_total = 0, None
+        for ns, cs_total in self.slab_walk(pk, rays_o, rays_d, z, sample_dist, d_sdf, d_n, d_rgb, rgb, panels_valid):
+            L.call("avc_weight_grad_reduce", self._partials, self._bpartials, ns, self._partials.stride(0), self._bpartials.stride(0),
+                   lay.gout_size, lay.gbias_size, gacc, int(nslab > 0), stream=st)
+            nslab += 1
+        grad = torch.empty(lay.nparam, device=self.device, dtype=torch.float32)
+        if nslab == 0:
+            grad.zero_()
         else:
-            grad = torch.zeros(lay.nparam, device=self.device, dtype=torch.float32)
-            grad.index_add_(0, self.dl.un_tgt, gout[self.dl.un_src] * self.dl.un_scale)
-            if lay.gbias_size:
-                grad.index_add_(0, self.dl.ub_tgt, gbias[self.dl.ub_src])
+            L.call("avc_weight_grad_unpack", gacc, self.dl.csr_off, self.dl.csr_src, self.dl.csr_scale, lay.nparam, grad, stream=st)
         if cs_total is not None:      # second-order term of row 0 of the last SDF layer: sum_points [gbar_hs ; gbar_h0] / sqrt2 (unique targets)
             grad.index_add_(0, self.dl.cs_tgt, cs_total[self.dl.cs_src] * self.dl.cs_scale)
         # (d loss / d (sdf bias) = sum of d_sdf over all points cancels heavily -- the eikonal term pulls both ways.  The tile carries d_sdf
         # as hi + lo bf16 (packing.py / avc_bwd_body.h) and gets it to 0.03 %; the default takes the sum from the fp32 cotangent instead,
-        # AVC_SDF_BIAS_FP32=0 leaves the products' value.  sdf = lin_out / scale (fields.py:93) with scale == 1: packing.spec_from_conf
+        # SDF_BIAS_FP32 = False leaves the products' value.  sdf = lin_out / scale (fields.py:93) with scale == 1: packing.spec_from_conf
         # refuses every other value, so no division is needed here.)
         if self.SDF_BIAS_FP32:
             grad[self._sdf_bias0] = d_sdf.sum()

@@ -1,7 +1,7 @@
 """NeuSRenderer with the reference's constructor and `render` contract
 (AvatarGen/AppearanceGen/models/renderer.py:72-404), executed by the fused gfx950 kernels:
 
-  coarse z + jitter (renderer.py:304-319)                      torch elementwise on device
+  coarse z + jitter (renderer.py:304-319)                      avc_coarse_z
   SDF at the coarse samples (:337-338)                         avc_sdf_forward        (f16 MFMA)
   4x { up_sample + sample_pdf + cat_z_vals } (:340-352)        avc_upsample_step + avc_sdf_forward
   render_core (:195-300)                                       avc_render_points_fwd + avc_composite_fwd,
@@ -10,7 +10,18 @@
 """
 import torch
 
+from . import lib as L
 from .engine import Engine, RenderCoreFn, flatten_dense
+
+
+def coarse_z_torch(near, far, n_samples, perturb, jitter):
+    """renderer.py:304-319 as torch statements: what avc_coarse_z computes (bit for bit, tests/test_gpu_kernels.py), and what
+    sample_z falls back to when near / far are not one value per ray"""
+    z = torch.linspace(0.0, 1.0, n_samples, device=near.device)
+    z = near + (far - near) * z[None, :]
+    if perturb > 0:
+        z = z + (jitter - 0.5) * 2.0 / n_samples
+    return z.contiguous()
 
 
 class RenderOut(dict):
@@ -55,19 +66,13 @@ class NeuSRenderer:
         dev = rays_o.device
         if perturb > 0 and jitter is None:
             jitter = torch.rand([R, 1], device=dev)
-        from .engine import FUSED_PACK
-        if dev.type == "cuda" and FUSED_PACK and near.numel() == R and far.numel() == R:
-            from . import lib as L
+        if near.numel() == R and far.numel() == R:       # one value per ray: one launch
             near_c, far_c = near.reshape(R).contiguous().float(), far.reshape(R).contiguous().float()
             jit = jitter.reshape(R).contiguous().float() if perturb > 0 else None
             z = torch.empty(R, self.n_samples, device=dev, dtype=torch.float32)
             L.call("avc_coarse_z", near_c, far_c, jit, R, self.n_samples, z)
         else:
-            z = torch.linspace(0.0, 1.0, self.n_samples, device=dev)
-            z = near + (far - near) * z[None, :]
-            if perturb > 0:
-                z = z + (jitter - 0.5) * 2.0 / self.n_samples
-            z = z.contiguous()
+            z = coarse_z_torch(near, far, self.n_samples, perturb, jitter)
         steps = []
         if self.n_importance > 0:
             sdf = eng.sdf_rays(pk, rays_o, rays_d, z)

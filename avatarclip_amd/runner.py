@@ -203,7 +203,8 @@ class Runner:
             self.file_backup()
         self.perceptor = None
         self.prior_renderer = None
-        self._side_stream = None      # the second HIP stream of the silhouette mode's view (make_view_on_side_stream), made on first use
+        self.overlap_view = True      # silhouette mode on the GPU: build the iteration's view on a second HIP stream (_take_view)
+        self._side_stream = None      # that stream (make_view_on_side_stream), made on first use
 
     def seed_data_rngs(self):
         """View-sharded data parallelism: the weights are identical on every rank (broadcast), the DATA must not be.  The
@@ -436,11 +437,8 @@ class Runner:
     # tests (tests/test_glue_golden.py runs the glue on fixtures produced by the reference's own lines):
     #   make_view (main.py:348-385) -> draw_background (:387-415) -> renderer.render (:417-420)
     #   -> shade_and_scatter (:422-487) -> assemble_loss (:489-534) -> backward / all-reduce / Adam (:536-538)
-    def _fused_head(self):
-        """AVC_FUSED_HEAD, read per call (tests/test_gpu_glue.py flips it on one Runner): the view's rays and the chess-board
-        background out of one launch each; 0 (or no GPU) = the torch statements"""
-        return self.device.type == "cuda" and os.environ.get("AVC_FUSED_HEAD", "1") != "0"
-
+    # On the GPU the view's rays, the chess-board background and shading + loss come out of one launch each; on the CPU the torch
+    # statements of the same reference lines run (and serve tests/test_gpu_glue.py as the parity references).  The device alone chooses.
     def _view_head_fused(self, pose, prior):
         """rays + near / far + the prior resampled to the ray grid in one launch (dataset.rays_fused) instead of ~45"""
         dilated_mask = sel_idx = None
@@ -475,12 +473,14 @@ class Runner:
         near, far = self.dataset.near_far_from_sphere(rays_o, rays_d)
         return H, W, rays_o, rays_d, near, far, true_rgb, mask, dilated_mask, sel_idx
 
-    def make_view(self, iter_i, camera=None):
+    def make_view(self, iter_i, camera=None, head=None):
+        """`head`: _view_head_fused or _view_head_torch (default: by device)"""
         dev = self.device
         eye, at, theta, phi, is_front = camera if camera is not None else self.sample_camera(iter_i)
         pose = h2d.upload(lookat(eye, at, np.array([0, 1, 0])), dev)
         prior = torch.as_tensor(self.prior_renderer(eye, at), dtype=torch.float32, device=dev)
-        head = self._view_head_fused if self._fused_head() else self._view_head_torch
+        if head is None:
+            head = self._view_head_fused if dev.type == "cuda" else self._view_head_torch
         H, W, rays_o, rays_d, near, far, true_rgb, mask, dilated_mask, sel_idx = head(pose, prior)
         ray_of_pixel = None
         if sel_idx is not None and dev.type == "cuda":     # pixel -> ray (or -1): what the fused glue scatters with (glue.ShadeLossFn)
@@ -491,8 +491,8 @@ class Runner:
                                      dilated_mask=dilated_mask, sel_idx=sel_idx, ray_of_pixel=ray_of_pixel, mask_binary=True)
 
     def _take_view(self, iter_i, camera=None):
-        """the view of this iteration: in silhouette mode on the GPU it is built on the side stream (AVC_OVERLAP_HEAD=0: on one stream)"""
-        if self.use_silhouettes and self.device.type == "cuda" and os.environ.get("AVC_OVERLAP_HEAD", "1") != "0":
+        """the view of this iteration: in silhouette mode on the GPU it is built on the side stream (overlap_view = False: on one stream)"""
+        if self.use_silhouettes and self.device.type == "cuda" and self.overlap_view:
             return self.make_view_on_side_stream(iter_i, camera)
         return self.make_view(iter_i, camera)
 
@@ -536,7 +536,7 @@ class Runner:
         elif choice_i == 2:
             chess_length = H // np.random.choice(np.arange(10, 20))
             sigma = torch.empty(1).uniform_(0.1, 2.0).item()   # torchvision GaussianBlur.get_params: torch CPU RNG
-            background_rgb = (chess_background_fused if self._fused_head() else chess_background)(H, W, chess_length, sigma, dev)
+            background_rgb = (chess_background_fused if dev.type == "cuda" else chess_background)(H, W, chess_length, sigma, dev)
         if self.use_silhouettes and choice_i in (1, 2):
             idx = getattr(view, "sel_idx", None)      # (gather by index: boolean-mask indexing would synchronise the stream for the count)
             masked_background_rgb = background_rgb.reshape(-1, 1).index_select(0, idx) if idx is not None else \
@@ -650,7 +650,7 @@ class Runner:
     def fused_shade_loss(self, render_out, view, choice_i, background_rgb, iter_i, light=None):
         """shade_and_scatter + assemble_loss (main.py:422-534) through the two fused kernels of glue.py: same host draws in the same
         order (light direction, ambience), same images into CLIP, same loss terms -- ~150 small launches fewer per iteration
-        (tests/test_gpu_glue.py: values and gradients against the torch statement).  AVC_FUSED_GLUE=0: the torch statement."""
+        (tests/test_gpu_glue.py: values and gradients against the torch statement)."""
         from . import glue
         dev, H, W = self.device, view.H, view.W
         P = H * W
@@ -691,9 +691,8 @@ class Runner:
         choice_i, background_rgb, masked_background_rgb = self.draw_background(view)
         render_out = self.renderer.render(view.rays_o, view.rays_d, view.near, view.far, background_rgb=masked_background_rgb,
                                           cos_anneal_ratio=self.get_cos_anneal_ratio())
-        fused = (self.device.type == "cuda" and os.environ.get("AVC_FUSED_GLUE", "1") != "0"
-                 and not (self.use_silhouettes and getattr(view, "ray_of_pixel", None) is None))
-        if fused:
+        # (the fused scatter goes by ray_of_pixel: a silhouette view without it takes the torch statement)
+        if self.device.type == "cuda" and not (self.use_silhouettes and getattr(view, "ray_of_pixel", None) is None):
             loss, parts, _ = self.fused_shade_loss(render_out, view, choice_i, background_rgb, iter_i)
         else:
             comp = self.shade_and_scatter(render_out, view, choice_i, background_rgb)

@@ -1,5 +1,33 @@
-"""Seeded nets and backward inputs shared by the engine-level GPU tests (tests/test_gpu_kernels.py)."""
+"""Seeded nets and backward inputs shared by the engine-level GPU tests (tests/test_gpu_kernels.py), and the torch statements those
+tests hold the engine's single-launch forms against."""
 import torch
+
+
+def pack_statement(dl, flatP):
+    """(w_f16, w_bf16, tab) of engine.Packed as torch gathers: the statement avc_pack_params is held to, bit for bit"""
+    pz = torch.cat([flatP.detach().float(), flatP.new_zeros(1)])
+    w = pz[dl.idx16] * dl.scale16
+    return w.to(torch.float16).contiguous(), w.to(torch.bfloat16).contiguous(), (pz[dl.idx32] * dl.scale32).contiguous()
+
+
+def points_bwd_statement(eng, pk, rays_o, rays_d, z, sample_dist, d_sdf, d_n, d_rgb, rgb, panels_valid=False):
+    """Engine.points_bwd with the tail in torch: the product's slab walk (same launches, same partial products), then per slab two
+    reductions + two adds, and at the end gather, scale and index_adds -- what avc_weight_grad_reduce / _unpack are held to"""
+    lay, dl = eng.dl.lay, eng.dl
+    gout = torch.zeros(lay.gout_size, device=eng.device, dtype=torch.float32)
+    gbias = torch.zeros(lay.gbias_size, device=eng.device, dtype=torch.float32)
+    cs_total = None
+    for ns, cs_total in eng.slab_walk(pk, rays_o, rays_d, z, sample_dist, d_sdf, d_n, d_rgb, rgb, panels_valid):
+        gout += eng._partials[:ns].sum(0)
+        gbias += eng._bpartials[:ns].sum(0)
+    grad = torch.zeros(lay.nparam, device=eng.device, dtype=torch.float32)
+    grad.index_add_(0, dl.un_tgt, gout[dl.un_src] * dl.un_scale)
+    grad.index_add_(0, dl.ub_tgt, gbias[dl.ub_src])
+    if cs_total is not None:
+        grad.index_add_(0, dl.cs_tgt, cs_total[dl.cs_src] * dl.cs_scale)
+    if eng.SDF_BIAS_FP32:
+        grad[eng._sdf_bias0] = d_sdf.sum()
+    return grad
 
 
 def _nets(small, dev, seed=0):

@@ -111,17 +111,13 @@ def test_resize_norm_equals_interpolate(H):
 
 @gpu
 @pytest.mark.parametrize("silhouettes", [True, False])
-def test_fused_head_equals_the_torch_statement(silhouettes, monkeypatch):
+def test_fused_head_equals_the_torch_statement(silhouettes):
     """Runner.make_view through dataset.rays_fused (rays, near / far and the resampled prior in one launch) against the torch statement
     of dataset.py:252-293,331-342 and main.py:376-380 -- which tests/test_host_logic.py pins against the reference's own functions."""
     dev = torch.device("cuda")
     r = _runner(silhouettes, True, True, dev)
     cam = r.sample_camera(1)
-    views = []
-    for fused in ("1", "0"):
-        monkeypatch.setenv("AVC_FUSED_HEAD", fused)
-        views.append(r.make_view(1, camera=cam))
-    a, b = views
+    a, b = r.make_view(1, camera=cam), r.make_view(1, camera=cam, head=r._view_head_torch)
     assert (a.H, a.W) == (b.H, b.W) and a.rays_o.shape == b.rays_o.shape
     for k in ("rays_o", "rays_d", "near", "far", "true_rgb", "mask"):
         x, y = getattr(a, k), getattr(b, k)

@@ -318,18 +318,14 @@ def test_train_clip_iteration_with_silhouette_rays_and_background_augmentation()
 
 
 @gpu
-def test_side_stream_view_keeps_the_draw_order_and_the_losses(monkeypatch):
+def test_side_stream_view_keeps_the_draw_order_and_the_losses():
     """Runner.make_view_on_side_stream (silhouette mode: the iteration's view enqueued on a second HIP stream, the shipped default): same
     cameras, same ray sets, same background choices and the same losses as the run that builds every view on the main stream
-    (AVC_OVERLAP_HEAD=0) -- the numpy draw order of main.py:348-440 is untouched.  (Full-frame mode uses no side stream.)"""
+    (Runner.overlap_view = False) -- the numpy draw order of main.py:348-440 is untouched.  (Full-frame mode uses no side stream.)"""
     import bench
     from avatarclip_amd.runner import Runner
 
     def run(overlap):
-        if overlap:
-            monkeypatch.delenv("AVC_OVERLAP_HEAD", raising=False)
-        else:
-            monkeypatch.setenv("AVC_OVERLAP_HEAD", "0")
         conf = bench.make_conf(256, 32, small=True)
         conf.put("train.use_silhouettes", True)
         conf.put("train.max_ray_num", 3000)
@@ -337,6 +333,8 @@ def test_side_stream_view_keeps_the_draw_order_and_the_losses(monkeypatch):
         torch.manual_seed(0)
         np.random.seed(3)
         r = Runner(None, mode="train_clip", conf=conf, device=torch.device("cuda"))
+        if not overlap:
+            r.overlap_view = False
         r.init_clip()
         r.init_smpl()
         r.update_learning_rate()

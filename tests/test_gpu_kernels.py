@@ -336,23 +336,22 @@ def test_fused_dense_parameter_assembly_matches_torch_weight_norm(extra_color, w
 
 
 @gpu
-def test_head_fusions_equal_their_torch_statements(monkeypatch):
+def test_head_fusions_equal_their_torch_statements():
     """The single-launch forms of the iteration's small steps against the torch ops they replace: the packed parameter blobs (bit for
     bit), the coarse sample depths (bit for bit, with and without jitter), inv_s and its backward, the column sums around the
     compositing kernels."""
     import avatarclip_amd.engine as E
     from avatarclip_amd import fields, lib as L, packing as PK
+    from avatarclip_amd.renderer import coarse_z_torch
+    from tests.engine_cases import _nets, pack_statement
     dev = torch.device("cuda")
     lib = L.load()
     for spec in (PK.NetSpec(128, 2, 1), PK.NetSpec(256, 2, 1)):
         dl = E._DevLayout.get(spec, dev)
         flat = torch.randn(dl.lay.nparam, generator=torch.Generator().manual_seed(1)).to(dev) * 0.3
-        monkeypatch.setattr(E, "FUSED_PACK", True)
         a = E.Packed(dl, flat)
-        monkeypatch.setattr(E, "FUSED_PACK", False)
-        b = E.Packed(dl, flat)
-        assert torch.equal(a.w_f16, b.w_f16) and torch.equal(a.w_bf16, b.w_bf16) and torch.equal(a.tab, b.tab)
-    from tests.engine_cases import _nets
+        w_f16, w_bf16, tab = pack_statement(dl, flat)
+        assert torch.equal(a.w_f16, w_f16) and torch.equal(a.w_bf16, w_bf16) and torch.equal(a.tab, tab)
     ren = _nets(True, dev)
     g = torch.Generator().manual_seed(2)
     R = 777
@@ -361,10 +360,7 @@ def test_head_fusions_equal_their_torch_statements(monkeypatch):
     ro = torch.zeros(R, 3, device=dev); rd = torch.nn.functional.normalize(torch.randn(R, 3, generator=g), dim=-1).to(dev)
     ren.n_importance = 0            # sample_z then returns the coarse depths
     for perturb, j in ((0, None), (1.0, jit)):
-        zs = []
-        for fused in (True, False):
-            monkeypatch.setattr(E, "FUSED_PACK", fused)
-            zs.append(ren.sample_z(None, ro, rd, near, far, perturb, j))
+        zs = [ren.sample_z(None, ro, rd, near, far, perturb, j), coarse_z_torch(near, far, ren.n_samples, perturb, j)]
         assert zs[0].shape == (R, ren.n_samples) and torch.equal(zs[0], zs[1]), (perturb, (zs[0] - zs[1]).abs().max())
     for v0 in (0.3, 0.05, -1.5, 1.45):       # (-1.5 and 1.45: outside the clip range -> zero gradient)
         net = fields.SingleVarianceNetwork(v0).to(dev)
@@ -387,7 +383,7 @@ def test_head_fusions_equal_their_torch_statements(monkeypatch):
 
 @gpu
 @pytest.mark.parametrize("n,m", [(32, 8), (56, 8), (47, 5), (64, 16), (112, 16), (120, 8)])
-def test_grouped_upsample_kernel_equals_one_ray_per_wavefront(n, m, monkeypatch):
+def test_grouped_upsample_kernel_equals_one_ray_per_wavefront(n, m):
     """avc_upsample_step with several rays per wavefront (16 or 32 lanes per ray) against the one-wavefront-per-ray kernel (which
     the golden records of the reference pin, test_upsample_steps_match_reference): same algorithm, the scans add / multiply in a
     different order -> new depths equal to ~1e-6 except where the inversion lands on a bin edge; the merge invariants hold exactly."""
@@ -401,10 +397,7 @@ def test_grouped_upsample_kernel_equals_one_ray_per_wavefront(n, m, monkeypatch)
     z = torch.sort(torch.rand(R, n, generator=g) * 2 + 0.2, dim=-1)[0].to(dev).contiguous()
     pts = ro[:, None, :] + rd[:, None, :] * z[..., None]
     sdf = (pts.norm(dim=-1) - 0.6 + 0.02 * torch.randn(R, n, generator=g).to(dev)).contiguous()     # a noisy sphere: surface crossings
-    outs = []
-    for grouped in ("1", "0"):
-        monkeypatch.setenv("AVC_UPSAMPLE_GROUP", grouped)
-        outs.append(eng.upsample_step(ro, rd, z, sdf, m, 64.0))
+    outs = [eng.upsample_step(ro, rd, z, sdf, m, 64.0), eng.upsample_step(ro, rd, z, sdf, m, 64.0, lanes=64)]
     (za, sa, na, sla), (zb, sb, nb_, slb) = outs
     err = (na - nb_).abs()
     assert err.median() < 2e-6 and (err > 1e-3).float().mean() < 5e-3, (err.median().item(), err.max().item())
@@ -420,9 +413,8 @@ def test_fused_split_sums_and_unpacking_equal_the_torch_statement(small, R, S, s
     """avc_weight_grad_reduce + avc_weight_grad_unpack (one launch per slab + one at the end) against the torch statement of the same
     arithmetic (two reductions + two adds per slab, gather, scale, two index_adds): same products, fp32 sums in a different order;
     with several slabs the accumulate path is exercised."""
-    from avatarclip_amd.engine import Engine
     dev = torch.device("cuda")
-    from tests.engine_cases import _inputs, _nets
+    from tests.engine_cases import _inputs, _nets, points_bwd_statement
     ren = _nets(small, dev)
     eng = ren.engine
     if slab_blocks is not None:
@@ -430,10 +422,9 @@ def test_fused_split_sums_and_unpacking_equal_the_torch_statement(small, R, S, s
     pk = eng.pack(ren.flat_params())
     ro, rd, z, dsdf, dn, drgb = _inputs(R, S, dev)
     gs = []
-    for fused in (False, True):
-        monkeypatch.setattr(Engine, "FUSED_WG_TAIL", fused)
+    for bwd in (lambda *a, **k: points_bwd_statement(eng, *a, **k), eng.points_bwd):
         _, _, rgbf = eng.points_fwd_train(pk, ro, rd, z, 2 / 32)
-        gs.append(eng.points_bwd(pk, ro, rd, z, 2 / 32, dsdf, dn, drgb, rgbf, panels_valid=True).clone())
+        gs.append(bwd(pk, ro, rd, z, 2 / 32, dsdf, dn, drgb, rgbf, panels_valid=True).clone())
     lay = eng.dl.lay
     assert torch.isfinite(gs[1]).all()
     for name, shape in lay.shapes:

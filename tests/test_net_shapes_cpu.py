@@ -65,6 +65,14 @@ def test_generated_offsets_header_has_one_specialisation_per_shape_and_is_the_co
     assert [int(l.split()[2]) for l in avc_h.splitlines() if l.startswith("#define AVC_NET_") and "COUNT" not in l] == list(range(6))
 
 
+def test_split_sum_buffers_of_every_supported_shape_are_whole_float4s():
+    """avc_weight_grad_reduce / _unpack move four floats per lane over [gout | gbias], and Engine.points_bwd has no other tail: both
+    sizes are multiples of 4 in every row of packing.SUPPORTED."""
+    for _, name, sp in PK.SUPPORTED:
+        lay = PK.layout_for(sp)
+        assert lay.gout_size % 4 == 0 and lay.gbias_size % 4 == 0, (name, lay.gout_size, lay.gbias_size)
+
+
 @pytest.mark.parametrize("shape", NEW_SHAPES, ids=SHAPE_IDS)
 def test_emulated_wave_matches_analytic_at_the_new_shapes(shape):
     """the statement of tests/test_packing_emulation.py::test_emulated_wave_matches_analytic, same 1e-6 gate, on the fixture's weights"""
