@@ -1,11 +1,12 @@
-"""CLIP ViT-B/32 image encoder on the gfx950 kernels -- drop-in for `perceptor.encode_image`
+"""CLIP ViT-B/32 and ViT-B/16 image encoder on the gfx950 kernels -- drop-in for `perceptor.encode_image`
 (AvatarGen/AppearanceGen/main.py:259-260,512,518,524; upstream: OpenAI clip/model.py VisionTransformer, un-vendored).
 
 All GEMMs (patch embedding, in_proj, out_proj, c_fc, c_proj, visual.proj) run in avc_vit_linear / avc_vit_linear_packed (bf16 MFMA,
 fp32 accumulate; the reference runs CLIP in fp16 on GPU), attention in avc_vit_attention_*.  Weights are frozen
 (`requires_grad_(False)`, main.py:260): the backward only propagates to the pixels, re-using the same GEMM kernel on
 the packed transposes.  LayerNorm / residual bookkeeping are torch elementwise ops under autograd.
-Accepts an OpenAI-format state dict (`visual.*` keys, e.g. torch.jit.load('ViT-B-32.pt').state_dict()).
+Accepts an OpenAI-format state dict (`visual.*` keys, e.g. torch.jit.load('ViT-B-32.pt').state_dict()); the variant -- patch 32 / 50
+tokens or patch 16 / 197 tokens, both width 768, 12 layers, 224 x 224 input -- is read from the checkpoint (vision_variant).
 """
 import math
 import os
@@ -29,6 +30,30 @@ def pack_weight(w: torch.Tensor) -> torch.Tensor:
     assert N % 32 == 0 and K % 16 == 0
     p = w.reshape(N // 32, 32, K // 16, 2, 8).permute(0, 2, 3, 1, 4).contiguous()
     return p.to(torch.bfloat16).reshape(-1)
+
+
+VARIANTS = ((32, 50), (16, 197))     # (patch, tokens) of ViT-B/32 and ViT-B/16 at 224 x 224
+
+
+def vision_variant(state_dict) -> tuple:
+    """(patch, tokens) of the image tower in an OpenAI-format CLIP state dict: the patch size from `visual.conv1.weight`, the token
+    count from `visual.positional_embedding`.  The kernels are built for width 768, head dim 64 and up to 256 tokens, the host path
+    for 12 layers at 224 x 224: ViT-B/32 (32, 50) and ViT-B/16 (16, 197).  Anything else is a ValueError that says what was found."""
+    def refuse(found):
+        raise ValueError("the CLIP image tower must be ViT-B/32 (patch 32, 50 tokens) or ViT-B/16 (patch 16, 197 tokens) at width %d "
+                         "with %d layers; found %s" % (WIDTH, LAYERS, found))
+    conv, pos = state_dict.get("visual.conv1.weight"), state_dict.get("visual.positional_embedding")
+    if conv is None or pos is None or conv.dim() != 4 or pos.dim() != 2:
+        refuse("no ViT image tower (`visual.conv1.weight` [width, 3, patch, patch] and `visual.positional_embedding` [tokens, width]; "
+               "a ResNet tower has neither of these shapes)")
+    width, patch, tokens = int(conv.shape[0]), int(conv.shape[-1]), int(pos.shape[0])
+    layers = len({k.split(".")[3] for k in state_dict if k.startswith("visual.transformer.resblocks.")})
+    found = "width %d, patch %d, %d tokens, %d layers" % (width, patch, tokens, layers)
+    if width != WIDTH or int(pos.shape[1]) != WIDTH or layers != LAYERS or tuple(conv.shape[1:]) != (3, patch, patch):
+        refuse(found)
+    if (patch, tokens) not in VARIANTS:
+        refuse(found + ("" if patch not in (32, 16) else " (patch %d has (224 / %d)^2 + 1 = %d)" % (patch, patch, (RES // patch) ** 2 + 1)))
+    return patch, tokens
 
 
 TRAIN_GRAPH = os.environ.get("AVC_CLIP_GRAPH", "1") != "0"        # see ClipVisionB32.encode_image
@@ -103,20 +128,20 @@ class LinearFn(torch.autograd.Function):
 class AttentionFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, qkv):
-        B, T, _ = qkv.shape
+        B, T, W3 = qkv.shape          # (the geometry is the tensor's: any T in [1, 256], width = heads * 64)
         qkv = qkv.contiguous().float()
-        out = torch.empty(B, T, WIDTH, device=qkv.device, dtype=torch.float32)
-        L.call("avc_vit_attention_fwd", qkv, out, B, T, WIDTH, HEADS)
+        out = torch.empty(B, T, W3 // 3, device=qkv.device, dtype=torch.float32)
+        L.call("avc_vit_attention_fwd", qkv, out, B, T, W3 // 3, W3 // 192)
         ctx.save_for_backward(qkv)
         return out
 
     @staticmethod
     def backward(ctx, dout):
         (qkv,) = ctx.saved_tensors
-        B, T, _ = qkv.shape
+        B, T, W3 = qkv.shape
         dout = dout.contiguous().float()
         dqkv = torch.empty_like(qkv)
-        L.call("avc_vit_attention_bwd", qkv, dout, dqkv, B, T, WIDTH, HEADS)
+        L.call("avc_vit_attention_bwd", qkv, dout, dqkv, B, T, W3 // 3, W3 // 192)
         return dqkv
 
 
@@ -134,8 +159,8 @@ class BlocksFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, model):
         st = L.stream()
-        B = x.shape[0]
-        M, W = B * TOKENS, WIDTH
+        B, T = x.shape[0], model.tokens
+        M, W = B * T, WIDTH
         x0 = x.reshape(M, W).contiguous().float()
         nb = len(model.blocks)
         dev = x0.device
@@ -161,7 +186,7 @@ class BlocksFn(torch.autograd.Function):
             x2, qkv, out = x2s[k], qkvs[k], xs[k]
             L.call("avc_vit_ln_pack", cur, blk["ln1"][0], blk["ln1"][1], 1e-5, M, W, a_ln, stream=st)
             linear(a_ln, blk["qkv"], None, qkv, None, None, 3 * W, W, 0)
-            L.call("avc_vit_attention_fwd_packed", qkv, a_at, B, TOKENS, W, HEADS, stream=st)
+            L.call("avc_vit_attention_fwd_packed", qkv, a_at, B, T, W, HEADS, stream=st)
             linear(a_at, blk["out"], cur, x2, None, None, W, W, 0)
             L.call("avc_vit_ln_pack", x2, blk["ln2"][0], blk["ln2"][1], 1e-5, M, W, a_ln, stream=st)
             linear(a_ln, blk["fc"], None, None, pres[i] if keep else None, a_fc, 4 * W, W, 1)
@@ -170,14 +195,15 @@ class BlocksFn(torch.autograd.Function):
         if keep:
             ctx.model, ctx.B = model, B
             ctx.save_for_backward(x0, xs, x2s, qkvs, pres)
-        return cur.reshape(B, TOKENS, W)
+        return cur.reshape(B, T, W)
 
     @staticmethod
     def backward(ctx, g):
         st = L.stream()
         model, B = ctx.model, ctx.B
         x0, xs, x2s, qkvs, pres = ctx.saved_tensors
-        M, W = B * TOKENS, WIDTH
+        T = model.tokens
+        M, W = B * T, WIDTH
         dev = x0.device
         g = g.reshape(M, W).contiguous().float()
         p_g, p_dh = model._train_buf("g", M, W), model._train_buf("dh", M, 4 * W)
@@ -197,18 +223,21 @@ class BlocksFn(torch.autograd.Function):
             # ln_2 backward + the residual branch's gradient: fp32 (the next residual sum) and packed (out_proj^T)
             L.call("avc_vit_ln_bwd", dy2, x2s[i], blk["ln2"][0], 1e-5, g, bufa, p_g2, M, W, stream=st)
             linear_t(p_g2, blk["out"], None, da, None, W, W, 0)
-            L.call("avc_vit_attention_bwd_packed", qkvs[i], da, p_dqkv, B, TOKENS, W, HEADS, stream=st)
+            L.call("avc_vit_attention_bwd_packed", qkvs[i], da, p_dqkv, B, T, W, HEADS, stream=st)
             linear_t(p_dqkv, blk["qkv"], None, dy1, None, W, 3 * W, 0)
             # ln_1 backward + residual: the gradient of the block's input, packed for the block below
             L.call("avc_vit_ln_bwd", dy1, xin, blk["ln1"][0], 1e-5, bufa, bufb, p_g if i else None, M, W, stream=st)
             g = bufb       # (bufa / bufb are re-used by the block below: each is dead by the time it is written again)
-        return g.reshape(B, TOKENS, W), None
+        return g.reshape(B, T, W), None
 
 
-class ClipVisionB32:
-    """`perceptor` stand-in: .encode_image(x[B,3,224,224]) -> [B,512] (differentiable wrt x only)."""
+class ClipVision:
+    """`perceptor` stand-in: .encode_image(x[B,3,224,224]) -> [B,512] (differentiable wrt x only).  ViT-B/32 or ViT-B/16, whichever
+    the state dict holds (vision_variant): `patch` and `tokens` are attributes of the instance.  `ClipVisionB32` is the same class
+    under its first name."""
 
     def __init__(self, state_dict: Dict[str, torch.Tensor], device="cuda"):
+        self.patch, self.tokens = vision_variant(state_dict)         # (on the CPU, before any library load)
         dev = torch.device(device)
         if dev.type != "cuda":
             raise RuntimeError("ClipVisionB32 runs on the MI355X kernels only (no CPU fallback)")
@@ -282,7 +311,7 @@ class ClipVisionB32:
                     with torch.cuda.device(self.device):     # (capture streams are created on the CURRENT device)
                         # the captured launches bake in the pointer of the linears' packing workspace: size it for the largest linear of
                         # this pass BEFORE the capture (no growth, i.e. no re-allocation, while launches are being recorded) ...
-                        _ws(self.device, L.load().avc_vit_workspace_bytes(B * TOKENS, 4 * WIDTH))
+                        _ws(self.device, L.load().avc_vit_workspace_bytes(B * self.tokens, 4 * WIDTH))
                         g = torch.cuda.make_graphed_callables(self._encode_image_eager, (sample,))
                         # ... and keep that buffer alive for as long as the graphs exist: a later, larger eager call (batched scoring,
                         # M > 128) makes _ws() allocate a new one, and dropping the old one would leave the replays writing into freed memory
@@ -331,12 +360,13 @@ class ClipVisionB32:
 
     def _blocks_packed(self, x):
         """the residual blocks with packed bf16 hand-offs between the kernels (BlocksFn): every call without a gradient to the
-        pixels, and gradient calls of up to 128 rows (2 images)"""
+        pixels, and gradient calls of up to 128 rows (2 images of ViT-B/32)"""
         return BlocksFn.apply(x, self)
 
     def _blocks_per_kernel(self, x):
         """the residual blocks as one autograd node per kernel (fp32 rows + a packing pass in front of every linear, torch LayerNorm):
-        gradient calls with 3+ images (AvatarAnimate's CLIP-guided optimisers), and what the tests hold BlocksFn against"""
+        gradient calls of more than 128 rows (3+ images of ViT-B/32: AvatarAnimate's CLIP-guided optimisers; every gradient call of
+        ViT-B/16, 197 rows an image), and what the tests hold BlocksFn against"""
         for blk in self.blocks:
             y = F.layer_norm(x, (WIDTH,), blk["ln1"][0], blk["ln1"][1], 1e-5)
             a = AttentionFn.apply(LinearFn.apply(y, blk["qkv"], 0, None))
@@ -348,16 +378,16 @@ class ClipVisionB32:
 
     def _encode_image_eager(self, image: torch.Tensor, blocks=None) -> torch.Tensor:
         """blocks: _blocks_packed or _blocks_per_kernel; None = the route this call is meant to take"""
-        B = image.shape[0]
-        # conv1 (32x32, stride 32, no bias) == GEMM over flattened patches in (c, ky, kx) order
-        x = image.float().reshape(B, 3, RES // PATCH, PATCH, RES // PATCH, PATCH).permute(0, 2, 4, 1, 3, 5)
-        x = x.reshape(B, (RES // PATCH) ** 2, 3 * PATCH * PATCH)
+        B, P = image.shape[0], self.patch
+        # conv1 (P x P, stride P, no bias) == GEMM over flattened patches in (c, ky, kx) order
+        x = image.float().reshape(B, 3, RES // P, P, RES // P, P).permute(0, 2, 4, 1, 3, 5)
+        x = x.reshape(B, (RES // P) ** 2, 3 * P * P)
         x = LinearFn.apply(x, self.conv, 0, None)
         x = torch.cat([self.cls.expand(B, 1, WIDTH), x], dim=1) + self.pos
         x = F.layer_norm(x, (WIDTH,), self.ln_pre[0], self.ln_pre[1], 1e-5)
         if blocks is None:
             grad = torch.is_grad_enabled() and x.requires_grad
-            blocks = self._blocks_per_kernel if grad and B * TOKENS >= BIG_M else self._blocks_packed
+            blocks = self._blocks_per_kernel if grad and B * self.tokens >= BIG_M else self._blocks_packed
         x = blocks(x)
         x = F.layer_norm(x[:, 0, :], (WIDTH,), self.ln_post[0], self.ln_post[1], 1e-5)
         return LinearFn.apply(x, self.proj, 0, None)
@@ -374,9 +404,12 @@ class ClipVisionB32:
         return self._text.encode_text(tokens)
 
 
+ClipVisionB32 = ClipVision       # the class's first name, from when ViT-B/32 was the only tower: every existing call site uses it
+
+
 def load_state_dict(path: str) -> Dict[str, torch.Tensor]:
-    """An OpenAI CLIP ViT-B/32 checkpoint: the TorchScript archive `ViT-B-32.pt` that `clip.load` downloads, a plain
-    `torch.save(model.state_dict())` file, or a .safetensors file with the same key names."""
+    """An OpenAI CLIP ViT-B/32 or ViT-B/16 checkpoint: the TorchScript archive `ViT-B-32.pt` / `ViT-B-16.pt` that `clip.load` downloads,
+    a plain `torch.save(model.state_dict())` file, or a .safetensors file with the same key names."""
     if path.endswith(".safetensors"):
         from safetensors.torch import load_file
         return load_file(path)
@@ -384,7 +417,7 @@ def load_state_dict(path: str) -> Dict[str, torch.Tensor]:
         obj = torch.load(path, map_location="cpu", weights_only=True)     # a plain state dict: no code is executed
     except Exception:
         try:
-            obj = torch.jit.load(path, map_location="cpu")                # OpenAI's ViT-B-32.pt is a TorchScript archive
+            obj = torch.jit.load(path, map_location="cpu")                # OpenAI's ViT-B-32.pt / ViT-B-16.pt are TorchScript archives
         except RuntimeError:
             # a pickled module or other arbitrary pickle: executes code from the file, as the reference's clip.load does --
             # only with the explicit opt-in

@@ -419,18 +419,37 @@ int avc_attn_fwd_mfma(const float* qkv, float* out, int B, int width, int heads,
 int avc_attn_bwd_mfma(const float* qkv, const float* dout, float* dqkv, int B, int width, int heads, void* stream);
 int avc_attn_fwd_mfma_packed(const float* qkv, void* out_packed, int B, int width, int heads, void* stream);
 int avc_attn_bwd_mfma_packed(const float* qkv, const float* dout, void* dqkv_packed, int B, int width, int heads, void* stream);
+// every other T in [1, 256]: the keys walked in 32-key tiles (avc_vit_attn.hip, second half)
+int avc_attn_fwd_tiled(const float* qkv, float* out, int B, int T, int width, int heads, void* stream);
+int avc_attn_bwd_tiled(const float* qkv, const float* dout, float* dqkv, int B, int T, int width, int heads, void* stream);
+int avc_attn_fwd_tiled_packed(const float* qkv, void* out_packed, int B, int T, int width, int heads, void* stream);
+int avc_attn_bwd_tiled_packed(const float* qkv, const float* dout, void* dqkv_packed, int B, int T, int width, int heads, void* stream);
+// one rule for the four entry points: 0 = refused (avc_last_error() says why), 1 = the 50-token kernels, 2 = the tiled ones
+static int vit_attn_route(int T, int width, int heads) {
+  if (T < 1 || T > 256 || heads < 1 || width != heads * AT_D) {
+    avc_set_error("avc_vit_attention: 1 <= T <= 256 tokens, head dim 64 (width == heads * 64)");
+    return 0;
+  }
+  return T == AT_T ? 1 : 2;
+}
 extern "C" int avc_vit_attention_bwd_packed(const float* qkv, const float* dout, void* dqkv_packed, int B, int T, int width, int heads,
                                             void* stream) {
-  if (T != AT_T || width != heads * AT_D) { avc_set_error("avc_vit_attention: built for 50 tokens, head dim 64"); return 1; }
+  const int route = vit_attn_route(T, width, heads);
+  if (!route) return 1;
+  if (route == 2) return B <= 0 ? 0 : avc_attn_bwd_tiled_packed(qkv, dout, dqkv_packed, B, T, width, heads, stream);
   return avc_attn_bwd_mfma_packed(qkv, dout, dqkv_packed, B, width, heads, stream);
 }
 extern "C" int avc_vit_attention_fwd_packed(const float* qkv, void* out_packed, int B, int T, int width, int heads, void* stream) {
-  if (T != AT_T || width != heads * AT_D) { avc_set_error("avc_vit_attention: built for 50 tokens, head dim 64"); return 1; }
+  const int route = vit_attn_route(T, width, heads);
+  if (!route) return 1;
+  if (route == 2) return B <= 0 ? 0 : avc_attn_fwd_tiled_packed(qkv, out_packed, B, T, width, heads, stream);
   return avc_attn_fwd_mfma_packed(qkv, out_packed, B, width, heads, stream);
 }
 
 extern "C" int avc_vit_attention_fwd(const float* qkv, float* out, int B, int T, int width, int heads, void* stream) {
-  if (T != AT_T || width != heads * AT_D) { avc_set_error("avc_vit_attention: built for 50 tokens, head dim 64"); return 1; }
+  const int route = vit_attn_route(T, width, heads);
+  if (!route) return 1;
+  if (route == 2) return B <= 0 ? 0 : avc_attn_fwd_tiled(qkv, out, B, T, width, heads, stream);
   return avc_attn_fwd_mfma(qkv, out, B, width, heads, stream);
 }
 extern "C" int avc_text_attention_fwd(const float* qkv, float* out, int B, int T, int width, int heads, int causal, void* stream) {
@@ -447,6 +466,8 @@ extern "C" int avc_text_attention_fwd(const float* qkv, float* out, int B, int T
 }
 extern "C" int avc_vit_attention_bwd(const float* qkv, const float* dout, float* dqkv, int B, int T, int width, int heads,
                                      void* stream) {
-  if (T != AT_T || width != heads * AT_D) { avc_set_error("avc_vit_attention: built for 50 tokens, head dim 64"); return 1; }
+  const int route = vit_attn_route(T, width, heads);
+  if (!route) return 1;
+  if (route == 2) return B <= 0 ? 0 : avc_attn_bwd_tiled(qkv, dout, dqkv, B, T, width, heads, stream);
   return avc_attn_bwd_mfma(qkv, dout, dqkv, B, width, heads, stream);
 }

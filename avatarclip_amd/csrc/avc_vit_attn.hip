@@ -255,6 +255,334 @@ __global__ __launch_bounds__(256) void vit_attn_bwd_mfma_kernel(const float* __r
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------------
+// 1 <= T <= 256 tokens (every T but 50, which stays on the kernels above; 197 = ViT-B/16): the keys no longer fit one 64-key tile,
+// so the sequence is walked in 32-key tiles, NT = ceil(T / 32) <= 8 of them.  Same transposed products, same fragments and the same
+// arithmetic class as above.  Where each operand is rounded to bf16:
+//   q / 8, k, v, dO   when they are read from the fp32 rows (q AFTER the scaling by 1/8, which is exact);
+//   P                 AFTER normalisation: a first pass over the key tiles takes the row maximum m and the row sum l of exp(s - m) in
+//                     fp32 (running maximum, l rescaled when m grows), a second pass recomputes the scores and rounds p = exp(s - m) / l
+//                     -- the T = 50 kernels' rounding point; nothing unnormalised is ever rounded;
+//   dS                = P (dP - D) from the fp32 P and dP and the fp32 D = sum_j P dP, rounded once; dQ's copy is rounded after the
+//                     (exact) scaling by 1/8.
+// Ragged T: K / V / Q / dO rows past T are ZERO-FILLED BY SELECTION when they are staged (the fp32 rows past b * T + T belong to the
+// next image or to nobody and are never read), key columns past T are taken out of the maximum, the sum and P by selection (s = -1e30,
+// p = 0), query rows past T are never stored.  Every output element is written by exactly one lane, every sum runs in one fixed
+// order and nothing depends on the image's place in the batch: no atomics, results are the same bits in every run and every batch.
+//   forward   one 4-wavefront workgroup per (image, head, 128 queries): K [key][d] and V^T [d][key] of the whole sequence in LDS
+//             (<= 69 KiB: two workgroups per CU), one wavefront per 32-query tile with its q fragments in registers.
+//   backward  one 8-wavefront workgroup per (image, head) -- dK and dV contract over ALL queries of the pair, and the entry points
+//             carry no workspace for statistics or partial sums.  Phase 1 (LDS: K, V, K^T): wavefront w owns query tile w; pass A takes
+//             m, l and D (D = sum_j exp(s - m) dP / l, rescaled with l) in one sweep over the key tiles, pass B recomputes s and dP,
+//             forms dS and accumulates dQ^T = K^T dS^T; m, 1/l, D go to LDS.  Phase 2 (LDS re-staged: Q, dO, Q^T, dO^T): wavefront w
+//             owns KEY tile w with its k / v fragments in registers and walks the query tiles in order 0 .. NT-1 with the products the
+//             other way round (S = Q K^T: lane = key, registers = queries), so that P and dS ARE the B operands of dV^T = dO^T P and
+//             dK^T = Q^T dS: no [key][query] round trip through LDS.  141 KiB of LDS: one workgroup per CU.
+#define ATL_TMAX 256
+#define ATL_LDT 264   // row stride of the [d][token] matrices (528 B: 8-byte aligned fragments, 4-bank skew per row)
+#define ATL_NAT (ATL_TMAX * ATM_LD * 2)      // bytes of a [token][d] matrix
+#define ATL_TR (ATM_D * ATL_LDT * 2)         // bytes of a [d][token] matrix
+#define ATL_BWD_LDS (2 * ATL_NAT + 2 * ATL_TR + 3 * ATL_TMAX * 4)
+
+__device__ __forceinline__ b8 frag_perm_t(const bf (*m)[ATL_LDT], int r, int s, int h) {   // frag_perm over up to 16 k-steps
+  const int k0 = 32 * (s >> 1) + 16 * (s & 1) + 4 * h;
+  struct { s4v lo, hi; } v;
+  v.lo = *reinterpret_cast<const s4v*>(&m[r][k0]);
+  v.hi = *reinterpret_cast<const s4v*>(&m[r][k0 + 8]);
+  return __builtin_bit_cast(b8, v);
+}
+// the four k-steps (over d) of row `rp` (64 fp32 values, NULL: a row past T) as a B operand: lane (n, h) holds d = 16 s + 8 h + 0..7
+__device__ __forceinline__ void row_frags(const float* rp, int h, float scale, b8 (&f)[4]) {
+#pragma unroll
+  for (int s = 0; s < 4; ++s) {
+    f4 lo = {0.f, 0.f, 0.f, 0.f}, hi = lo;
+    if (rp) { lo = *reinterpret_cast<const f4*>(rp + 16 * s + 8 * h) * scale; hi = *reinterpret_cast<const f4*>(rp + 16 * s + 8 * h + 4) * scale; }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { f[s][j] = (bf)lo[j]; f[s][4 + j] = (bf)hi[j]; }
+  }
+}
+// one accumulator tile (x scale) -> its two B-operand k-steps (slot (s, h, j) = row acc_row(8 s + j, h) of the tile)
+__device__ __forceinline__ void acc_to_b2(const facc& a, float scale, b8 (&f)[2]) {
+#pragma unroll
+  for (int j = 0; j < 8; ++j) { f[0][j] = (bf)(a[j] * scale); f[1][j] = (bf)(a[8 + j] * scale); }
+}
+__device__ __forceinline__ facc tile_product(const bf (*A)[ATM_LD], int row, const b8 (&f)[4], int h) {
+  facc c;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) c[r] = 0.f;
+#pragma unroll
+  for (int s = 0; s < 4; ++s) c = MF<b8>::mma(frag_nat(A, row, s, h), f[s], c);
+  return c;
+}
+
+template <bool PACKED>
+__global__ __launch_bounds__(256) void vit_attn_fwd_tiled_kernel(const float* __restrict__ qkv, float* __restrict__ out, int T, int Wd,
+                                                                 int heads, float scale) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int NT = (T + 31) >> 5;
+  bf (*K)[ATM_LD] = reinterpret_cast<bf (*)[ATM_LD]>(smem);                                     // [32 NT][72]
+  bf (*VT)[ATL_LDT] = reinterpret_cast<bf (*)[ATL_LDT]>(smem + (size_t)NT * 32 * ATM_LD * 2);    // [64][264]
+  const int b = blockIdx.x / heads, hd = blockIdx.x % heads;
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int n = lane & 31, h = lane >> 5;
+  const float* base = qkv + (long)b * T * 3 * Wd + hd * ATM_D;
+  for (int e = threadIdx.x; e < NT * 32 * (ATM_D / 4); e += 256) {
+    const int r = e / (ATM_D / 4), c = 4 * (e % (ATM_D / 4));
+    f4 k = {0.f, 0.f, 0.f, 0.f}, v = k;
+    if (r < T) {
+      const float* rp = base + (long)r * 3 * Wd + c;
+      k = *reinterpret_cast<const f4*>(rp + Wd); v = *reinterpret_cast<const f4*>(rp + 2 * Wd);
+    }
+    put4(&K[r][c], k);
+#pragma unroll
+    for (int u = 0; u < 4; ++u) VT[c + u][r] = (bf)v[u];
+  }
+  const int ti = 4 * blockIdx.y + wv, i = 32 * ti + n;
+  b8 qf[4];
+  row_frags(ti < NT && i < T ? base + (long)i * 3 * Wd : nullptr, h, scale, qf);
+  __syncthreads();
+  if (ti >= NT) return;              // (no barrier below)
+  // pass A: row maximum and row sum over the key tiles
+  float mx = -1e30f, sum = 0.f;
+  for (int tj = 0; tj < NT; ++tj) {
+    facc s = tile_product(K, 32 * tj + n, qf, h);
+    float tm = -1e30f;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      s[r] = 32 * tj + acc_row(r, h) < T ? s[r] : -1e30f;      // keys past T
+      tm = fmaxf(tm, s[r]);
+    }
+    tm = fmaxf(tm, __shfl_xor(tm, 32));
+    const float mn = fmaxf(mx, tm);
+    sum *= __expf(mx - mn);
+#pragma unroll
+    for (int r = 0; r < 16; ++r) sum += __expf(s[r] - mn);
+    mx = mn;
+  }
+  sum += __shfl_xor(sum, 32);
+  const float inv = 1.f / sum;
+  // pass B: P, rounded after normalisation, and O^T = V^T P^T
+  facc o[2];
+#pragma unroll
+  for (int td = 0; td < 2; ++td)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) o[td][r] = 0.f;
+  for (int tj = 0; tj < NT; ++tj) {
+    facc s = tile_product(K, 32 * tj + n, qf, h);
+#pragma unroll
+    for (int r = 0; r < 16; ++r) s[r] = 32 * tj + acc_row(r, h) < T ? __expf(s[r] - mx) * inv : 0.f;
+    b8 pf[2];
+    acc_to_b2(s, 1.f, pf);
+#pragma unroll
+    for (int td = 0; td < 2; ++td)
+#pragma unroll
+      for (int u = 0; u < 2; ++u) o[td] = MF<b8>::mma(frag_perm_t(VT, 32 * td + n, 2 * tj + u, h), pf[u], o[td]);
+  }
+  if (i >= T) return;                // query rows past T are never stored
+#pragma unroll
+  for (int td = 0; td < 2; ++td) {
+    if (PACKED) {
+#pragma unroll
+      for (int r = 0; r < 16; ++r)
+        put_packed_elem(reinterpret_cast<bf*>(out), Wd >> 4, (long)b * T + i, hd * ATM_D + 32 * td + acc_row(r, h), o[td][r]);
+    } else {
+      float* op = out + ((long)b * T + i) * Wd + hd * ATM_D + 32 * td;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) op[acc_row(r, h)] = o[td][r];
+    }
+  }
+}
+
+template <bool PACKED>
+__global__ __launch_bounds__(512) void vit_attn_bwd_tiled_kernel(const float* __restrict__ qkv, const float* __restrict__ dout,
+                                                                 float* __restrict__ dqkv, int T, int Wd, int heads, float scale) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int NT = (T + 31) >> 5;
+  // phase 1: K, V [token][d], K^T [d][token]; phase 2 (over them): Q, dO [token][d], Q^T, dO^T [d][token]; the statistics behind both
+  bf (*M0)[ATM_LD] = reinterpret_cast<bf (*)[ATM_LD]>(smem);
+  bf (*M1)[ATM_LD] = reinterpret_cast<bf (*)[ATM_LD]>(smem + ATL_NAT);
+  bf (*T0)[ATL_LDT] = reinterpret_cast<bf (*)[ATL_LDT]>(smem + 2 * ATL_NAT);
+  bf (*T1)[ATL_LDT] = reinterpret_cast<bf (*)[ATL_LDT]>(smem + 2 * ATL_NAT + ATL_TR);
+  float* st_m = reinterpret_cast<float*>(smem + 2 * ATL_NAT + 2 * ATL_TR);
+  float* st_inv = st_m + ATL_TMAX;
+  float* st_d = st_inv + ATL_TMAX;
+  const int b = blockIdx.x / heads, hd = blockIdx.x % heads;
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int n = lane & 31, h = lane >> 5;
+  const float* base = qkv + (long)b * T * 3 * Wd + hd * ATM_D;
+  const float* dob = dout + (long)b * T * Wd + hd * ATM_D;
+  const int own = 32 * wv + n;       // this lane's query (phase 1) / key (phase 2)
+  const bool live = wv < NT;         // the wavefront owns a tile
+  for (int e = threadIdx.x; e < NT * 32 * (ATM_D / 4); e += 512) {
+    const int r = e / (ATM_D / 4), c = 4 * (e % (ATM_D / 4));
+    f4 k = {0.f, 0.f, 0.f, 0.f}, v = k;
+    if (r < T) {
+      const float* rp = base + (long)r * 3 * Wd + c;
+      k = *reinterpret_cast<const f4*>(rp + Wd); v = *reinterpret_cast<const f4*>(rp + 2 * Wd);
+    }
+    put4(&M0[r][c], k); put4(&M1[r][c], v);
+#pragma unroll
+    for (int u = 0; u < 4; ++u) T0[c + u][r] = (bf)k[u];
+  }
+  __syncthreads();
+  if (live) {
+    // ---- phase 1, query tile wv: S^T = K Q^T and dP^T = V dO^T per key tile (lane = query, registers = keys)
+    b8 qf[4], dof[4];
+    row_frags(own < T ? base + (long)own * 3 * Wd : nullptr, h, scale, qf);
+    row_frags(own < T ? dob + (long)own * Wd : nullptr, h, 1.f, dof);
+    float mx = -1e30f, sum = 0.f, dacc = 0.f;
+    for (int tj = 0; tj < NT; ++tj) {
+      facc s = tile_product(M0, 32 * tj + n, qf, h);
+      const facc dp = tile_product(M1, 32 * tj + n, dof, h);
+      float tm = -1e30f;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        s[r] = 32 * tj + acc_row(r, h) < T ? s[r] : -1e30f;
+        tm = fmaxf(tm, s[r]);
+      }
+      tm = fmaxf(tm, __shfl_xor(tm, 32));
+      const float mn = fmaxf(mx, tm), corr = __expf(mx - mn);
+      sum *= corr; dacc *= corr;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const float e = 32 * tj + acc_row(r, h) < T ? __expf(s[r] - mn) : 0.f;
+        sum += e; dacc += e * dp[r];
+      }
+      mx = mn;
+    }
+    sum += __shfl_xor(sum, 32);
+    dacc += __shfl_xor(dacc, 32);
+    const float inv = 1.f / sum, dsum = dacc * inv;      // D = sum_j P dP
+    facc dq[2];
+#pragma unroll
+    for (int td = 0; td < 2; ++td)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) dq[td][r] = 0.f;
+    for (int tj = 0; tj < NT; ++tj) {
+      facc s = tile_product(M0, 32 * tj + n, qf, h);
+      const facc dp = tile_product(M1, 32 * tj + n, dof, h);
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const float p = 32 * tj + acc_row(r, h) < T ? __expf(s[r] - mx) * inv : 0.f;
+        s[r] = p * (dp[r] - dsum);                       // dS^T (w.r.t. the scaled scores)
+      }
+      b8 dsf[2];
+      acc_to_b2(s, scale, dsf);                          // dQ = scale * dS K
+#pragma unroll
+      for (int td = 0; td < 2; ++td)
+#pragma unroll
+        for (int u = 0; u < 2; ++u) dq[td] = MF<b8>::mma(frag_perm_t(T0, 32 * td + n, 2 * tj + u, h), dsf[u], dq[td]);
+    }
+    if (h == 0) { st_m[own] = mx; st_inv[own] = inv; st_d[own] = dsum; }
+    if (own < T) {
+#pragma unroll
+      for (int td = 0; td < 2; ++td) {
+        if (PACKED) {
+#pragma unroll
+          for (int r = 0; r < 16; ++r)
+            put_packed_elem(reinterpret_cast<bf*>(dqkv), (3 * Wd) >> 4, (long)b * T + own, hd * ATM_D + 32 * td + acc_row(r, h), dq[td][r]);
+        } else {
+          float* qp = dqkv + ((long)b * T + own) * 3 * Wd + hd * ATM_D + 32 * td;
+#pragma unroll
+          for (int r = 0; r < 16; ++r) qp[acc_row(r, h)] = dq[td][r];
+        }
+      }
+    }
+  }
+  __syncthreads();                   // every wavefront is done with K, V, K^T
+  for (int e = threadIdx.x; e < NT * 32 * (ATM_D / 4); e += 512) {
+    const int r = e / (ATM_D / 4), c = 4 * (e % (ATM_D / 4));
+    f4 q = {0.f, 0.f, 0.f, 0.f}, d = q;
+    if (r < T) {
+      q = *reinterpret_cast<const f4*>(base + (long)r * 3 * Wd + c) * scale;
+      d = *reinterpret_cast<const f4*>(dob + (long)r * Wd + c);
+    }
+    put4(&M0[r][c], q); put4(&M1[r][c], d);
+#pragma unroll
+    for (int u = 0; u < 4; ++u) { T0[c + u][r] = (bf)q[u]; T1[c + u][r] = (bf)d[u]; }
+  }
+  __syncthreads();
+  if (!live) return;                 // (no barrier below)
+  // ---- phase 2, key tile wv: S = Q K^T and dP = dO V^T per query tile (lane = key, registers = queries), query tiles in order
+  b8 kf[4], vf[4];
+  row_frags(own < T ? base + (long)own * 3 * Wd + Wd : nullptr, h, 1.f, kf);
+  row_frags(own < T ? base + (long)own * 3 * Wd + 2 * Wd : nullptr, h, 1.f, vf);
+  facc dk[2], dv[2];
+#pragma unroll
+  for (int td = 0; td < 2; ++td)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) { dk[td][r] = 0.f; dv[td][r] = 0.f; }
+  for (int ti = 0; ti < NT; ++ti) {
+    facc p = tile_product(M0, 32 * ti + n, kf, h);
+    facc ds = tile_product(M1, 32 * ti + n, vf, h);
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int qi = 32 * ti + acc_row(r, h);
+      p[r] = (qi < T && own < T) ? __expf(p[r] - st_m[qi]) * st_inv[qi] : 0.f;     // rows and columns past T by selection
+      ds[r] = p[r] * (ds[r] - st_d[qi]);
+    }
+    b8 pf[2], dsf[2];
+    acc_to_b2(p, 1.f, pf);
+    acc_to_b2(ds, 1.f, dsf);
+#pragma unroll
+    for (int td = 0; td < 2; ++td)
+#pragma unroll
+      for (int u = 0; u < 2; ++u) {
+        dv[td] = MF<b8>::mma(frag_perm_t(T1, 32 * td + n, 2 * ti + u, h), pf[u], dv[td]);      // dV^T = dO^T P
+        dk[td] = MF<b8>::mma(frag_perm_t(T0, 32 * td + n, 2 * ti + u, h), dsf[u], dk[td]);     // dK^T = Q_scaled^T dS
+      }
+  }
+  if (own >= T) return;
+#pragma unroll
+  for (int td = 0; td < 2; ++td) {
+    if (PACKED) {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int col = hd * ATM_D + 32 * td + acc_row(r, h);
+        put_packed_elem(reinterpret_cast<bf*>(dqkv), (3 * Wd) >> 4, (long)b * T + own, Wd + col, dk[td][r]);
+        put_packed_elem(reinterpret_cast<bf*>(dqkv), (3 * Wd) >> 4, (long)b * T + own, 2 * Wd + col, dv[td][r]);
+      }
+    } else {
+      float* kp = dqkv + ((long)b * T + own) * 3 * Wd + hd * ATM_D + 32 * td;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) { kp[Wd + acc_row(r, h)] = dk[td][r]; kp[2 * Wd + acc_row(r, h)] = dv[td][r]; }
+    }
+  }
+}
+
+template <bool PACKED>
+static int attn_fwd_tiled(const float* qkv, void* out, int B, int T, int width, int heads, void* stream, const char* what) {
+  const int NT = (T + 31) >> 5;
+  const int lds = NT * 32 * ATM_LD * 2 + ATL_TR;
+  static unsigned long long attr_seen = 0;
+  if (avc_first_use_on_device(attr_seen))
+    (void)hipFuncSetAttribute((const void*)vit_attn_fwd_tiled_kernel<PACKED>, hipFuncAttributeMaxDynamicSharedMemorySize, ATL_NAT + ATL_TR);
+  hipLaunchKernelGGL(vit_attn_fwd_tiled_kernel<PACKED>, dim3(B * heads, (NT + 3) / 4), dim3(256), lds, (hipStream_t)stream, qkv, (float*)out, T,
+                     width, heads, 0.125f);
+  return avc_check_launch(what);
+}
+template <bool PACKED>
+static int attn_bwd_tiled(const float* qkv, const float* dout, void* dqkv, int B, int T, int width, int heads, void* stream, const char* what) {
+  static unsigned long long attr_seen = 0;
+  if (avc_first_use_on_device(attr_seen))
+    (void)hipFuncSetAttribute((const void*)vit_attn_bwd_tiled_kernel<PACKED>, hipFuncAttributeMaxDynamicSharedMemorySize, ATL_BWD_LDS);
+  hipLaunchKernelGGL(vit_attn_bwd_tiled_kernel<PACKED>, dim3(B * heads), dim3(512), ATL_BWD_LDS, (hipStream_t)stream, qkv, dout, (float*)dqkv, T,
+                     width, heads, 0.125f);
+  return avc_check_launch(what);
+}
+int avc_attn_fwd_tiled(const float* qkv, float* out, int B, int T, int width, int heads, void* stream) {
+  return attn_fwd_tiled<false>(qkv, out, B, T, width, heads, stream, "avc_vit_attention_fwd");
+}
+int avc_attn_fwd_tiled_packed(const float* qkv, void* out_packed, int B, int T, int width, int heads, void* stream) {
+  return attn_fwd_tiled<true>(qkv, out_packed, B, T, width, heads, stream, "avc_vit_attention_fwd_packed");
+}
+int avc_attn_bwd_tiled(const float* qkv, const float* dout, float* dqkv, int B, int T, int width, int heads, void* stream) {
+  return attn_bwd_tiled<false>(qkv, dout, dqkv, B, T, width, heads, stream, "avc_vit_attention_bwd");
+}
+int avc_attn_bwd_tiled_packed(const float* qkv, const float* dout, void* dqkv_packed, int B, int T, int width, int heads, void* stream) {
+  return attn_bwd_tiled<true>(qkv, dout, dqkv_packed, B, T, width, heads, stream, "avc_vit_attention_bwd_packed");
+}
+
 int avc_attn_fwd_mfma(const float* qkv, float* out, int B, int width, int heads, void* stream) {
   hipLaunchKernelGGL(vit_attn_fwd_mfma_kernel<false>, dim3(B * heads), dim3(256), 0, (hipStream_t)stream, qkv, out, width, heads, 0.125f);
   return avc_check_launch("avc_vit_attention_fwd");

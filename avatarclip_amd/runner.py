@@ -352,7 +352,7 @@ class Runner:
                 if path is not None and os.path.exists(path):
                     clip_state_dict = clip_vit.load_state_dict(path)
                 else:
-                    self._standin("the CLIP ViT-B/32 state dict (clip.weights / $AVC_CLIP_WEIGHTS)")
+                    self._standin("the CLIP ViT-B/32 or ViT-B/16 state dict (clip.weights / $AVC_CLIP_WEIGHTS)")
                     clip_state_dict = clip_vit_random_state_dict(0)
             perceptor = clip_vit.ClipVisionB32(clip_state_dict, self.device)
         self.perceptor = perceptor
@@ -988,10 +988,13 @@ class Runner:
         return path
 
 
-def clip_vit_random_state_dict(seed):
-    """Seeded ViT-B/32 weights with OpenAI's init scales and key names (used only when no real weights are given)."""
+def clip_vit_random_state_dict(seed, patch=32):
+    """Seeded ViT-B/32 (patch=16: ViT-B/16, 197 positional rows) weights with OpenAI's init scales and key names (used only when no
+    real weights are given)."""
+    if patch not in (32, 16):
+        raise ValueError("clip_vit_random_state_dict: patch 32 (ViT-B/32) or 16 (ViT-B/16), got %r" % (patch,))
     g = torch.Generator().manual_seed(seed)
-    W, L, P, T, E = 768, 12, 32, 50, 512
+    W, L, P, T, E = 768, 12, patch, (224 // patch) ** 2 + 1, 512
     rn = lambda *s, std=1.0: torch.randn(*s, generator=g) * std
     sd = {"visual.conv1.weight": rn(W, 3, P, P, std=0.02), "visual.class_embedding": rn(W, std=W ** -0.5),
           "visual.positional_embedding": rn(T, W, std=W ** -0.5), "visual.proj": rn(W, E, std=W ** -0.5)}

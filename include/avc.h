@@ -261,7 +261,8 @@ long avc_vit_workspace_bytes(int M, int K);
  * gradient, hundreds of images: ShapeGen/main.py:104-128, AvatarAnimate pose_generation.py:79-110), forward AND backward up to 128 rows
  * (the per-iteration call of the training loop, main.py:512,524: 1-2 images WITH a gradient to the pixels):
  *   avc_vit_ln_pack               LayerNorm(x[M,768]; gamma, beta, eps) (clip/model.py LayerNorm, fp32 statistics) -> packed
- *   avc_vit_attention_fwd_packed  attention with its output packed for the out-projection (rows = b * 50 + token)
+ *   avc_vit_attention_fwd_packed  attention with its output packed for the out-projection (rows = b * T + token; 1 <= T <= 256 as
+ *                                 avc_vit_attention_fwd; rows past B * T of the last row tile are not written)
  *   avc_vit_pack                  fp32 rows (optionally times QuickGELU'(gelu_pre)) -> packed operand
  *   avc_vit_linear_packed         y = f(xs W^T + b) (+ residual) from a packed operand; act 0 identity, 1 QuickGELU (y_pre, if given,
  *                                 receives the pre-activation), 2 times QuickGELU'(gelu_pre[M,N]) (backward of a QuickGELU layer; act 2
@@ -277,15 +278,21 @@ int avc_vit_linear_packed(const void* xs_packed, const void* w_packed, const flo
                           float* y, float* y_pre, void* ys_packed, int M, int N, int K, int act, void* stream);
 int avc_vit_attention_fwd_packed(const float* qkv, void* out_packed, int B, int T, int width, int heads, void* stream);
 int avc_vit_pack(const float* x, const float* gelu_pre, void* xs_packed, int M, int K, void* stream);
-/* avc_vit_attention_bwd with dqkv leaving as the packed operand ([B * 50, 3 W]) of the transposed in-projection */
+/* avc_vit_attention_bwd with dqkv leaving as the packed operand ([B * T, 3 W]; 1 <= T <= 256; T = 50 is ViT-B/32, 197 is ViT-B/16) of
+ * the transposed in-projection; rows past B * T of the last row tile are not written (the convention of avc_vit_ln_bwd) */
 int avc_vit_attention_bwd_packed(const float* qkv, const float* dout, void* dqkv_packed, int B, int T, int width, int heads, void* stream);
 int avc_vit_ln_bwd(const float* dy, const float* x, const float* gamma, float eps, const float* residual_grad, float* dx,
                    void* xs_packed, int M, int K, void* stream);
-/* multi-head self-attention of ResidualAttentionBlock over T=50 tokens, head dim 64: qkv[B,T,3W] -> out[B,T,W] */
+/* multi-head self-attention of ResidualAttentionBlock over 1 <= T <= 256 tokens (T = 50 is ViT-B/32, 197 is ViT-B/16), head dim 64,
+ * width == heads * 64: qkv[B,T,3W] -> out[B,T,W].  bf16 operands on the matrix core, fp32 accumulation and softmax statistics; T = 50
+ * runs in one 64-key tile, every other T in 32-key tiles; another T or head dim returns 1.  No atomics: an image's result is the same
+ * bits in every run, every batch and at every place in a batch. */
 int avc_vit_attention_fwd(const float* qkv, float* out, int B, int T, int width, int heads, void* stream);
 /* text tower (perceptor.encode_text, main.py:276-288; clip/model.py): self-attention over T <= 128 tokens, head dim 64, with
  * the causal mask of CLIP's text transformer when `causal` != 0.  Forward only (prompts are encoded once, detached). */
 int avc_text_attention_fwd(const float* qkv, float* out, int B, int T, int width, int heads, int causal, void* stream);
+/* its backward: dout[B,T,W] -> dqkv[B,T,3W] (q, k, v gradients side by side as in qkv); 1 <= T <= 256 as above, the softmax is recomputed
+ * from qkv */
 int avc_vit_attention_bwd(const float* qkv, const float* dout, float* dqkv, int B, int T, int width, int heads,
                           void* stream);
 
