@@ -516,12 +516,22 @@ class Engine:
         return grad
 
 
+def eikonal_from_sums(sums, group):
+    """sums [2] = this rank's (sum of the eikonal terms, sum of their weights) -> (gradient_error, its denominator) of the whole view:
+    one all-reduce over `group`, then renderer.py:283-285's quotient.  A rank without rays passes zeros."""
+    import torch.distributed as dist
+    dist.all_reduce(sums, op=dist.ReduceOp.SUM, group=group)
+    den = sums[1] + 1e-5
+    return sums[0] / den, den
+
+
 class RenderCoreFn(torch.autograd.Function):
     """render_core (renderer.py:195-300) on fixed z_vals: fused point MLP + compositing, differentiable wrt the
-    flat dense parameter vector and inv_s."""
+    flat dense parameter vector and inv_s.  `group`: the process group the view's rays are spread over (train.shard_view), None
+    for a ray set that is the whole view -- it touches the eikonal term alone, every other output is per ray."""
 
     @staticmethod
-    def forward(ctx, flatP, inv_s, eng, rays_o, rays_d, z_vals, sample_dist, cos_anneal, bg, bg_mode):
+    def forward(ctx, flatP, inv_s, eng, rays_o, rays_d, z_vals, sample_dist, cos_anneal, bg, bg_mode, group=None):
         pk = eng.pack(flatP)
         inv_s_d = inv_s.detach().float().contiguous()
         R, S = z_vals.shape
@@ -537,8 +547,14 @@ class RenderCoreFn(torch.autograd.Function):
             sdf, nrm, rgb, z_vals, rays_o, rays_d, inv_s_d, sample_dist, cos_anneal, bg, bg_mode)
         wsum, wmax = wstat[0].reshape(R, 1), wstat[1].reshape(R, 1)       # (planar: views, no copies)
         eo = torch.empty(2, device=eik.device, dtype=torch.float32)        # renderer.py:283-285 in one launch: (gradient_error, its denominator)
-        L.call("avc_colsum", eik, R, 2, 1, eo, eng.colsum_scratch())
-        gerr, eik_den = eo[0], eo[1]
+        if group is None:
+            L.call("avc_colsum", eik, R, 2, 1, eo, eng.colsum_scratch())
+            gerr, eik_den = eo[0], eo[1]
+        else:
+            # the rays of one view over the ranks of `group` (train.shard_view): the eikonal term is the view's -- the raw sums of
+            # this rank's rays, added up over the ranks, then the same quotient; the backward scales by the GLOBAL denominator
+            L.call("avc_colsum", eik, R, 2, 0, eo, eng.colsum_scratch())
+            gerr, eik_den = eikonal_from_sums(eo, group)
         ctx.eng, ctx.pk = eng, pk
         ctx.consts = (sample_dist, cos_anneal, bg_mode)
         ctx.save_for_backward(rays_o, rays_d, z_vals, sdf, nrm, rgb, inv_s_d, eik_den, bg if bg is not None else inv_s_d)
@@ -576,4 +592,4 @@ class RenderCoreFn(torch.autograd.Function):
         grad = eng.points_bwd(pk, rays_o, rays_d, z_vals, sample_dist, d_sdf, d_n, d_rgb, rgb, panels_valid=valid)
         d_inv_s = torch.empty(1, device=d_inv.device, dtype=torch.float32)
         L.call("avc_colsum", d_inv, R, 1, 0, d_inv_s, eng.colsum_scratch())
-        return grad, d_inv_s, None, None, None, None, None, None, None, None
+        return grad, d_inv_s, None, None, None, None, None, None, None, None, None

@@ -1,7 +1,8 @@
 """CLI with the reference's flags (AvatarGen/AppearanceGen/main.py:947-980):
    python -m avatarclip_amd.main --mode {train,train_clip,validate_mesh,render_geometry_cast_light,interpolate_i_j} --conf X [--is_continue] [--gpu N] [--case NAME]
 Multi-GPU (view-sharded): torchrun --nproc-per-node N -m avatarclip_amd.main --mode train_clip --conf X
-Views per optimisation step (train.views_per_iter; default one per rank): --views_per_iter V, on any number of ranks that divides V"""
+Views per optimisation step (train.views_per_iter; default one per rank): --views_per_iter V, on any number of ranks that divides V
+One view's rays over the ranks (train.shard_view): --shard_view; views_per_iter then defaults to 1 and every view is cut over all ranks"""
 import argparse
 import logging
 
@@ -29,13 +30,16 @@ def main():
     parser.add_argument("--views_per_iter", type=int, default=None,
                         help="camera views per optimisation step over all ranks (a multiple of the number of ranks); overrides "
                              "train.views_per_iter of the conf; default: one view per rank")
+    parser.add_argument("--shard_view", default=None, action="store_true",
+                        help="cut the rays of each view over the ranks by pixel range instead of one view per rank (the one-view "
+                             "optimisation of the reference confs on N devices); overrides train.shard_view of the conf")
     args = parser.parse_args()
     rank, world, local_rank = parallel.init_from_env()
     torch.cuda.set_device(local_rank if world > 1 else args.gpu)
     if args.mode in ("validate_mesh", "render_geometry_cast_light"):
         args.is_continue = True
     runner = Runner(args.conf, args.mode, args.case, args.is_continue, allow_standins=args.allow_standins or None,
-                    views_per_iter=args.views_per_iter)
+                    views_per_iter=args.views_per_iter, shard_view=args.shard_view)
     if args.mode == "validate_mesh":   # main.py:972-974
         runner.validate_mesh(world_space=True, resolution=512, threshold=args.mcube_threshold)
         runner.render_geometry_cast_light()

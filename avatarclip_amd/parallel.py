@@ -1,15 +1,18 @@
 """View-sharded data parallelism: one process per GPU, rank r of W renders the views {r, r+W, ...} of
 a step's train.views_per_iter (default W: one each), ONE flat-bucket all-reduce of the ~400k fp32 gradients per step (1.6 MB: latency-bound on xGMI, so a single bucket
 and no overlap machinery), identical Adam step on every rank.  backend "nccl" is RCCL on ROCm; "gloo" is used by
-the CPU tests."""
+the CPU tests.  train.shard_view: the rays of ONE view over the ranks instead -- the cut (shard_ranges) and the collectives of the three
+quantities that are the view's and not the rank's (allreduce_sum, PixelGather; the eikonal sums: engine.RenderCoreFn)."""
+import datetime
 import os
 
 import torch
 import torch.distributed as dist
 
 
-def init_from_env(backend=None):
-    """Initialise torch.distributed from RANK / WORLD_SIZE / MASTER_* (torchrun).  Returns (rank, world, local_rank)."""
+def init_from_env(backend=None, timeout=None):
+    """Initialise torch.distributed from RANK / WORLD_SIZE / MASTER_* (torchrun).  Returns (rank, world, local_rank).  `timeout`
+    (seconds): how long a collective waits for its peers before it raises (default: the backend's)."""
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -29,7 +32,8 @@ def init_from_env(backend=None):
             backend = os.environ.get("AVC_DIST_BACKEND") or ("nccl" if torch.cuda.is_available() else "gloo")
         if backend == "nccl":
             torch.cuda.set_device(local_rank)
-        dist.init_process_group(backend=backend, rank=rank, world_size=world)
+        kw = {} if timeout is None else {"timeout": datetime.timedelta(seconds=timeout)}
+        dist.init_process_group(backend=backend, rank=rank, world_size=world, **kw)
     return rank, world, local_rank
 
 
@@ -232,6 +236,91 @@ def allreduce_grads(params, world=None):
         n = g.numel()
         g.copy_(flat[off:off + n].view_as(g))
         off += n
+
+
+# ---------------------------------------------------------------------- train.shard_view: one view's rays over the ranks
+# (DESIGN.md section 6).  Every rank builds the same view and renders the rays of its own pixel range; what is global in the loss --
+# the eikonal sums, the four loss sums, the CLIP images -- crosses the ranks through the three functions below.  `group` = None
+# everywhere means "no collective" (one process, or the mode off): the argument comes back untouched, nothing is launched.
+
+def shard_group():
+    """the process group a sharded view's collectives run on: the world, or None where there is no process group or one rank"""
+    if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+        return dist.group.WORLD
+    return None
+
+
+def shard_ranges(world, n_pixels, sel_idx=None):
+    """The cut of one view over `world` ranks -> (q, p): rank r owns the rays [q[r], q[r + 1]) and the row-major pixels
+    [p[r], p[r + 1]) of the H x W grid; the pixel ranges tile [0, n_pixels).  Full frame (sel_idx None: ray i is pixel i): ranges as
+    equal as possible.  Silhouette mode (sel_idx = the ascending pixel positions of the R rays): the cuts lie at the ray quantiles
+    r * R // world, so the ray counts differ by at most one, and a rank's rays are exactly those whose pixels lie in its range; a rank
+    without rays (R < world) gets an empty pixel range.  One host transfer of world - 1 positions in that mode, none otherwise."""
+    if sel_idx is None:
+        p = [r * n_pixels // world for r in range(world + 1)]
+        return p, p
+    R = int(sel_idx.numel())
+    q = [r * R // world for r in range(world + 1)]
+    inner = [k for k in q[1:-1] if k > 0]
+    at = sel_idx[torch.as_tensor(inner, dtype=torch.long, device=sel_idx.device)].tolist() if inner else []
+    p = [0] * (world - len(inner)) + [int(v) for v in at] + [n_pixels]
+    return q, p
+
+
+class _AllReduceSum(torch.autograd.Function):
+    """y = sum over the ranks of x.  Every rank goes on to compute the SAME loss from y, and the bucket adds the ranks' parameter
+    gradients up: the gradient a rank owes for its own x is d loss / d y, so the backward is the identity, without a collective."""
+
+    @staticmethod
+    def forward(ctx, x, group):
+        y = x.detach().clone()
+        dist.all_reduce(y, op=dist.ReduceOp.SUM, group=group)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        return dy, None
+
+
+def allreduce_sum(x, group=None):
+    return x if group is None else _AllReduceSum.apply(x, group)
+
+
+class _GatherPixels(torch.autograd.Function):
+    """x [B, n_r, C], the rank's pixel range of B images -> the whole images [B, P, C] on every rank.  The ranges are padded to one
+    size so that the all-gather is uniform (every rank sends n_max pixels); send and receive buffers are the caller's, kept from
+    step to step.  Backward: the rank's own range of the image gradient -- the other ranks' ranges are their rays' business."""
+
+    @staticmethod
+    def forward(ctx, x, p, rank, group, bufs):
+        world, B, C = len(p) - 1, x.shape[0], x.shape[2]
+        n_max = max(p[r + 1] - p[r] for r in range(world))
+        send, recv = bufs(B * n_max * C, world, x)
+        send = send.view(B, n_max, C)
+        send[:, :x.shape[1]].copy_(x.detach())
+        dist.all_gather(list(recv.view(world, B, n_max, C).unbind(0)), send, group=group)
+        ctx.range = (p[rank], p[rank + 1])
+        return torch.cat([recv.view(world, B, n_max, C)[r, :, :p[r + 1] - p[r]] for r in range(world)], dim=1)
+
+    @staticmethod
+    def backward(ctx, dy):
+        return dy[:, ctx.range[0]:ctx.range[1]], None, None, None, None
+
+
+class PixelGather:
+    """gather_pixels with its two staging buffers (grown when a view needs more, never shrunk)"""
+
+    def __init__(self):
+        self.send = self.recv = None
+
+    def _bufs(self, n, world, like):
+        if self.send is None or self.send.numel() < n or self.send.device != like.device:
+            self.send = torch.zeros(n, dtype=like.dtype, device=like.device)
+            self.recv = torch.zeros(world * n, dtype=like.dtype, device=like.device)
+        return self.send[:n], self.recv[:world * n]
+
+    def __call__(self, x, p, rank, group=None):
+        return x if group is None else _GatherPixels.apply(x, p, rank, group, self._bufs)
 
 
 def barrier():

@@ -86,7 +86,7 @@ class NeuSRenderer:
                 z, sdf = z_out, sdf_out
         return (z, steps) if return_steps else z
 
-    def render_core(self, rays_o, rays_d, z_vals, sample_dist, background_rgb=None, cos_anneal_ratio=0.0, flatP=None):
+    def render_core(self, rays_o, rays_d, z_vals, sample_dist, background_rgb=None, cos_anneal_ratio=0.0, flatP=None, group=None):
         eng = self.engine
         if flatP is None:
             flatP = self.flat_params()
@@ -103,7 +103,7 @@ class NeuSRenderer:
             else:
                 raise ValueError("background_rgb must be [1,3] or [R,1] (main.py:387-415)")
         color, extra, weights, gradients, gerr, cdf, mid_z, inside, sdf, wsum, wmax, nsum = RenderCoreFn.apply(
-            flatP, inv_s, eng, rays_o, rays_d, z_vals, float(sample_dist), float(cos_anneal_ratio), bg, bg_mode)
+            flatP, inv_s, eng, rays_o, rays_d, z_vals, float(sample_dist), float(cos_anneal_ratio), bg, bg_mode, group)
         if not self.extra_color:
             extra = None
             if background_rgb is not None:  # renderer.py:280-281
@@ -113,9 +113,10 @@ class NeuSRenderer:
                 "gradient_error": gerr, "inside_sphere": inside, "weight_sum": wsum, "weight_max": wmax, "weighted_normals": nsum}
 
     def render(self, rays_o, rays_d, near, far, perturb_overwrite=-1, background_rgb=None, cos_anneal_ratio=0.0,
-               jitter=None, z_vals=None):
+               jitter=None, z_vals=None, group=None):
         """Same contract as the reference (renderer.py:302-397).  `jitter` ([R,1] uniform) and `z_vals` are
-        optional injection points used by the parity tests; they default to the reference behaviour."""
+        optional injection points used by the parity tests; they default to the reference behaviour.  `group`: the rays are one
+        rank's share of a view (train.shard_view) -- the eikonal term is reduced over that process group (engine.RenderCoreFn)."""
         rays_o = rays_o.contiguous().float()
         rays_d = rays_d.contiguous().float()
         sample_dist = 2.0 / self.n_samples
@@ -125,7 +126,7 @@ class NeuSRenderer:
             pk = self.engine.pack(flatP)
             z_vals = self.sample_z(pk, rays_o, rays_d, near.float(), far.float(), perturb, jitter)
         z_vals = z_vals.contiguous()
-        ret = self.render_core(rays_o, rays_d, z_vals, sample_dist, background_rgb, cos_anneal_ratio, flatP)
+        ret = self.render_core(rays_o, rays_d, z_vals, sample_dist, background_rgb, cos_anneal_ratio, flatP, group)
         weights = ret["weights"]
         R, S = weights.shape
         out = RenderOut({

@@ -6,6 +6,8 @@ Differences that are deliberate and documented:
     initialised every rank draws its own camera and ONE flat-bucket all-reduce (RCCL over xGMI) averages the
     gradients before the identical Adam step; `train.views_per_iter = V` sets the number of views per step
     independently of the number of ranks (rank r of W renders the views r, r + W, ... one after the other; DESIGN.md section 6);
+    `train.shard_view = true` instead cuts the rays of each view over the ranks by pixel range: every rank draws the same view and
+    renders 1/W of it, which is the reference's one-view optimisation on W devices (_clip_loss_sharded);
   * the SMPL silhouette prior (smplx + neural_renderer, main.py:290-335,360) is rendered by the HIP rasteriser of
     smpl_prior.py from a posed mesh (`general.smpl_mesh`, an .obj, or `init_smpl(prior_renderer=...)`); the licensed SMPL
     pickles stay an input.  Seeded CLIP weights, seeded text embeddings, the procedural ellipsoid prior and a missing
@@ -87,7 +89,7 @@ class ScalarLog:
 
 class Runner:
     def __init__(self, conf_path, mode="train", case="CASE_NAME", is_continue=False, is_colab=False, conf=None,
-                 device=None, data_root=None, allow_standins=None, views_per_iter=None):
+                 device=None, data_root=None, allow_standins=None, views_per_iter=None, shard_view=None):
         if device is None:
             if not torch.cuda.is_available():
                 raise RuntimeError("avatarclip_amd.Runner needs an MI355X (torch.cuda) -- the hot path has no CPU fallback")
@@ -102,8 +104,24 @@ class Runner:
         self.rank, self.world = parallel.rank_world()
         # train.views_per_iter: camera views per optimisation step over ALL ranks (default: one per rank).  The argument overrides the conf.
         V = self.conf.get_int("train.views_per_iter", default=None) if views_per_iter is None else views_per_iter
-        self.views_per_iter = self.world if V is None else int(V)
-        if self.views_per_iter <= 0 or self.views_per_iter % self.world != 0:
+        # train.shard_view: the rays of ONE view are cut over the ranks by pixel range instead of every rank
+        # rendering views of its own.  All ranks then build the same views from the same data streams: for the views, the job is one
+        # process (_view_rank of _view_world), and views_per_iter defaults to 1.  The argument overrides the conf.
+        self.shard_view = bool(self.conf.get_bool("train.shard_view", default=False) if shard_view is None else shard_view)
+        if self.shard_view and mode == "train":
+            raise ValueError("train.shard_view with mode 'train': that mode draws pixels of stored images, not camera views; "
+                             "the key applies to mode 'train_clip' only")
+        self._view_rank, self._view_world = (0, 1) if self.shard_view else (self.rank, self.world)
+        self._shard_group = parallel.shard_group() if self.shard_view else None     # None: one rank, nothing to cut
+        self._gather_pixels = parallel.PixelGather()
+        if self.shard_view:
+            self.views_per_iter = 1 if V is None else int(V)
+            if self.views_per_iter <= 0:
+                raise ValueError("train.views_per_iter = %d must be positive (train.shard_view: each view is cut over all %d ranks)"
+                                 % (self.views_per_iter, self.world))
+        else:
+            self.views_per_iter = self.world if V is None else int(V)
+        if self.views_per_iter <= 0 or self.views_per_iter % self._view_world != 0:
             raise ValueError("train.views_per_iter = %d must be a positive multiple of the world size %d (rank r renders the views r, r + %d, ...)"
                              % (self.views_per_iter, self.world, self.world))
         if mode == "train" and self.views_per_iter != self.world:
@@ -167,7 +185,7 @@ class Runner:
         params_to_train = list(self.sdf_network.parameters()) + list(self.deviation_network.parameters()) + \
             list(self.color_network.parameters())
         self.params_to_train = params_to_train
-        several = self.views_per_iter != self.world     # more than one view per rank and step
+        several = self.views_per_iter != self._view_world     # more than one view per rank and step
         if parallel.is_on():
             parallel.broadcast_params(params_to_train)
         if parallel.is_on() or several:
@@ -213,15 +231,16 @@ class Runner:
         gradients.  Rank r > 0 re-seeds its data RNGs with seed + r (rank 0 keeps the single-GPU stream); without
         train.seed a base seed is drawn on rank 0 and broadcast (without a process group: drawn here).  With train.views_per_iter = V
         the streams belong to the VIEWS: view j of a step draws from the streams seeded base + j, whichever rank renders it; the
-        process's own streams are those of its first view, j = rank (_fresh_view_rngs makes the others)."""
+        process's own streams are those of its first view, j = rank (_fresh_view_rngs makes the others).  With train.shard_view every
+        rank builds every view, so every rank is rank 0 here: one set of streams, those of a single process."""
         base = self.seed
         if base is None:
             t = torch.tensor([int(np.random.randint(0, 2 ** 31 - 1))], dtype=torch.int64, device=self.device)
             parallel.broadcast_tensor(t)
             base = int(t.item())
         self.base_seed = base
-        self.data_seed = base + self.rank
-        if self.rank > 0 or self.seed is None:
+        self.data_seed = base + self._view_rank
+        if self._view_rank > 0 or self.seed is None:
             np.random.seed(self.data_seed); random.seed(self.data_seed)
             torch.manual_seed(self.data_seed)
             if self.device.type == "cuda":
@@ -243,7 +262,7 @@ class Runner:
         seed_data_rngs makes, taken as states, the process's own streams put back"""
         mine = self._data_rng_state()
         out = []
-        for j in range(self.rank + self.world, self.views_per_iter, self.world):
+        for j in range(self._view_rank + self._view_world, self.views_per_iter, self._view_world):
             np.random.seed(self.base_seed + j); random.seed(self.base_seed + j)
             torch.manual_seed(self.base_seed + j)
             if self.device.type == "cuda":
@@ -256,13 +275,20 @@ class Runner:
         """main.py:247-251 / 556-561: periodic images and meshes (rank 0)."""
         if self.rank != 0:
             return
-        if self.val_freq > 0 and self.iter_step % self.val_freq == 0:
-            if clip_stage:
-                self.validate_image(idx=58 if self.dataset.n_images > 58 else -1, save=True)
-            else:
-                self.validate_image(save=True)
-        if self.val_mesh_freq > 0 and self.iter_step % self.val_mesh_freq == 0:
-            self.validate_mesh()
+        # train.shard_view: the ranks cut the SAME view, so their data streams must stay in step; what rank 0 alone draws here (the
+        # validation camera, the jitter of its render) is taken from a copy of the streams and the streams are put back
+        held = self._data_rng_state() if self._shard_group is not None else None
+        try:
+            if self.val_freq > 0 and self.iter_step % self.val_freq == 0:
+                if clip_stage:
+                    self.validate_image(idx=58 if self.dataset.n_images > 58 else -1, save=True)
+                else:
+                    self.validate_image(save=True)
+            if self.val_mesh_freq > 0 and self.iter_step % self.val_mesh_freq == 0:
+                self.validate_mesh()
+        finally:
+            if held is not None:
+                self._set_data_rng_state(held)
 
     def _after_step(self, loss, clip_stage):
         """main.py:240-253 / 549-563: report, checkpoint, validation, next learning rate"""
@@ -486,9 +512,33 @@ class Runner:
         if sel_idx is not None and dev.type == "cuda":     # pixel -> ray (or -1): what the fused glue scatters with (glue.ShadeLossFn)
             ray_of_pixel = torch.full((H * W,), -1, dtype=torch.int32, device=dev)
             ray_of_pixel[sel_idx] = torch.arange(sel_idx.numel(), dtype=torch.int32, device=dev)
-        return types.SimpleNamespace(eye=eye, at=at, theta=theta, phi=phi, is_front=is_front, pose=pose, H=H, W=W,
+        view = types.SimpleNamespace(eye=eye, at=at, theta=theta, phi=phi, is_front=is_front, pose=pose, H=H, W=W,
                                      rays_o=rays_o, rays_d=rays_d, near=near, far=far, true_rgb=true_rgb, mask=mask,
                                      dilated_mask=dilated_mask, sel_idx=sel_idx, ray_of_pixel=ray_of_pixel, mask_binary=True)
+        if self._shard_group is not None:      # (here, so that the silhouette mode's cut positions come to the host with the view's other round trips)
+            view.ray_cuts, view.pixel_cuts = parallel.shard_ranges(self.world, H * W, sel_idx)
+        return view
+
+    def shard_of_view(self, view, rank=None):
+        """train.shard_view: rank `rank`'s part of `view` -- the rays [q0, q1) and the row-major pixels [p0, p1) of parallel.shard_ranges --
+        as a view of its own whose tensors are slices.  Its pixel grid is the range itself, H = p1 - p0 rows of W = 1 pixel, with
+        sel_idx / ray_of_pixel / dilated_mask local to it, so that the per-pixel statements (shade_and_scatter, glue.ShadeLossFn)
+        apply unchanged; `full_hw` and `pixel_cuts` say where the range lies in the image that CLIP sees."""
+        r = self.rank if rank is None else rank
+        (q0, q1), (p0, p1) = view.ray_cuts[r:r + 2], view.pixel_cuts[r:r + 2]
+        n = p1 - p0
+        sel_idx = ray_of_pixel = dilated_mask = None
+        if view.sel_idx is not None:
+            sel_idx = view.sel_idx[q0:q1] - p0
+            dilated_mask = view.dilated_mask.reshape(-1)[p0:p1].reshape(n, 1)
+            if view.ray_of_pixel is not None:
+                ray_of_pixel = torch.full((n,), -1, dtype=torch.int32, device=self.device)
+                ray_of_pixel[sel_idx] = torch.arange(q1 - q0, dtype=torch.int32, device=self.device)
+        return types.SimpleNamespace(eye=view.eye, at=view.at, theta=view.theta, phi=view.phi, is_front=view.is_front, pose=view.pose, H=n, W=1,
+                                     rays_o=view.rays_o[q0:q1], rays_d=view.rays_d[q0:q1], near=view.near[q0:q1], far=view.far[q0:q1],
+                                     true_rgb=view.true_rgb[p0:p1], mask=view.mask[p0:p1], dilated_mask=dilated_mask, sel_idx=sel_idx,
+                                     ray_of_pixel=ray_of_pixel, mask_binary=view.mask_binary, rays=(q0, q1), pixels=(p0, p1),
+                                     full_hw=(view.H, view.W), pixel_cuts=view.pixel_cuts, rank=r)
 
     def _take_view(self, iter_i, camera=None):
         """the view of this iteration: in silhouette mode on the GPU it is built on the side stream (overlap_view = False: on one stream)"""
@@ -616,18 +666,40 @@ class Runner:
                     texture_shading=texture_shading, rand_shading_rgb=rand_shading_rgb)
 
     def assemble_loss(self, render_out, comp, view, iter_i):
-        """main.py:489-534."""
+        """main.py:489-534.  train.shard_view (`view` = this rank's pixel range, shard_of_view): the sums of the colour and mask terms
+        over the range are added up over the ranks -- the BCE mean written as its sum over the P pixels of the whole view -- and the
+        images are gathered, so that every rank computes the view's loss; `render_out` may be None on a rank without rays."""
         H, W = view.H, view.W
+        group = self._shard_group if hasattr(view, "full_hw") else None
         mask = self._loss_mask(view.mask)
-        mask_sum = mask.sum() + 1e-5
-        color_error = (comp["color_fine"] - view.true_rgb) * mask
-        color_fine_loss = F.l1_loss(color_error, torch.zeros_like(color_error), reduction="sum") / mask_sum
-        psnr = None
-        if self.writer is not None:   # main.py:493 (a logged statistic only: not computed when nothing records it)
-            with torch.no_grad():
-                psnr = 20.0 * torch.log10(1.0 / (((comp["color_fine"] - view.true_rgb) ** 2 * mask).sum() / (mask_sum * 3.0)).sqrt())
-        eikonal_loss = render_out["gradient_error"]
-        mask_loss = F.binary_cross_entropy(comp["weight_sum"].clip(1e-3, 1.0 - 1e-3), mask)
+        if group is None:
+            mask_sum = mask.sum() + 1e-5
+            color_error = (comp["color_fine"] - view.true_rgb) * mask
+            color_fine_loss = F.l1_loss(color_error, torch.zeros_like(color_error), reduction="sum") / mask_sum
+            psnr = None
+            if self.writer is not None:   # main.py:493 (a logged statistic only: not computed when nothing records it)
+                with torch.no_grad():
+                    psnr = 20.0 * torch.log10(1.0 / (((comp["color_fine"] - view.true_rgb) ** 2 * mask).sum() / (mask_sum * 3.0)).sqrt())
+            eikonal_loss = render_out["gradient_error"]
+            mask_loss = F.binary_cross_entropy(comp["weight_sum"].clip(1e-3, 1.0 - 1e-3), mask)
+        else:
+            H, W = view.full_hw
+            color_error = (comp["color_fine"] - view.true_rgb) * mask
+            sums = parallel.allreduce_sum(torch.stack([
+                F.l1_loss(color_error, torch.zeros_like(color_error), reduction="sum"), mask.sum(),
+                F.binary_cross_entropy(comp["weight_sum"].clip(1e-3, 1.0 - 1e-3), mask, reduction="sum"),
+                ((comp["color_fine"] - view.true_rgb) ** 2 * mask).sum().detach()]), group)
+            mask_sum = sums[1] + 1e-5
+            color_fine_loss, mask_loss = sums[0] / mask_sum, sums[2] / (H * W)
+            psnr = None
+            if self.writer is not None:
+                with torch.no_grad():
+                    psnr = 20.0 * torch.log10(1.0 / (sums[3] / (mask_sum * 3.0)).sqrt())
+            eikonal_loss = view.eikonal
+            B = 2 if self.add_no_texture else 1
+            names = ["texture_shading" if self.texture_cast_light else "extra_color_fine"] + (["rand_shading_rgb"] if B == 2 else [])
+            images = self._gather_pixels(torch.stack([comp[k] for k in names]), view.pixel_cuts, view.rank, group)
+            comp = dict(comp, **{k: images[i] for i, k in enumerate(names)})
         text = self._prompt_for(iter_i, view)
         img = comp["texture_shading"] if self.texture_cast_light else comp["extra_color_fine"]
         if self.add_no_texture:
@@ -645,7 +717,7 @@ class Runner:
             cosine_shading = torch.cosine_similarity(torch.mean(enc2, dim=0), torch.mean(text, dim=0), dim=0)
             loss = loss + (1.0 - cosine_shading) * self.clip_weight
         return loss, dict(color=color_fine_loss, eikonal=eikonal_loss, mask=mask_loss, cosine=cosine, cosine_shading=cosine_shading,
-                          psnr=psnr, s_val=render_out["s_val"][:1].mean())
+                          psnr=psnr, s_val=render_out["s_val"][:1].mean() if render_out is not None else self._s_val())
 
     def fused_shade_loss(self, render_out, view, choice_i, background_rgb, iter_i, light=None):
         """shade_and_scatter + assemble_loss (main.py:422-534) through the two fused kernels of glue.py: same host draws in the same
@@ -653,13 +725,19 @@ class Runner:
         (tests/test_gpu_glue.py: values and gradients against the torch statement)."""
         from . import glue
         dev, H, W = self.device, view.H, view.W
+        # train.shard_view: `view` is this rank's pixel range of the image (shard_of_view) -- shading, scatter and the per-pixel loss
+        # terms run on the range; the four sums and the images become the whole view's before the loss tail and CLIP see them.  A rank
+        # without pixels (render_out None) makes the same host draws and joins the same collectives with nothing.
+        group = self._shard_group if hasattr(view, "full_hw") else None
+        if group is not None:
+            H, W = view.full_hw
         P = H * W
         shading = self.add_no_texture or self.texture_cast_light
         light4 = nsum = None
         if shading:
             light_dir, ambience = self._draw_light(view) if light is None else (np.asarray(light[0]), float(light[1]))
             light4 = h2d.upload(glue.unit_light(light_dir, ambience), dev)
-            nsum = self._weighted_normals(render_out)
+            nsum = self._weighted_normals(render_out) if render_out is not None else None
         bg, bg_const, rop = None, 0.0, None
         if self.use_silhouettes:
             rop = view.ray_of_pixel
@@ -669,24 +747,33 @@ class Runner:
                 bg = background_rgb.reshape(-1)
         # main.py:489: (mask > 0.5).float() is the identity on the 0 / 1 masks make_view produces
         mask = view.mask if self.mask_weight > 0.0 and getattr(view, "mask_binary", False) else self._loss_mask(view.mask)
-        images, sums = glue.ShadeLossFn.apply(
-            render_out["color_fine"], render_out["extra_color_fine"], render_out["weight_sum"].reshape(-1), nsum, view.true_rgb,
-            mask.reshape(-1), rop, bg, bg_const, light4, not self.texture_cast_light)
+        B = 2 if self.add_no_texture else 1
+        if render_out is None:
+            images, sums = torch.zeros(2, 0, 3, device=dev), torch.zeros(4, device=dev)
+            eikonal_loss, s_val = view.eikonal, self._s_val()
+        else:
+            images, sums = glue.ShadeLossFn.apply(
+                render_out["color_fine"], render_out["extra_color_fine"], render_out["weight_sum"].reshape(-1), nsum, view.true_rgb,
+                mask.reshape(-1), rop, bg, bg_const, light4, not self.texture_cast_light)
+            eikonal_loss, s_val = render_out["gradient_error"], render_out["s_val"][0, 0]
+        if group is not None:
+            sums = parallel.allreduce_sum(sums, group)
+            images = self._gather_pixels(images[:B], view.pixel_cuts, view.rank, group)
         psnr = None
         if self.writer is not None:   # main.py:493 (a logged statistic only)
             with torch.no_grad():
                 psnr = 20.0 * torch.log10(1.0 / (sums[3] / ((sums[1] + 1e-5) * 3.0)).sqrt())
-        eikonal_loss = render_out["gradient_error"]
         text = self._prompt_for(iter_i, view)
-        B = 2 if self.add_no_texture else 1
         enc_both = self.perceptor.encode_image(glue.ResizeNormFn.apply(images[:B].reshape(B, H, W, 3)))
         # main.py:491-534 from here on (colour / mask normalisation, the cosines, the weighted sum) in one launch: glue.LossTailFn
         loss, st = glue.LossTailFn.apply(enc_both, text, sums, eikonal_loss, self.igr_weight, self.mask_weight, self.clip_weight, P)
         return loss, dict(color=st[1], eikonal=eikonal_loss, mask=st[2], cosine=st[3], cosine_shading=st[4] if self.add_no_texture else None,
-                          psnr=psnr, s_val=render_out["s_val"][0, 0]), images
+                          psnr=psnr, s_val=s_val), images
 
     def clip_loss(self, iter_i, camera=None):
         """main.py:348-534: one view from camera to scalar loss (differentiable)."""
+        if self._shard_group is not None:
+            return self._clip_loss_sharded(iter_i, camera)
         view = self._take_view(iter_i, camera)
         choice_i, background_rgb, masked_background_rgb = self.draw_background(view)
         render_out = self.renderer.render(view.rays_o, view.rays_d, view.near, view.far, background_rgb=masked_background_rgb,
@@ -700,6 +787,65 @@ class Runner:
         self.last_view = view
         return loss, parts
 
+    def _s_val(self):
+        """the statistic render() reports as s_val (renderer.py:288), for a rank that rendered nothing"""
+        with torch.no_grad():
+            return 1.0 / torch.exp(self.deviation_network.variance.detach() * 10.0).clip(1e-6, 1e6)
+
+    def _eikonal_sums_torch(self, render_out, view):
+        """renderer.py:283-285 before the quotient, from what render() returns: [sum of (|grad| - 1)^2, count] over the samples within
+        radius 1.2 -- the torch statement of avc_colsum mode 0 on the compositing kernel's eik [R,2]"""
+        pts = view.rays_o[:, None, :] + view.rays_d[:, None, :] * render_out["mid_z_vals"][..., :, None]
+        relax = (torch.linalg.norm(pts, ord=2, dim=-1) < 1.2).float().detach()
+        err = (torch.linalg.norm(render_out["gradients"], ord=2, dim=-1) - 1.0) ** 2
+        return torch.stack([(relax * err).sum(), relax.sum()])
+
+    def _clip_loss_sharded(self, iter_i, camera=None):
+        """clip_loss with train.shard_view on more than one rank.  Every rank builds the WHOLE view and makes all
+        of its draws -- camera, prior, silhouette selection, background, the z-jitter of all R rays, light -- from streams that are the
+        same on every rank, so the view is the one a single process would render.  The rank then renders the rays of its pixel range
+        alone (shard_of_view) and shades, scatters and sums over that range; the eikonal sums, the loss sums and the images are made
+        the view's by the collectives of parallel.py, and every rank computes the view's loss.  Its backward pass reaches this rank's
+        rays only: the bucket's SUM over the ranks is the gradient of the view.  A rank whose range is empty (fewer rays than ranks)
+        renders nothing and joins every collective with zeros."""
+        dev, group = self.device, self._shard_group
+        view = self._take_view(iter_i, camera)
+        choice_i, background_rgb, masked_background_rgb = self.draw_background(view)
+        R = view.rays_o.shape[0]
+        if R == 0:
+            raise RuntimeError("train.shard_view: the view has no rays to cut over the ranks")
+        jitter = torch.rand([R, 1], device=dev) if self.renderer.perturb > 0 else None      # renderer.py:318, for all R rays as render() draws it
+        part = self.shard_of_view(view)
+        (q0, q1), (p0, p1) = part.rays, part.pixels
+        cut = lambda t, a, b: t if t is None or t.shape[-1] == 3 else t[a:b]      # [1,3] colours are the same for every ray / pixel
+        fused = dev.type == "cuda"
+        render_out = None
+        if q1 > q0:
+            kw = dict(group=group) if fused else {}
+            render_out = self.renderer.render(part.rays_o, part.rays_d, part.near, part.far, background_rgb=cut(masked_background_rgb, q0, q1),
+                                              cos_anneal_ratio=self.get_cos_anneal_ratio(), jitter=cut(jitter, q0, q1), **kw)
+        if fused and render_out is not None:
+            part.eikonal = render_out["gradient_error"]
+        else:      # the torch statement of the same reduction (and, on either device, the rank without rays)
+            sums = self._eikonal_sums_torch(render_out, part) if render_out is not None else torch.zeros(2, device=dev)
+            s = parallel.allreduce_sum(sums, group)
+            part.eikonal = s[0] / (s[1] + 1e-5)
+        background_part = cut(background_rgb, p0, p1)
+        if fused:
+            loss, parts, _ = self.fused_shade_loss(render_out, part, choice_i, background_part, iter_i)
+        else:
+            if render_out is not None:
+                comp = self.shade_and_scatter(render_out, part, choice_i, background_part)
+            else:
+                if self.add_no_texture or self.texture_cast_light:
+                    self._draw_light(view)
+                z3 = torch.zeros(0, 3, device=dev)
+                comp = dict(color_fine=z3, extra_color_fine=z3, weight_sum=torch.zeros(0, 1, device=dev), texture_shading=z3, rand_shading_rgb=z3)
+            loss, parts = self.assemble_loss(render_out, comp, part, iter_i)
+        view.part = part
+        self.last_view = view
+        return loss, parts
+
     def train_clip_iteration(self, iter_i, camera=None):
         """One optimisation step: this rank's views_per_iter / world views (global index j = rank, rank + world, ...; all with the same
         iter_i, so the face camera and face prompt hold for the whole step), one after the other -- the operand panels belong to one
@@ -708,7 +854,7 @@ class Runner:
         from its own streams (_fresh_view_rngs), swapped in around its clip_loss and kept for the next step; the rank's first view
         draws from the process's streams, which are back in place when the step returns.  `camera`: one camera for the one view of a
         rank, or a list of one camera per view."""
-        n = self.views_per_iter // self.world
+        n = self.views_per_iter // self._view_world      # (train.shard_view: all views_per_iter views, each cut over all ranks)
         if camera is not None and n > 1 and len(camera) != n:
             raise ValueError("%d views per rank and step: `camera` must be a list of %d cameras" % (n, n))
         release = getattr(self.perceptor, "release_graphs", None)
@@ -728,7 +874,8 @@ class Runner:
                         self._view_rngs[k - 1] = self._data_rng_state()
                 if k == 0:
                     self._zero_grad()
-                loss.backward()       # (draws nothing: the next view's streams replace this view's directly)
+                if loss.requires_grad:    # (not on a rank that owns no ray of a sharded view: its part of the gradient is zero)
+                    loss.backward()       # (draws nothing: the next view's streams replace this view's directly)
                 losses.append(loss.detach())
                 # (one view: the statistics as they always were kept; several: detached, no autograd graph outlives its view)
                 parts_of.append(parts if n == 1 else {key: None if v is None else v.detach() for key, v in parts.items()})
@@ -737,7 +884,8 @@ class Runner:
         finally:
             if mine is not None:      # an exception included: the process's streams are never left swapped out
                 self._set_data_rng_state(mine)
-        self._reduce_and_step(None if n == 1 else self.views_per_iter)
+        # (train.shard_view: the ranks' gradients are PARTS of each view's gradient -- SUM over the ranks, mean over the views alone)
+        self._reduce_and_step(None if n == 1 and not self.shard_view else self.views_per_iter)
         self.last_views, self.last_view_losses = views, losses
         if n == 1:
             loss, p = losses[0], parts_of[0]
