@@ -521,7 +521,8 @@ __global__ __launch_bounds__(256) void composite_bwd_kernel(
     gx += wv * dn0; gy += wv * dn1; gz += wv * dn2;
     if (pn < 1.2f) {
       const float gn = sqrtf(nx * nx + ny * ny + nz * nz);
-      const float k = eik_scale * 2.f * (gn - 1.f) / gn;
+      // (a zero normal: the norm's subgradient 0, as torch.linalg.norm's backward gives -- not -inf * 0)
+      const float k = gn > 0.f ? eik_scale * 2.f * (gn - 1.f) / gn : 0.f;
       gx += k * nx; gy += k * ny; gz += k * nz;
     }
     d_normal[3 * (base + i)] = gx; d_normal[3 * (base + i) + 1] = gy; d_normal[3 * (base + i) + 2] = gz;

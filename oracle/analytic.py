@@ -198,12 +198,15 @@ def composite_backward(cf, sdf, n, rgb6, rays_d, inv_s, cos_anneal, bg, d_color,
     dQ = -d_araw / (P + 1e-5)
     de_prev = dP * P * (1 - P) * inv_s
     de_next = dQ * Q * (1 - Q) * inv_s
-    d_inv_s = (dP * P * (1 - P) * cf["e_prev"] + dQ * Q * (1 - Q) * cf["e_next"]).sum()
+    d_inv_s_ray = (dP * P * (1 - P) * cf["e_prev"] + dQ * Q * (1 - Q) * cf["e_next"]).sum(-1)
+    d_inv_s = d_inv_s_ray.sum()
     d_sdf = de_prev + de_next
     d_ic = (de_next - de_prev) * cf["dists"] * 0.5
     c = cf["c"]
     d_c = d_ic * (0.5 * (1 - cos_anneal) * ((-0.5 * c + 0.5) > 0).to(w.dtype) + cos_anneal * ((-c) > 0).to(w.dtype))
     d_n = d_c[..., None] * rays_d[:, None, :] + d_n_up
     gn = cf["gn"]
-    d_n = d_n + (d_eik / cf["eik_den"]) * (cf["relax"] * 2 * (gn - 1) / gn)[..., None] * n
-    return dict(d_sdf=d_sdf, d_n=d_n, d_rgb6=d_rgb6, d_inv_s=d_inv_s, wbar=wbar, abar=abar)
+    # (a zero normal contributes 0: the subgradient torch.linalg.norm's backward takes at 0)
+    unit = torch.where(gn > 0, (gn - 1) / torch.where(gn > 0, gn, torch.ones_like(gn)), torch.zeros_like(gn))
+    d_n = d_n + (d_eik / cf["eik_den"]) * (cf["relax"] * 2 * unit)[..., None] * n
+    return dict(d_sdf=d_sdf, d_n=d_n, d_rgb6=d_rgb6, d_inv_s=d_inv_s, d_inv_s_ray=d_inv_s_ray, wbar=wbar, abar=abar)

@@ -16,6 +16,9 @@ Tolerances (fp32 oracle vs f16-MFMA forward / bf16-MFMA gradient sweeps, fp32 ac
   operand panels (what avc_render_points_fwd_train / _bwd store)   per tile group max(0, |err| - u |ref|) / rms(ref) <= 3 x its measured
                  maximum, u = 2^-11 (f16) / 2^-8 (bf16): 9e-4 .. 4.5e-2 forward, 9.6e-4 .. 1.55e-1 backward, never above 0.25; masks
                  exact against the stored r; invariances bit for bit (tests/test_gpu_panels.py)
+  up-sampling, every sample (avc_upsample_step(_lanes))   residual in CDF space <= 1e-5 + n 2^-23 + 4 x the float32 CPU statement's on
+                 the same ray, no sample left out; merge bit for bit; n, m at the dispatch edges (tests/test_gpu_rays_exact.py)
+  compositing, S = 1 .. 256 / column sums   S > 128 and saturated sigmoids: 4 x the float32 CPU statement's error; sums exact (same module)
 """
 import numpy as np
 import pytest
