@@ -355,8 +355,10 @@ extern "C" int avc_resize_norm_bwd(const float* dout, int B, int H, int W, const
 // ---------------------------------------------------------------------------------------------------------------
 // The head of an iteration: rays of a view (dataset.py:277-293 gen_rays_pose / :252-275 the selected pixels of gen_rays_silhouettes),
 // their near / far from the unit sphere (:331-342), and the prior image resampled to the ray grid (main.py:376-380: nearest) -- ~45 small
-// torch launches as one.  torch.linspace's own formula (start + i step below the middle, end - (n - 1 - i) step above) so that the
-// pixel centres are the same floats.
+// torch launches as one.  The pixel centres follow torch.linspace's own formula (start + i step below the middle, end - (n - 1 - i) step
+// above).  The rays are NOT the torch statement's bit for bit: torch's vector norm and its sum over the rotation's columns round
+// differently from the three-term expressions below, and near = mid - 1 cancels -- a few units in the last place of rays_d, up to a
+// dozen of near (tests/test_gpu_glue_exact.py measures it against Runner._view_head_torch on the GPU; profiles/glue_exact.md).
 __device__ __forceinline__ float linspace_at(float end, int n, int i) {   // torch.linspace(0, end, n)[i], float32
   if (n == 1) return 0.f;
   const float step = end / (float)(n - 1);
@@ -448,7 +450,8 @@ extern "C" int avc_chess_background(float* out, int H, int W, int chess_length, 
 
 // renderer.py:311-322: the coarse sample depths z[r][i] = near[r] + (far[r] - near[r]) * linspace(0, 1, n)[i] (+ (jitter[r] - 0.5) * 2 / n
 // with perturb), every float32 operation rounded like the torch op it replaces (torch.linspace: start + step * i below the middle,
-// end - step * (n - 1 - i) above).  One launch instead of nine.
+// end - step * (n - 1 - i) above; a tensor divided by a host scalar: multiplied by the scalar's float32 reciprocal, which differs
+// from the quotient by an ulp unless n is a power of two).  One launch instead of nine.
 __global__ __launch_bounds__(GLUE_THREADS) void coarse_z_kernel(const float* __restrict__ near, const float* __restrict__ far,
                                                                 const float* __restrict__ jitter, int R, int n, float* __restrict__ z) {
 #pragma clang fp contract(off)   // (as in gen_rays_kernel: the torch ops this replaces are separate launches, each product and sum rounded)
@@ -458,7 +461,7 @@ __global__ __launch_bounds__(GLUE_THREADS) void coarse_z_kernel(const float* __r
   const float lin = linspace_at(1.f, n, i);     // (torch.linspace's kernel itself contracts end - step * k into one fma: so does linspace_at)
   const float nr = near[r];
   float v = nr + (far[r] - nr) * lin;
-  if (jitter) v = v + (jitter[r] - 0.5f) * 2.0f / (float)n;
+  if (jitter) v = v + (jitter[r] - 0.5f) * 2.0f * (1.0f / (float)n);
   z[t] = v;
 }
 extern "C" int avc_coarse_z(const float* near, const float* far, const float* jitter, int R, int n, float* z, void* stream) {
@@ -487,7 +490,7 @@ __device__ __forceinline__ float tail_block_sum(float v, float (*red)[TAIL_D / 6
   for (int w = 0; w < TAIL_D / 64; ++w) t += red[slot][w];
   return t;
 }
-// out[8] = loss, colour loss, mask loss, cos_0, cos_1, 0, 0, 0;  saved[4 B] = per image (|e| clamped, cos, |e| raw, 0); saved[4 B] = |t| clamped
+// out[8] = loss, colour loss, mask loss, cos_0 .. cos_{B-1} (B <= 4), 0 in the slots left;  saved[4 B] = per image (|e| clamped, cos, |e| raw, 0); saved[4 B] = |t| clamped
 __global__ __launch_bounds__(TAIL_D) void loss_tail_fwd_kernel(const float* __restrict__ enc, const float* __restrict__ text, int B, int T,
                                                                const float* __restrict__ sums, const float* __restrict__ eik, TailW w,
                                                                float* __restrict__ loss, float* __restrict__ out, float* __restrict__ saved) {
@@ -512,7 +515,8 @@ __global__ __launch_bounds__(TAIL_D) void loss_tail_fwd_kernel(const float* __re
     float l = colour + eik[0] * w.igr_w + maskl * w.mask_w;
     for (int b = 0; b < B; ++b) l = l + (1.f - cosv[b]) * w.clip_w;
     loss[0] = l;
-    out[0] = l; out[1] = colour; out[2] = maskl; out[3] = cosv[0]; out[4] = cosv[1]; out[5] = 0.f; out[6] = 0.f; out[7] = 0.f;
+    out[0] = l; out[1] = colour; out[2] = maskl; out[7] = 0.f;
+    for (int b = 0; b < 4; ++b) out[3 + b] = b < B ? cosv[b] : 0.f;
   }
 }
 // g = d L / d loss (device scalar).  d_enc [B,512]; dd[8]: [0..3] = gradient of sums (l1, mask_sum: 0, bce, sq: 0), [4] = of the eikonal term

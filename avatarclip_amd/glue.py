@@ -68,7 +68,8 @@ class ShadeLossFn(torch.autograd.Function):
 
 class LossTailFn(torch.autograd.Function):
     """(enc [B,512], text [T,512], sums [4] of ShadeLossFn, eikonal scalar) -> loss (scalar), stats [8] = loss, colour loss, mask loss,
-    cos_0, cos_1: main.py:491-534 from the embeddings on -- the two cosine similarities, the normalisations of the colour / mask sums
+    cos_0 .. cos_{B-1} (stats[3 + b] for every image b < B <= 4, 0 in the slots left): main.py:491-534 from the embeddings on -- the
+    cosine similarities (two in train_clip), the normalisations of the colour / mask sums
     and the weighted sum -- in one launch each way (csrc/avc_glue.hip loss_tail_*; ~35 + ~40 torch launches otherwise)."""
 
     @staticmethod

@@ -191,7 +191,7 @@ int avc_coarse_z(const float* near_, const float* far_, const float* jitter, int
 /* The scalar tail of the loss (main.py:491-534) in one launch each way: cos_b = torch.cosine_similarity(torch.mean(enc[b:b+1], 0),
  * torch.mean(text, 0), dim=0) for the B images (enc [B,512], text [T,512]) and
  *   loss = sums[0] / (sums[1] + 1e-5) + eikonal * igr_weight + (sums[2] / P) * mask_weight + sum_b (1 - cos_b) * clip_weight
- * (the reference's order of additions).  loss: device scalar; out [8] = loss, colour loss, mask loss, cos_0, cos_1 (statistics); saved
+ * (the reference's order of additions).  loss: device scalar; out [8] = loss, colour loss, mask loss, cos_0 .. cos_{B-1}, 0 (statistics); saved
  * [4 B + 1]: what the backward needs.  The backward takes g = d L / d loss (device scalar) and writes d_enc [B,512] and dd [8]: [0..3] the
  * gradient of sums (what avc_shade_loss_bwd takes as gs), [4] that of the eikonal term. */
 int avc_loss_tail_fwd(const float* enc, const float* text, int B, int T, int D, const float* sums, const float* eikonal, float igr_weight,
