@@ -556,16 +556,17 @@ def _write_previews(ctx, out_dir, poses, motion, size):
                 P.save_frames(images[i:i + 1], os.path.join(out_dir, "candidate_%d.png" % i))
 
 
-def run(conf, ctx, pose_assets=None, motion_assets=None, preview=False, preview_size=512):
+def run(conf, ctx, pose_assets=None, motion_assets=None, preview=False, preview_size=512, pose_ctx=None):
     """main.py:14-41: candidate poses (saved as candidate_<i>.npy), then -- unless general.mode == 'pose' -- the motion (motion.npy).  The
     reference also writes pyrender pictures of them (candidate_<i>.jpg, motion.mp4; visualize.py render_pose / render_motion): with
     `preview` this writes candidate_<i>.png and motion.gif of `preview_size` pixels from the HIP posing kernel and the preview rasteriser
     (preview.py: its own camera framing and shading, not pyrender's; no .jpg / .mp4 encoder here).  Off by default; the returned tensors
-    are the same either way."""
+    are the same either way.  `pose_ctx`: a second AnimateContext for the pose generator alone (pipeline.py: a pose codebook of ViT-B/32
+    embeddings searched beside a ViT-B/16 main tower); None: `ctx`."""
     out_dir = conf.get_string("general.base_exp_dir")
     os.makedirs(out_dir, exist_ok=True)
     text = conf.get_string("general.text")
-    poses = build_pose_generator(dict(conf["pose_generator"]), ctx, **(pose_assets or {})).get_topk_poses(text)
+    poses = build_pose_generator(dict(conf["pose_generator"]), ctx if pose_ctx is None else pose_ctx, **(pose_assets or {})).get_topk_poses(text)
     for i in range(poses.shape[0]):
         np.save(os.path.join(out_dir, "candidate_%d.npy" % i), poses[i].detach().cpu().numpy())
     if conf.get_string("general.mode") == "pose":

@@ -370,7 +370,9 @@ class Runner:
                                "general.allow_standins = True for benchmarks / tests)" % what)
         logging.warning("%s is missing: using the seeded / procedural stand-in", what)
 
-    def init_clip(self, perceptor=None, text_embeddings=None, clip_state_dict=None):
+    def init_clip(self, perceptor=None, text_embeddings=None, clip_state_dict=None, tokenizer=None):
+        """`tokenizer`: an already built tokenizer.SimpleTokenizer for the prompts of the conf (pipeline.py shares one over its stages);
+        None: built here from clip.bpe_path / $AVC_CLIP_BPE when the perceptor carries a text tower"""
         from . import clip_vit
         if perceptor is None:
             if clip_state_dict is None:
@@ -385,8 +387,7 @@ class Runner:
         self.clip_preprocess = clip_vit.clip_preprocess
         te = text_embeddings or {}
 
-        tokenizer = None
-        if getattr(perceptor, "_text_sd", None) is not None:
+        if tokenizer is None and getattr(perceptor, "_text_sd", None) is not None:
             try:
                 from .tokenizer import SimpleTokenizer
                 tokenizer = SimpleTokenizer(self.conf.get_string("clip.bpe_path", default=None))

@@ -80,6 +80,22 @@ def write_nerf_dataset(output_dir, vertices, faces, device="cuda", image_size=25
     return u8, transforms
 
 
+def pose_shape(vertices, smpl_model, pose_type="stand_pose", pose_npy=None, device="cuda"):
+    """render.py:108-121: the coarse shape [V,3] posed by `my_lbs` -- the stand pose of `pose_npy`, or the T pose whose root is turned by
+    pi/2 about x -> (vertices [V,3] float32, the SMPL model's faces).  smpl_model: a path for smpl_lbs.load_smpl_arrays."""
+    from . import smpl_lbs
+    smpl = smpl_lbs.load_smpl_arrays(smpl_model, device)
+    if pose_type == "stand_pose":
+        pose = np.load(pose_npy).astype(np.float32)
+    else:
+        pose = np.zeros([1, 24, 3], np.float32)
+        pose[:, 0, 0] = np.pi / 2
+    rot = smpl_lbs.batch_rodrigues(torch.from_numpy(pose.reshape(-1, 3)).to(device)).reshape(1, -1, 3, 3)
+    verts, _ = smpl_lbs.lbs(torch.from_numpy(np.asarray(vertices, np.float32)).to(device).reshape(1, -1, 3), rot, smpl["posedirs"],
+                            smpl["J_regressor"], smpl["parents"], smpl["lbs_weights"])
+    return verts[0].cpu().numpy(), smpl["faces"]
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--coarse_shape_obj", type=str, required=True)
@@ -91,17 +107,7 @@ def main():
     from .smpl_prior import read_obj
     v, f = read_obj(args.coarse_shape_obj)
     if args.smpl_model is not None:
-        from . import smpl_lbs
-        smpl = smpl_lbs.load_smpl_arrays(args.smpl_model, "cuda")
-        if args.pose_type == "stand_pose":
-            pose = np.load(args.pose_npy).astype(np.float32)
-        else:
-            pose = np.zeros([1, 24, 3], np.float32)
-            pose[:, 0, 0] = np.pi / 2
-        rot = smpl_lbs.batch_rodrigues(torch.from_numpy(pose.reshape(-1, 3)).cuda()).reshape(1, -1, 3, 3)
-        verts, _ = smpl_lbs.lbs(torch.from_numpy(v).cuda().reshape(1, -1, 3), rot, smpl["posedirs"], smpl["J_regressor"], smpl["parents"],
-                                smpl["lbs_weights"])
-        v, f = verts[0].cpu().numpy(), smpl["faces"]
+        v, f = pose_shape(v, args.smpl_model, args.pose_type, args.pose_npy)
     print("Begin rendering obj: {}".format(args.coarse_shape_obj))
     write_nerf_dataset(args.output_folder, v, f)
     print("Renderings written to: {}".format(args.output_folder))
