@@ -4,7 +4,8 @@
 All GEMMs (patch embedding, in_proj, out_proj, c_fc, c_proj, visual.proj) run in avc_vit_linear / avc_vit_linear_packed (bf16 MFMA,
 fp32 accumulate; the reference runs CLIP in fp16 on GPU), attention in avc_vit_attention_*.  Weights are frozen
 (`requires_grad_(False)`, main.py:260): the backward only propagates to the pixels, re-using the same GEMM kernel on
-the packed transposes.  LayerNorm / residual bookkeeping are torch elementwise ops under autograd.
+the packed transposes.  The twelve residual blocks are one autograd node (BlocksFn) at any batch size; ln_pre / ln_post and the
+class-token bookkeeping around them are torch ops under autograd.
 Accepts an OpenAI-format state dict (`visual.*` keys, e.g. torch.jit.load('ViT-B-32.pt').state_dict()); the variant -- patch 32 / 50
 tokens or patch 16 / 197 tokens, both width 768, 12 layers, 224 x 224 input -- is read from the checkpoint (vision_variant).
 """
@@ -79,8 +80,9 @@ def _ws(device, nbytes):
     return _workspace[key]
 
 
-BIG_M = 129   # rows from which a call counts as "batched" (3+ images): the linears then run in the LDS-staged GEMM (the C side decides
-# that by itself), BlocksFn has no backward and takes the grown-on-demand operands; up to 128 rows the latency kernel
+BIG_M = 129   # rows from which a call counts as "batched" (3+ images of ViT-B/32, every ViT-B/16 call): the linears then run in the
+# LDS-staged GEMM (the C side decides that by itself); up to 128 rows the latency kernel.  BlocksFn runs on either, with and without a
+# gradient; which packed operands a call takes: BlocksFn._operands
 
 
 def _linear_raw(x2d, lin, transposed, bias, residual, act, want_pre, gelu_pre=None):
@@ -149,12 +151,24 @@ class BlocksFn(torch.autograd.Function):
     """The 12 residual blocks (clip/model.py ResidualAttentionBlock) as ONE autograd node: activations go from kernel to kernel as
     packed bf16 operands -- LayerNorm writes the operand of the linear behind it, attention that of the out-projection, c_fc +
     QuickGELU that of c_proj -- instead of fp32 rows and a packing pass in front of every linear.  The forward serves any number of
-    rows: up to 128 (the per-iteration call, 1-2 images) on the latency kernel, more (scoring calls, no gradient: ShapeGen/main.py:
-    104-128, pose_generation.py:79-110) on the LDS-staged GEMM; avc_vit_linear_packed chooses.  The backward exists up to 128 rows: the
-    proj^T product leaves already multiplied by QuickGELU' and packed, and the LayerNorm backward adds the residual branch's gradient
-    and packs its result for the transposed linear below.  7 + 8 launches per block instead of 11 + ~14 (a packing launch per linear,
-    torch LayerNorm kernels, AccumulateGrad adds).  Arithmetic as in LinearFn / AttentionFn / F.layer_norm: bf16 operands, fp32
-    accumulation, fp32 residual stream and LayerNorm statistics."""
+    rows, forward and backward: up to 128 (the per-iteration call, 1-2 images of ViT-B/32) on the latency kernel, more (scoring calls:
+    ShapeGen/main.py:104-128, pose_generation.py:79-110; every ViT-B/16 call, 197 rows an image; the 5-view batches of AvatarAnimate's
+    CLIP-guided optimisers) on the LDS-staged GEMM; avc_vit_linear_packed chooses.  In the backward the proj^T product leaves already
+    multiplied by QuickGELU' and packed, and the LayerNorm backward adds the residual branch's gradient and packs its result for the
+    transposed linear below.  7 + 8 launches per block instead of 11 + ~14 (a packing launch per linear, torch LayerNorm kernels,
+    AccumulateGrad adds).  Arithmetic as in LinearFn / AttentionFn / F.layer_norm: bf16 operands, fp32 accumulation, fp32 residual
+    stream and LayerNorm statistics."""
+
+    @staticmethod
+    def _operands(model, B, M, keep):
+        """(allocator, prefix of the role names) of a call's packed operands.  Up to 128 rows, and every gradient call of 1-2 images
+        (what encode_image captures as HIP graphs: 197 / 394 rows of ViT-B/16), the per-shape buffers that are never re-allocated --
+        a captured launch must not point at a buffer that a later, larger call replaces.  Everything else one buffer per role grown
+        on demand, the gradient calls' under names of their own (a scoring call between a forward and its backward leaves them
+        alone).  Rows past M of a grown buffer hold whatever was there: rows are independent in every kernel, no valid row reads them."""
+        if M < BIG_M or (keep and B <= 2):
+            return model._train_buf, ""
+        return model._packed_buf, ("grad_" if keep else "")
 
     @staticmethod
     def forward(ctx, x, model):
@@ -165,18 +179,14 @@ class BlocksFn(torch.autograd.Function):
         nb = len(model.blocks)
         dev = x0.device
         keep = ctx.needs_input_grad[0]
-        if keep and M >= BIG_M:
-            raise RuntimeError("BlocksFn: the packed backward covers up to 128 rows (2 images); ClipVisionB32._blocks_per_kernel is the "
-                               "route of a gradient call with more")
         # what the backward reads is kept per block; without one a block writes over the one before it and the residual stream is
         # updated in place, in x0 (the caller's ln_pre output: nobody reads it again)
         qkvs = torch.empty(nb if keep else 1, M, 3 * W, device=dev, dtype=torch.float32)
         x2s = torch.empty(nb if keep else 1, M, W, device=dev, dtype=torch.float32)
         xs = torch.empty(nb, M, W, device=dev, dtype=torch.float32) if keep else x0.unsqueeze(0)   # block outputs (= the next block's input)
         pres = torch.empty(nb, M, 4 * W, device=dev, dtype=torch.float32) if keep else None
-        # up to 128 rows the operands captured graphs point at, never re-allocated; beyond, one buffer per role grown on demand
-        buf = model._train_buf if M < BIG_M else model._packed_buf
-        a_ln, a_at, a_fc = buf("ln", M, W), buf("attn", M, W), buf("fc", M, 4 * W)
+        buf, pf = BlocksFn._operands(model, B, M, keep)
+        a_ln, a_at, a_fc = buf(pf + "ln", M, W), buf(pf + "attn", M, W), buf(pf + "fc", M, 4 * W)
 
         def linear(xs_, lin, res, y, y_pre, ys, N, K, act):
             L.call("avc_vit_linear_packed", xs_, lin.wp, lin.b, res, None, y, y_pre, ys, M, N, K, act, stream=st)
@@ -206,8 +216,9 @@ class BlocksFn(torch.autograd.Function):
         M, W = B * T, WIDTH
         dev = x0.device
         g = g.reshape(M, W).contiguous().float()
-        p_g, p_dh = model._train_buf("g", M, W), model._train_buf("dh", M, 4 * W)
-        p_g2, p_dqkv = model._train_buf("g2", M, W), model._train_buf("dqkv", M, 3 * W)
+        buf, pf = BlocksFn._operands(model, B, M, True)
+        p_g, p_dh = buf(pf + "g", M, W), buf(pf + "dh", M, 4 * W)
+        p_g2, p_dqkv = buf(pf + "g2", M, W), buf(pf + "dqkv", M, 3 * W)
         t768 = torch.empty(5, M, W, device=dev, dtype=torch.float32)
         dy2, da, dy1, bufa, bufb = t768[0], t768[1], t768[2], t768[3], t768[4]
 
@@ -279,7 +290,8 @@ class ClipVision:
         return self
 
     def _packed_buf(self, tag, M, K):
-        """a packed operand of BlocksFn above 128 rows (scoring calls): one per role, grown on demand, stream-ordered reuse"""
+        """a packed operand of BlocksFn above 128 rows (scoring calls; gradient calls of 3+ images under "grad_" roles): one per
+        role, grown on demand, stream-ordered reuse"""
         need = L.load().avc_vit_workspace_bytes(M, K)
         buf = self._packed.get(tag)
         if buf is None or buf.numel() < need:
@@ -287,8 +299,9 @@ class ClipVision:
         return buf
 
     def _train_buf(self, tag, M, K):
-        """a packed operand of BlocksFn up to 128 rows (the per-iteration call): one per (role, shape), never re-allocated -- captured
-        graphs point at it; zero-filled once (the attention kernel only writes the rows below M)"""
+        """a packed operand of BlocksFn up to 128 rows and of every gradient call of 1-2 images (the per-iteration call): one per
+        (role, shape), never re-allocated -- captured graphs point at it; zero-filled once (the attention kernel only writes the
+        rows below M)"""
         key = ("train", tag, M, K)
         buf = self._packed.get(key)
         if buf is None:
@@ -359,14 +372,13 @@ class ClipVision:
             self._graph_busy[B] = False
 
     def _blocks_packed(self, x):
-        """the residual blocks with packed bf16 hand-offs between the kernels (BlocksFn): every call without a gradient to the
-        pixels, and gradient calls of up to 128 rows (2 images of ViT-B/32)"""
+        """the residual blocks with packed bf16 hand-offs between the kernels (BlocksFn): the route of every call, with or without a
+        gradient to the pixels, at any number of rows"""
         return BlocksFn.apply(x, self)
 
     def _blocks_per_kernel(self, x):
         """the residual blocks as one autograd node per kernel (fp32 rows + a packing pass in front of every linear, torch LayerNorm):
-        gradient calls of more than 128 rows (3+ images of ViT-B/32: AvatarAnimate's CLIP-guided optimisers; every gradient call of
-        ViT-B/16, 197 rows an image), and what the tests hold BlocksFn against"""
+        no call takes it by default; it is what the tests hold BlocksFn against"""
         for blk in self.blocks:
             y = F.layer_norm(x, (WIDTH,), blk["ln1"][0], blk["ln1"][1], 1e-5)
             a = AttentionFn.apply(LinearFn.apply(y, blk["qkv"], 0, None))
@@ -377,7 +389,7 @@ class ClipVision:
         return x
 
     def _encode_image_eager(self, image: torch.Tensor, blocks=None) -> torch.Tensor:
-        """blocks: _blocks_packed or _blocks_per_kernel; None = the route this call is meant to take"""
+        """blocks: _blocks_packed or _blocks_per_kernel; None = the route every call is meant to take, the packed one"""
         B, P = image.shape[0], self.patch
         # conv1 (P x P, stride P, no bias) == GEMM over flattened patches in (c, ky, kx) order
         x = image.float().reshape(B, 3, RES // P, P, RES // P, P).permute(0, 2, 4, 1, 3, 5)
@@ -385,10 +397,7 @@ class ClipVision:
         x = LinearFn.apply(x, self.conv, 0, None)
         x = torch.cat([self.cls.expand(B, 1, WIDTH), x], dim=1) + self.pos
         x = F.layer_norm(x, (WIDTH,), self.ln_pre[0], self.ln_pre[1], 1e-5)
-        if blocks is None:
-            grad = torch.is_grad_enabled() and x.requires_grad
-            blocks = self._blocks_per_kernel if grad and B * self.tokens >= BIG_M else self._blocks_packed
-        x = blocks(x)
+        x = (blocks or self._blocks_packed)(x)
         x = F.layer_norm(x[:, 0, :], (WIDTH,), self.ln_post[0], self.ln_post[1], 1e-5)
         return LinearFn.apply(x, self.proj, 0, None)
 

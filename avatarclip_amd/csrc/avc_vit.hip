@@ -136,8 +136,8 @@ __global__ __launch_bounds__(64 * VIT_WAVES) void vit_linear_kernel(const b8* __
 
 // batched calls: the LDS-staged GEMM of avc_vit_gemm.hip (128 x 128 blocks; 12.7 ms per encoder pass against 20.3 for the direct-from-L1
 // kernel above, profiles/r03_score_bench.txt), which returns false for the shapes it does not cover
-bool avc_vit_gemm_lds(const void* xs, const void* wp, const float* bias, const float* res, float* y, float* y_pre, void* ys, int M, int N,
-                      int K, int act, int mt_packed, void* stream);
+bool avc_vit_gemm_lds(const void* xs, const void* wp, const float* bias, const float* res, const float* gpre, float* y, float* y_pre,
+                      void* ys, int M, int N, int K, int act, int mt_packed, void* stream);
 
 extern "C" long avc_vit_workspace_bytes(int M, int K) {
   const long mt = ((M + 127) / 128) * 4;   // whole groups of 4 row tiles (the rows past M are packed as zeros)
@@ -163,9 +163,9 @@ static int vit_linear_dispatch(const char* who, const void* xs, const void* wp, 
     else if (per_wave <= 12) hipLaunchKernelGGL((vit_linear_kernel<1, 12>), grid, block, lds, s, x8, w8, bias, res, y, y_pre, M, N, K, act, y8, gpre);
     else if (per_wave <= 18) hipLaunchKernelGGL((vit_linear_kernel<1, 18>), grid, block, lds, s, x8, w8, bias, res, y, y_pre, M, N, K, act, y8, gpre);
     else hipLaunchKernelGGL((vit_linear_kernel<1, 24>), grid, block, lds, s, x8, w8, bias, res, y, y_pre, M, N, K, act, y8, gpre);
-  } else if (act == 2 || (y && ys) || !avc_vit_gemm_lds(xs, wp, bias, res, y, y_pre, ys, M, N, K, act, ((M + 127) / 128) * 4, stream)) {
-    avc_set_error("avc_vit_linear: more than 128 rows need N % 128 == 0, K % 32 == 0, act 0 or 1, no residual with an activation, and "
-                  "neither y, residual nor y_pre with a packed output");
+  } else if (!avc_vit_gemm_lds(xs, wp, bias, res, gpre, y, y_pre, ys, M, N, K, act, ((M + 127) / 128) * 4, stream)) {
+    avc_set_error("avc_vit_linear: more than 128 rows need N % 128 == 0, K % 32 == 0, no residual with an activation, neither y nor a "
+                  "residual with a packed output, y_pre beside a packed output only with act 1, and a packed output with act 2");
     return 1;
   }
   return avc_check_launch(who);
@@ -310,8 +310,8 @@ extern "C" int avc_vit_linear_packed(const void* xs_packed, const void* w_packed
   return vit_linear_dispatch("avc_vit_linear_packed", xs_packed, w_packed, bias, residual, gelu_pre, y, y_pre, ys_packed, M, N, K, act, stream);
 }
 
-// ---- the per-iteration training pipeline (1-2 images WITH a gradient to the pixels, M <= 128 rows): the same packed hand-offs for
-// the latency kernel, forward and backward (clip_vit.BlocksFn).  Per block 7 launches forward (ln_pack, qkv, attention, out +
+// ---- the training pipeline (images WITH a gradient to the pixels; any M: up to 128 rows the latency kernel, more the GEMM of
+// avc_vit_gemm.hip with its y_pre and act 2 epilogues): the same packed hand-offs forward and backward (clip_vit.BlocksFn).  Per block 7 launches forward (ln_pack, qkv, attention, out +
 // residual, ln_pack, fc -> pre + packed QuickGELU, proj + residual) and 8 backward instead of 11 + 14 torch-autograd nodes with a
 // packing launch in front of every linear, torch LayerNorm kernels and AccumulateGrad adds between them.
 extern "C" int avc_vit_pack(const float* x, const float* gelu_pre, void* xs_packed, int M, int K, void* stream) {

@@ -30,10 +30,14 @@ __device__ __forceinline__ void g2_wait_vm() {
   asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NWAIT) : "memory");
 }
 
-template <int TM, int TN, int KB, int NST, int OCC, bool ACT, bool PRE, bool RES, bool PACK>
+// GP (only with PACK): act 2 -- the product times QuickGELU'(gpre[M,N]), the backward of a QuickGELU layer folded into the transposed
+// linear behind it.  PRE with PACK: the forward of that layer when its backward will run (fp32 pre-activation + packed activation).
+template <int TM, int TN, int KB, int NST, int OCC, bool ACT, bool PRE, bool RES, bool PACK, bool GP>
 __global__ __launch_bounds__(256, OCC) void vit_gemm_lds_kernel(const b8* __restrict__ Xs, const b8* __restrict__ Wp,
                                                            const float* __restrict__ bias, const float* __restrict__ res,
-                                                           float* __restrict__ Y, float* __restrict__ Ypre, b8* __restrict__ Ys, int M, int N, int K) {
+                                                           const float* __restrict__ gpre, float* __restrict__ Y, float* __restrict__ Ypre,
+                                                           b8* __restrict__ Ys, int M, int N, int K) {
+  static_assert(!GP || (PACK && !ACT && !PRE && !RES), "act 2 leaves packed only");
   extern __shared__ __attribute__((aligned(16))) char lds[];
   constexpr int AT = 2 * TM, BT = 2 * TN, FR = AT + BT;         // row tiles, column tiles, fragments per k-step of the block
   constexpr int CHUNKS = FR * KB;                             // 1-KiB DMA chunks per ring slot
@@ -106,22 +110,49 @@ __global__ __launch_bounds__(256, OCC) void vit_gemm_lds_kernel(const b8* __rest
   }
   if (PACK) {
     // the output as the NEXT linear's packed bf16 operand ([row tile][k-step][lane (row, half)][8 columns]) instead of fp32 rows:
-    // every wavefront turns its tiles round through its own 2-KiB corner of the (now idle) ring -- accumulator layout (lane =
-    // column, registers = rows) in, 16 bytes of one row out -- and stores whole 1-KiB fragments
+    // every wavefront turns its tiles round through its own 2.5-KiB corner of the (now idle) ring -- accumulator layout (lane =
+    // column, registers = rows) in, 16 bytes of one row out -- and stores whole 1-KiB fragments.  The rows past M of the last group
+    // go out too (f(bias); with GP zeros, as the latency kernel writes them); what is read (gpre) or written (Ypre) by ROW has
+    // exactly M rows and is touched below M only: lane = column, so each register's 32 columns of one row are one 128-byte segment
+    // gpre of tile t + 1 is requested before tile t is turned round (these calls fill a fraction of the chip: nothing else hides
+    // the round trip), all 16 loads of a tile at once and none of them conditional: a row past M reads row M - 1 instead and is
+    // zeroed below
+    float gp[2][16];
+    auto fetch_gp = [&](int t, int p) {
+      const int col = 32 * (int)(nt_base + wn * TN + t / TM) + n;
+      const int row0 = 32 * (int)(mt_base + wm * TM + t % TM) + 4 * h;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int row = row0 + (r & 3) + 8 * (r >> 2);
+        gp[p][r] = gpre[(long)(row < M ? row : M - 1) * N + col];
+      }
+    };
+    if (GP) fetch_gp(0, 0);
     __syncthreads();                                     // everybody is done reading the ring
     __bf16* T = reinterpret_cast<__bf16*>(lds) + wv * (32 * 40);        // [32 rows][32 columns], row stride 40 (80 B: 16-B aligned, skewed)
     const int KSo = N >> 4;
 #pragma unroll
     for (int j = 0; j < TN; ++j) {
       const long nt = nt_base + wn * TN + j;
-      const float bv = bias ? bias[32 * (int)nt + n] : 0.f;
+      const int col = 32 * (int)nt + n;
+      const float bv = bias ? bias[col] : 0.f;
 #pragma unroll
       for (int i = 0; i < TM; ++i) {
         const long mt = mt_base + wm * TM + i;
+        const int row0 = 32 * (int)mt + 4 * h;
+        const int tt = j * TM + i;
+        if (GP && tt + 1 < TM * TN) fetch_gp(tt + 1, (tt + 1) & 1);
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
+          const int row = row0 + (r & 3) + 8 * (r >> 2);
           float v = acc[i][j][r] + bv;
+          if (PRE) { if (row < M) Ypre[(long)row * N + col] = v; }
           if (ACT) v = v * sigmoidf_(1.702f * v);
+          if (GP) {
+            const float p = gp[tt & 1][r], sg = sigmoidf_(1.702f * p);
+            v *= sg + 1.702f * p * sg * (1.f - sg);
+            if (row >= M) v = 0.f;
+          }
           T[((r & 3) + 8 * (r >> 2) + 4 * h) * 40 + n] = (__bf16)v;
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -162,37 +193,44 @@ __global__ __launch_bounds__(256, OCC) void vit_gemm_lds_kernel(const b8* __rest
 }
 
 template <int TM, int TN, int KB, int NST, int OCC>
-static void g2_launch(const b8* xs, const b8* wp, const float* bias, const float* res, float* y, float* y_pre, b8* ys, int M, int N, int K,
-                      int act, int mt_packed, hipStream_t s) {
+static void g2_launch(const b8* xs, const b8* wp, const float* bias, const float* res, const float* gpre, float* y, float* y_pre, b8* ys,
+                      int M, int N, int K, int act, int mt_packed, hipStream_t s) {
   constexpr int lds = (2 * TM + 2 * TN) * KB * 1024 * NST;
   static_assert(lds >= 4 * 32 * 40 * 2, "the pack-out epilogue borrows 2.5 KiB per wavefront");
   static unsigned long long attr_seen = 0;
-#define G2_K(A, P, R, Q) vit_gemm_lds_kernel<TM, TN, KB, NST, OCC, A, P, R, Q>
+#define G2_K(A, P, R, Q, G) vit_gemm_lds_kernel<TM, TN, KB, NST, OCC, A, P, R, Q, G>
   if (avc_first_use_on_device(attr_seen)) {
-    (void)hipFuncSetAttribute((const void*)G2_K(false, false, false, false), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    (void)hipFuncSetAttribute((const void*)G2_K(false, false, true, false), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    (void)hipFuncSetAttribute((const void*)G2_K(true, false, false, false), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    (void)hipFuncSetAttribute((const void*)G2_K(true, true, false, false), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    (void)hipFuncSetAttribute((const void*)G2_K(true, false, false, true), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    (void)hipFuncSetAttribute((const void*)G2_K(false, false, false, true), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    (void)hipFuncSetAttribute((const void*)G2_K(false, false, false, false, false), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    (void)hipFuncSetAttribute((const void*)G2_K(false, false, true, false, false), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    (void)hipFuncSetAttribute((const void*)G2_K(true, false, false, false, false), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    (void)hipFuncSetAttribute((const void*)G2_K(true, true, false, false, false), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    (void)hipFuncSetAttribute((const void*)G2_K(true, false, false, true, false), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    (void)hipFuncSetAttribute((const void*)G2_K(false, false, false, true, false), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    (void)hipFuncSetAttribute((const void*)G2_K(true, true, false, true, false), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    (void)hipFuncSetAttribute((const void*)G2_K(false, false, false, true, true), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
   }
   const dim3 grid(N / (64 * TN), mt_packed / (2 * TM)), block(256);
-#define G2_GO(A, P, R, Q) hipLaunchKernelGGL((G2_K(A, P, R, Q)), grid, block, lds, s, xs, wp, bias, res, y, y_pre, ys, M, N, K)
-  if (ys && act) G2_GO(true, false, false, true);
-  else if (ys) G2_GO(false, false, false, true);
-  else if (act && y_pre) G2_GO(true, true, false, false);
-  else if (act) G2_GO(true, false, false, false);
-  else if (res) G2_GO(false, false, true, false);
-  else G2_GO(false, false, false, false);
+#define G2_GO(A, P, R, Q, G) hipLaunchKernelGGL((G2_K(A, P, R, Q, G)), grid, block, lds, s, xs, wp, bias, res, gpre, y, y_pre, ys, M, N, K)
+  if (ys && act == 2) G2_GO(false, false, false, true, true);
+  else if (ys && act && y_pre) G2_GO(true, true, false, true, false);
+  else if (ys && act) G2_GO(true, false, false, true, false);
+  else if (ys) G2_GO(false, false, false, true, false);
+  else if (act && y_pre) G2_GO(true, true, false, false, false);
+  else if (act) G2_GO(true, false, false, false, false);
+  else if (res) G2_GO(false, false, true, false, false);
+  else G2_GO(false, false, false, false, false);
 #undef G2_GO
 #undef G2_K
 }
 // the caller (avc_vit.hip) has packed whole groups of 4 row tiles; false = shape not covered (N, K not multiples of the block)
-// ys != NULL: the output goes out as the packed bf16 operand of the next linear (no fp32 y, no residual, no y_pre)
-bool avc_vit_gemm_lds(const void* xs, const void* wp, const float* bias, const float* res, float* y, float* y_pre, void* ys, int M, int N,
-                      int K, int act, int mt_packed, void* stream) {
-  if ((K % (16 * G2_KB)) || (mt_packed % (2 * G2_TM)) || (N % (64 * G2_TN)) || (act && res) || (ys && (res || y_pre))) return false;
-  g2_launch<G2_TM, G2_TN, G2_KB, G2_STAGES, G2_OCC>((const b8*)xs, (const b8*)wp, bias, res, y, y_pre, (b8*)ys, M, N, K, act, mt_packed,
-                                                    (hipStream_t)stream);
+// ys != NULL: the output goes out as the packed bf16 operand of the next linear (no fp32 y, no residual; y_pre only beside
+// QuickGELU, act 1).  act 2 (gpre != NULL, the caller has checked the pair): packed output only
+bool avc_vit_gemm_lds(const void* xs, const void* wp, const float* bias, const float* res, const float* gpre, float* y, float* y_pre,
+                      void* ys, int M, int N, int K, int act, int mt_packed, void* stream) {
+  if ((K % (16 * G2_KB)) || (mt_packed % (2 * G2_TM)) || (N % (64 * G2_TN)) || (act && res) || (ys && (res || y)) ||
+      (ys && y_pre && act != 1) || (act == 2 && !ys))
+    return false;
+  g2_launch<G2_TM, G2_TN, G2_KB, G2_STAGES, G2_OCC>((const b8*)xs, (const b8*)wp, bias, res, gpre, y, y_pre, (b8*)ys, M, N, K, act,
+                                                    mt_packed, (hipStream_t)stream);
   return true;
 }

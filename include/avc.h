@@ -242,10 +242,10 @@ int avc_mc_emit(const float* u, int nx, int ny, int nz, float iso, const int* vf
  * act 1 = QuickGELU (y_pre, if given, receives the pre-activation for the backward).  The backward dX = dY W is the same
  * call with the packed W^T (weights are frozen in AvatarCLIP: main.py:260).  N % 32 == 0, K % 16 == 0.  Up to 128 rows (the
  * per-iteration calls, the text tower's 77) one 8-wavefront split-K workgroup per (32 columns, 32 rows), every combination of the
- * arguments.  More than 128 rows (batched scoring) an LDS-staged GEMM, one 4-wavefront workgroup per 128 x 128 output block
- * (csrc/avc_vit_gemm.hip), which covers N % 128 == 0, K % 32 == 0 and no residual together with an activation -- every linear of
- * both CLIP towers, forward and transposed (N, K in {512, 768, 1536, 2048, 2304, 3072}); anything else returns 1 with the condition in
- * avc_last_error(), there is no slower kernel behind it. */
+ * arguments.  More than 128 rows (batched scoring, every ViT-B/16 call, gradient calls of 3+ images) an LDS-staged GEMM, one
+ * 4-wavefront workgroup per 128 x 128 output block (csrc/avc_vit_gemm.hip), which covers N % 128 == 0, K % 32 == 0 and no residual
+ * together with an activation -- every linear of both CLIP towers, forward and transposed (N, K in {512, 768, 1536, 2048, 2304,
+ * 3072}); anything else returns 1 with the condition in avc_last_error(), there is no slower kernel behind it. */
 int avc_vit_linear(const float* x, const void* w_packed, const float* bias, const float* residual, float* y,
                    float* y_pre, int M, int N, int K, int act, void* workspace /* avc_vit_workspace_bytes(M, K) */,
                    void* stream);
@@ -257,9 +257,10 @@ int avc_vit_linear_bwd_gelu(const float* dy, const float* pre, const void* wt_pa
 long avc_vit_workspace_bytes(int M, int K);
 /* The 12 residual blocks (clip_vit.BlocksFn: clip/model.py ResidualAttentionBlock as one autograd node; weights frozen, main.py:260)
  * keep the activations between the kernels as packed bf16 operands ([row tile][k-step][lane (row, half)][8], avc_vit_workspace_bytes(M, K)
- * bytes for an [M,K] activation) instead of fp32 rows + a packing pass per linear -- forward for any M (the batched scoring calls, no
- * gradient, hundreds of images: ShapeGen/main.py:104-128, AvatarAnimate pose_generation.py:79-110), forward AND backward up to 128 rows
- * (the per-iteration call of the training loop, main.py:512,524: 1-2 images WITH a gradient to the pixels):
+ * bytes for an [M,K] activation) instead of fp32 rows + a packing pass per linear -- forward AND backward for any M: the batched scoring
+ * calls (no gradient, hundreds of images: ShapeGen/main.py:104-128, AvatarAnimate pose_generation.py:79-110), the per-iteration call of
+ * the training loop (main.py:512,524: 1-2 images WITH a gradient to the pixels, 50-100 rows of ViT-B/32, 197-394 of ViT-B/16) and the
+ * 5-view batches of AvatarAnimate's CLIP-guided optimisers (250 rows and more):
  *   avc_vit_ln_pack               LayerNorm(x[M,768]; gamma, beta, eps) (clip/model.py LayerNorm, fp32 statistics) -> packed
  *   avc_vit_attention_fwd_packed  attention with its output packed for the out-projection (rows = b * T + token; 1 <= T <= 256 as
  *                                 avc_vit_attention_fwd; rows past B * T of the last row tile are not written)
@@ -268,8 +269,11 @@ long avc_vit_workspace_bytes(int M, int K);
  *                                 receives the pre-activation), 2 times QuickGELU'(gelu_pre[M,N]) (backward of a QuickGELU layer; act 2
  *                                 if and only if gelu_pre != NULL); the result leaves as fp32 rows y and / or as the packed operand
  *                                 ys_packed of the next linear (one of the two must be given).  Kernels and shapes as avc_vit_linear:
- *                                 up to 128 rows every combination; more than 128 rows N % 128 == 0, K % 32 == 0, act 0 or 1, no
- *                                 residual with an activation, and with ys_packed neither y, residual nor y_pre -- else it returns 1
+ *                                 up to 128 rows every combination; more than 128 rows N % 128 == 0, K % 32 == 0, no residual with
+ *                                 an activation, with ys_packed neither y nor a residual, y_pre beside ys_packed only with act 1
+ *                                 (c_fc of a forward that keeps what its backward reads: nothing of y_pre past row M is written),
+ *                                 and act 2 only into ys_packed (c_proj^T of the backward: no row of gelu_pre past M is read, the
+ *                                 packed rows past M of the last group of four row tiles are zeros) -- else it returns 1
  *   avc_vit_ln_bwd                dx = (d LayerNorm(x; gamma) / dx)^T dy (+ residual_grad): fp32 rows and, xs_packed != NULL, the packed
  *                                 operand of the transposed linear behind it (statistics recomputed from x, eps as in avc_vit_ln_pack;
  *                                 rows past M of xs_packed are not touched: up to 128 rows the caller's buffer holds zeros there) */
