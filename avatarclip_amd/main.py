@@ -1,8 +1,10 @@
 """CLI with the reference's flags (AvatarGen/AppearanceGen/main.py:947-980):
-   python -m avatarclip_amd.main --mode {train,train_clip,validate_mesh,render_geometry_cast_light,interpolate_i_j} --conf X [--is_continue] [--gpu N] [--case NAME]
+   python -m avatarclip_amd.main --mode {train,train_clip,validate_mesh,render_geometry_cast_light,interpolate_i_j} --conf X [--is_continue] [--resume] [--gpu N] [--case NAME]
 Multi-GPU (view-sharded): torchrun --nproc-per-node N -m avatarclip_amd.main --mode train_clip --conf X
 Views per optimisation step (train.views_per_iter; default one per rank): --views_per_iter V, on any number of ranks that divides V
-One view's rays over the ranks (train.shard_view): --shard_view; views_per_iter then defaults to 1 and every view is cut over all ranks"""
+One view's rays over the ranks (train.shard_view): --shard_view; views_per_iter then defaults to 1 and every view is cut over all ranks
+Continue an interrupted train / train_clip run draw for draw: --resume (the newest checkpoint with complete records under
+<base_exp_dir>/resume/; none: the run starts at step 0, so the same command line can be issued again and again by a job scheduler)"""
 import argparse
 import logging
 
@@ -19,6 +21,12 @@ def main():
     parser.add_argument("--mode", type=str, default="train")
     parser.add_argument("--mcube_threshold", type=float, default=0.0)
     parser.add_argument("--is_continue", default=False, action="store_true")
+    parser.add_argument("--resume", default=False, action="store_true",
+                        help="train / train_clip: continue the interrupted run of this base_exp_dir exactly where its newest complete "
+                             "checkpoint + resume records stand (weights, Adam state, data streams, iteration counter); starts at step 0 "
+                             "when there is none.  --is_continue alone loads the weights and restarts the data streams")
+    parser.add_argument("--resume_tag", type=str, default=None,
+                        help="an opaque string written into this run's resume records; --resume continues only records with the same tag")
     parser.add_argument("--gpu", type=int, default=0)
     parser.add_argument("--case", type=str, default="")
     parser.add_argument("--clip_weights", type=str, default=None, help="OpenAI ViT-B-32 state dict / .pt")
@@ -39,7 +47,7 @@ def main():
     if args.mode in ("validate_mesh", "render_geometry_cast_light"):
         args.is_continue = True
     runner = Runner(args.conf, args.mode, args.case, args.is_continue, allow_standins=args.allow_standins or None,
-                    views_per_iter=args.views_per_iter, shard_view=args.shard_view)
+                    views_per_iter=args.views_per_iter, shard_view=args.shard_view, resume=args.resume, resume_tag=args.resume_tag)
     if args.mode == "validate_mesh":   # main.py:972-974
         runner.validate_mesh(world_space=True, resolution=512, threshold=args.mcube_threshold)
         runner.render_geometry_cast_light()

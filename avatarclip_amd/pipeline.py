@@ -6,7 +6,7 @@
         --clip_weights ViT-B-32.pt --bpe bpe_simple_vocab_16e6.txt.gz --smpl SMPL_NEUTRAL.npz --pose_npy stand_pose.npy \\
         --template_obj zero_beta_smpl.obj --AE_path_fname model_VAE_16.pth --codebook_fname shape_codebook.pth \\
         --vposer data/vposer --codebook data/codebook.pth --motion_vae data/motion_vae.pth --renderer_gradient
-        [--from STAGE] [--until STAGE] [--force]
+        [--from STAGE] [--until STAGE] [--force] [--restart_stages]
 
   stage       calls                                                            writes under out_dir/
   shape       shapegen.create_load_AE, load_codebook, shape_gen, writeOBJ      shape/coarse_shape.obj, shape/shape.json
@@ -29,6 +29,11 @@ Every stage is a call into the module that implements it; none of their arithmet
     own settings, the sha256 of every asset file it reads and the fingerprints of the stages it consumes.  A stage is skipped
     exactly when its recorded fingerprint equals the current one and every recorded output still exists with the recorded size.
     The file is rewritten atomically after every stage, so a killed run resumes after its last finished stage.
+  * the two long stages continue INSIDE the stage: `init` and `appearance` tag the Runner's resume records (runner.py, beside every
+    checkpoint) with the stage's fingerprint, and a stage whose previous record is `running` or `failed` with the current fingerprint
+    is started with Runner(resume=True): it goes on from its newest complete checkpoint, draw for draw, and its `done` record says
+    `resumed_from: <step>`.  Checkpoints of another prompt or conf carry another tag and are never continued; `--force` and
+    `--restart_stages` start the stage at step 0.
 
 `run(spec)` takes a PipelineSpec or a dict of its fields.  Single process: train.views_per_iter / train.shard_view stay with
 `avatarclip_amd.main`."""
@@ -104,6 +109,7 @@ class PipelineSpec:
     from_stage: Optional[str] = None
     until_stage: Optional[str] = None
     force: bool = False
+    restart_stages: bool = False             # init / appearance: start an interrupted stage at step 0 instead of continuing it (in no fingerprint)
     # ---- the only test-facing fields: prompt embeddings where no BPE table / text tower exists.  text_embeddings: {"neutral_txt",
     # "target_txt", "prompt", "face_prompt", "back_prompt"} -> [1, 512]; text_feature: callable(text) -> [512] (AnimateContext's)
     text_embeddings: Any = None
@@ -441,6 +447,9 @@ class Run:
         self.spec, self.manifest, self.out_dir = spec, manifest, spec.out_dir
         self._device = self._tokenizer = self._vposer = None
         self._towers = {}
+        # set by `run` before a stage is called: every stage's fingerprint (the tag of the Runner's resume records), the stages to continue
+        # inside (continue_stage); set by the stage: the step its Runner continued from
+        self.fingerprints, self.resume, self.resumed_from = {}, set(), {}
 
     @property
     def device(self):
@@ -562,7 +571,9 @@ def stage_dataset(run):
 
 def stage_init(run):
     from .runner import Runner
-    r = Runner(run.conf_path("init"), mode="train", conf=run.conf("init"), device=run.device)
+    r = Runner(run.conf_path("init"), mode="train", conf=run.conf("init"), device=run.device, resume="init" in run.resume,
+               resume_tag=run.fingerprints.get("init"))
+    run.resumed_from["init"] = r.resumed_from
     r.train()
     return {"checkpoint": _final_checkpoint(r)}
 
@@ -570,7 +581,9 @@ def stage_init(run):
 def stage_appearance(run):
     from .runner import Runner
     s = run.spec
-    r = Runner(run.conf_path("appearance"), mode="train_clip", conf=run.conf("appearance"), device=run.device)
+    r = Runner(run.conf_path("appearance"), mode="train_clip", conf=run.conf("appearance"), device=run.device, resume="appearance" in run.resume,
+               resume_tag=run.fingerprints.get("appearance"))
+    run.resumed_from["appearance"] = r.resumed_from
     keys = [k for k in ("prompt", "face_prompt", "back_prompt") if k in (s.text_embeddings or {})]
     r.init_clip(perceptor=run.tower(), text_embeddings={k: s.text_embeddings[k] for k in keys} or None,
                 tokenizer=run.tokenizer() if s.bpe is not None else None)
@@ -650,6 +663,16 @@ def _sync():
         torch.cuda.synchronize()
 
 
+RESUMABLE = ("init", "appearance")       # the stages that are a Runner's optimisation loop
+
+
+def continue_stage(spec, stage, record, fingerprint):
+    """the rule: a resumable stage is continued inside exactly when its previous run did not finish (`running`: killed, `failed`: an
+    exception) under the fingerprint it has now, and the caller did not ask for a fresh start"""
+    return (stage in RESUMABLE and not spec.force and not spec.restart_stages and bool(record)
+            and record.get("status") in ("running", "failed") and record.get("fingerprint") == fingerprint)
+
+
 def run(spec, log=print):
     """Check everything, then run the selected stages that are not up to date.  Returns {"out_dir", "stages": {stage: "ran" | "skipped" |
     "not selected"}, "manifest": the manifest as written}."""
@@ -662,6 +685,7 @@ def run(spec, log=print):
     fps = fingerprints(spec)
     os.makedirs(spec.out_dir, exist_ok=True)
     shared = Run(spec, manifest)
+    shared.fingerprints = dict(fps)
     report = {}
     for st in STAGES:
         if st not in selected:
@@ -671,6 +695,8 @@ def run(spec, log=print):
             report[st] = "skipped"
             log("[pipeline] %-10s up to date" % st)
             continue
+        if continue_stage(spec, st, manifest["stages"].get(st), fps[st]):
+            shared.resume.add(st)
         manifest["stages"][st] = {"status": "running", "fingerprint": fps[st]}
         write_manifest(spec.out_dir, manifest)
         t0 = time.perf_counter()
@@ -679,6 +705,8 @@ def run(spec, log=print):
             _sync()
             record = {"status": "done", "fingerprint": fps[st], "seconds": round(time.perf_counter() - t0, 3),
                       "outputs": {k: _describe(spec.out_dir, p) for k, p in sorted(outputs.items())}}
+            if shared.resumed_from.get(st) is not None:
+                record["resumed_from"] = int(shared.resumed_from[st])
         except BaseException as e:
             manifest["stages"][st] = {"status": "failed", "fingerprint": fps[st], "seconds": round(time.perf_counter() - t0, 3), "error": repr(e)[:2000]}
             write_manifest(spec.out_dir, manifest)

@@ -13,7 +13,10 @@ Differences that are deliberate and documented:
     pickles stay an input.  Seeded CLIP weights, seeded text embeddings, the procedural ellipsoid prior and a missing
     `train.pretrain` are STAND-INS for benchmarks and tests: they must be asked for (`allow_standins=True` /
     `general.allow_standins = True`), otherwise the Runner raises instead of training on meaningless inputs;
-  * tensorboard logging is optional (absent offline) and scalar logging does not force a device sync every step.
+  * tensorboard logging is optional (absent offline) and scalar logging does not force a device sync every step;
+  * `resume=True` continues an interrupted train / train_clip run draw for draw from a resume record written beside every checkpoint
+    (the reference's `is_continue` loads the weights and starts the data streams and the iteration counter over; it is kept as it is);
+    checkpoints and records are written under a temporary name and moved into place.
 """
 import importlib
 import logging
@@ -89,7 +92,12 @@ class ScalarLog:
 
 class Runner:
     def __init__(self, conf_path, mode="train", case="CASE_NAME", is_continue=False, is_colab=False, conf=None,
-                 device=None, data_root=None, allow_standins=None, views_per_iter=None, shard_view=None):
+                 device=None, data_root=None, allow_standins=None, views_per_iter=None, shard_view=None, resume=False, resume_tag=None):
+        """`resume`: continue the run that was interrupted in this base_exp_dir -- the newest checkpoint whose resume records
+        (<base_exp_dir>/resume/, one per rank, written beside every checkpoint) are complete and carry `resume_tag`: networks, Adam state
+        and iter_step as `is_continue` loads them, and at the top of train() / train_clip() the data streams, the per-view streams, the
+        image permutation and the iteration counter, so that the run goes on draw for draw.  Without such a checkpoint the run starts
+        at step 0.  `resume_tag`: an opaque string written into this run's records; a record with another tag is never continued."""
         if device is None:
             if not torch.cuda.is_available():
                 raise RuntimeError("avatarclip_amd.Runner needs an MI355X (torch.cuda) -- the hot path has no CPU fallback")
@@ -209,7 +217,20 @@ class Runner:
                                         "set general.allow_standins = True to start from the geometric initialisation"
                                         % pretrain_pth)
         latest_model_name = None
-        if is_continue:
+        self.resume_tag = "" if resume_tag is None else str(resume_tag)
+        self.resumed_from = None          # the step a resume=True run continued from (None: it started where any other run starts)
+        self._resume_record = None        # this rank's record of that step until train() / train_clip() has put it in place
+        self._image_perm = self._next_iter_i = None      # train()'s permutation / train_clip()'s counter, for the record
+        if resume:
+            step = self._find_resume_step()
+            if step is None:
+                logging.info("resume: no checkpoint with complete resume records tagged %r under %s -- starting from step 0",
+                             self.resume_tag, self.base_exp_dir)
+            else:
+                latest_model_name = "ckpt_{:0>6d}.pth".format(step)
+                self._resume_record = self._read_resume_record(step, self.rank)
+                self.resumed_from = step
+        elif is_continue:
             model_list = [m for m in os.listdir(os.path.join(self.base_exp_dir, "checkpoints"))
                           if m[-3:] == "pth" and int(m[5:-4]) <= self.end_iter]
             model_list.sort()
@@ -296,10 +317,13 @@ class Runner:
             if clip_stage:
                 print(self.base_exp_dir)
             print("iter:{:8>d} loss = {} lr={}".format(self.iter_step, loss.item(), self.optimizer.param_groups[0]["lr"]))
-        if self.iter_step % self.save_freq == 0 and self.rank == 0:
+        saving = self.iter_step % self.save_freq == 0
+        if saving and self.rank == 0:
             self.save_checkpoint()
         self._validation_hooks(clip_stage)
         self.update_learning_rate()
+        if saving:      # here and not beside save_checkpoint: the hooks above draw from the data streams, and no view is in flight
+            self.save_resume_record()
 
     def _zero_grad(self):
         self.optimizer.zero_grad(set_to_none=self.grad_bucket is None)
@@ -329,12 +353,21 @@ class Runner:
         self._open_writer()
         self.update_learning_rate()
         res_step = self.end_iter - self.iter_step
-        image_perm = self.get_image_perm()
+        record = self._restore_resume_record()
+        if record is not None and record["image_perm"] is not None:
+            # the interrupted epoch's permutation, without the start-of-run draw; a record taken at an epoch's last step precedes the
+            # reshuffle the uninterrupted run made right after it: that draw is made here, from the restored streams
+            self._image_perm = record["image_perm"]
+            if self.iter_step % len(self._image_perm) == 0:
+                self._image_perm = self.get_image_perm()
+        else:
+            self._image_perm = self.get_image_perm()
         for _ in range(res_step):
+            image_perm = self._image_perm
             data = self.dataset.gen_random_rays_at(image_perm[self.iter_step % len(image_perm)], self.batch_size)
             self._after_step(self.train_iteration(data), clip_stage=False)
             if self.iter_step % len(image_perm) == 0:
-                image_perm = self.get_image_perm()
+                self._image_perm = self.get_image_perm()
         if self.writer is not None:
             self.writer.flush()
 
@@ -442,9 +475,13 @@ class Runner:
         self._open_writer()
         self.update_learning_rate()
         res_step = self.end_iter - self.iter_step
-        for iter_i in range(res_step):
+        record = self._restore_resume_record()
+        # (a resumed run counts on from the interrupted run's iter_i: the face camera, the prompt choice and the stop below stay in phase)
+        first = 0 if record is None or record["iter_i"] is None else int(record["iter_i"])
+        for iter_i in range(first, first + res_step):
             if iter_i == 30010:  # main.py:346-347
                 break
+            self._next_iter_i = iter_i + 1
             self._after_step(self.train_clip_iteration(iter_i), clip_stage=True)
         if self.writer is not None:
             self.writer.flush()
@@ -937,7 +974,7 @@ class Runner:
                     copyfile(os.path.join(dir_name, f_name), os.path.join(cur_dir, f_name))
         copyfile(self.conf_path, os.path.join(self.base_exp_dir, "recording", "config.conf"))
 
-    def _torch_load(self, path):
+    def _torch_load(self, path, map_location=None):
         """checkpoints of this stage hold tensors, the optimizer's plain containers and an int: the tensors-only unpickler reads
         them without executing code from the file.  A file it rejects is loaded with the full unpickler -- which executes code from
         the file, as the reference's plain torch.load does -- only with the same explicit opt-in as the other loaders
@@ -954,13 +991,13 @@ class Runner:
             # (files written under numpy 1 -- the reference's shipped checkpoint -- name it by its old module path)
             safe += [np_scalar, (np_scalar, "numpy.core.multiarray.scalar"), (np_scalar, "numpy._core.multiarray.scalar")]
             with torch.serialization.safe_globals(safe):
-                return torch.load(path, map_location=self.device, weights_only=True)
+                return torch.load(path, map_location=self.device if map_location is None else map_location, weights_only=True)
         except pickle.UnpicklingError as e:
             if os.environ.get("AVC_ALLOW_UNSAFE_PICKLE") != "1":
                 raise RuntimeError("%s is not a tensors-only checkpoint (%s); loading it would execute pickled code (set "
                                    "AVC_ALLOW_UNSAFE_PICKLE=1 to allow that)" % (path, str(e)[:200])) from e
             logging.warning("%s is not a tensors-only checkpoint: loading it with the full unpickler (AVC_ALLOW_UNSAFE_PICKLE=1)", path)
-            return torch.load(path, map_location=self.device, weights_only=False)
+            return torch.load(path, map_location=self.device if map_location is None else map_location, weights_only=False)
 
     def load_checkpoint(self, checkpoint_name):
         checkpoint = self._torch_load(os.path.join(self.base_exp_dir, "checkpoints", checkpoint_name))
@@ -985,7 +1022,77 @@ class Runner:
             "iter_step": self.iter_step,
         }
         os.makedirs(os.path.join(self.base_exp_dir, "checkpoints"), exist_ok=True)
-        torch.save(checkpoint, os.path.join(self.base_exp_dir, "checkpoints", "ckpt_{:0>6d}.pth".format(self.iter_step)))
+        _save_atomically(checkpoint, os.path.join(self.base_exp_dir, "checkpoints", "ckpt_{:0>6d}.pth".format(self.iter_step)))
+
+    # ------------------------------------------------------------------ resume records
+    # <base_exp_dir>/resume/ckpt_<step>.rank<r>.pt beside checkpoints/ckpt_<step>.pth: what the checkpoint (the reference's format, left
+    # as it is) does not hold of a run -- where its data streams stand.  Tensors, ints, floats, strings and None only (_torch_load reads it
+    # with the tensors-only unpickler).  Not in checkpoints/, and not named *pth: the is_continue listing parses every such name there.
+    def _resume_record_path(self, step, rank):
+        return os.path.join(self.base_exp_dir, "resume", "ckpt_{:0>6d}.rank{:d}.pt".format(step, rank))
+
+    def save_resume_record(self):
+        """this rank's record of the current step.  Called at the end of _after_step, after the checkpoint is in place: a complete set of
+        records means a complete checkpoint."""
+        record = {
+            "iter_step": int(self.iter_step), "mode": str(self.mode), "world": int(self.world), "rank": int(self.rank),
+            "views_per_iter": int(self.views_per_iter), "shard_view": bool(self.shard_view), "resume_tag": self.resume_tag,
+            "base_seed": getattr(self, "base_seed", self.seed), "data_seed": getattr(self, "data_seed", self.seed),
+            "streams": pack_rng_state(self._data_rng_state()), "view_streams": [pack_rng_state(s) for s in self._view_rngs],
+            "iter_i": None if self._next_iter_i is None else int(self._next_iter_i),
+            "image_perm": None if self._image_perm is None else self._image_perm.detach().cpu().clone(),
+        }
+        path = self._resume_record_path(self.iter_step, self.rank)
+        os.makedirs(os.path.dirname(path), exist_ok=True)
+        _save_atomically(record, path)
+
+    def _read_resume_record(self, step, rank):
+        """the record of (step, rank), its tensors on the host (generator states are host data); None when there is none"""
+        path = self._resume_record_path(step, rank)
+        return self._torch_load(path, map_location="cpu") if os.path.isfile(path) else None
+
+    def _find_resume_step(self):
+        """resume=True: the newest step <= end_iter whose checkpoint and whose records of all ranks exist and carry this run's tag, or
+        None.  Rank 0 looks, every rank gets its answer.  A record written by another kind of run (world size, views per step, view
+        sharding, mode) is refused with both values named: its streams are not those of this run's views."""
+        found = -1
+        if self.rank == 0:
+            ckpt_dir = os.path.join(self.base_exp_dir, "checkpoints")
+            names = os.listdir(ckpt_dir) if os.path.isdir(ckpt_dir) else []
+            steps = sorted((int(m[5:-4]) for m in names if m[:5] == "ckpt_" and m[-4:] == ".pth" and m[5:-4].isdigit()), reverse=True)
+            for step in steps:
+                if step > self.end_iter:
+                    continue
+                records = [self._read_resume_record(step, 0)]
+                if records[0] is not None and records[0]["world"] == self.world:      # (another world size: refused below)
+                    records += [self._read_resume_record(step, k) for k in range(1, self.world)]
+                if all(r is not None and r["resume_tag"] == self.resume_tag and r["iter_step"] == step for r in records):
+                    found = step
+                    break
+        if parallel.is_on():
+            t = torch.tensor([found], dtype=torch.int64, device=self.device)
+            parallel.broadcast_tensor(t)
+            found = int(t.item())
+        if found < 0:
+            return None
+        record = self._read_resume_record(found, 0)
+        for key, mine in (("world", self.world), ("views_per_iter", self.views_per_iter), ("shard_view", self.shard_view), ("mode", self.mode)):
+            if record[key] != mine:
+                raise ValueError("resume: the records of step %d under %s were written by a run with %s = %r, this run has %s = %r; "
+                                 "its data streams cannot be continued (restart the run without resume)"
+                                 % (found, self.base_exp_dir, key, record[key], key, mine))
+        return found
+
+    def _restore_resume_record(self):
+        """at the top of train() / train_clip(): put the streams of the interrupted run in place -- after init_clip, init_smpl and the
+        dataset have drawn whatever they draw while they are built -- and hand the record on (None: not a resumed run)"""
+        record, self._resume_record = self._resume_record, None
+        if record is None:
+            return None
+        self._set_data_rng_state(unpack_rng_state(record["streams"]))
+        self._view_rngs = [unpack_rng_state(s) for s in record["view_streams"]]
+        logging.info("resume: continuing %s at step %d", self.base_exp_dir, record["iter_step"])
+        return record
 
     def _render_chunks(self, rays_o, rays_d, keys, chunk=None, **render_kw):
         """render() over chunks of rays without keeping a graph (main.py:752-783 and its siblings); returns dict of cats."""
@@ -1135,6 +1242,36 @@ class Runner:
         mesh.write_ply(path, vertices, triangles, colors)
         logging.info("mesh: %d vertices, %d triangles -> %s", vertices.shape[0], triangles.shape[0], path)
         return path
+
+
+def _save_atomically(obj, path):
+    """torch.save under a temporary name beside `path`, then os.replace: a reader never finds a truncated file under the final name
+    (the temporary name does not end in pth either: the is_continue listing parses every such name in checkpoints/)"""
+    tmp = "%s.tmp.%d" % (path, os.getpid())
+    try:
+        torch.save(obj, tmp)
+        os.replace(tmp, path)
+    except BaseException:
+        if os.path.exists(tmp):
+            os.remove(tmp)
+        raise
+
+
+def pack_rng_state(state):
+    """Runner._data_rng_state() as tensors, ints, floats, strings and None (what the tensors-only unpickler reads back)"""
+    (np_name, np_keys, np_pos, np_has_gauss, np_cached), (py_version, py_internal, py_gauss_next), host, device = state
+    return {"numpy_name": str(np_name), "numpy_keys": torch.from_numpy(np.asarray(np_keys).astype(np.int64)), "numpy_pos": int(np_pos),
+            "numpy_has_gauss": int(np_has_gauss), "numpy_cached_gaussian": float(np_cached),
+            "random_version": int(py_version), "random_internal": torch.tensor(py_internal, dtype=torch.int64),
+            "random_gauss_next": None if py_gauss_next is None else float(py_gauss_next),
+            "torch_host": host.detach().cpu().clone(), "torch_device": None if device is None else device.detach().cpu().clone()}
+
+
+def unpack_rng_state(d):
+    """the inverse of pack_rng_state, bit for bit"""
+    return ((d["numpy_name"], d["numpy_keys"].numpy().astype(np.uint32), d["numpy_pos"], d["numpy_has_gauss"], d["numpy_cached_gaussian"]),
+            (d["random_version"], tuple(int(v) for v in d["random_internal"].tolist()), d["random_gauss_next"]),
+            d["torch_host"].to(torch.uint8), None if d["torch_device"] is None else d["torch_device"].to(torch.uint8))
 
 
 def clip_vit_random_state_dict(seed, patch=32):
