@@ -2,6 +2,7 @@
 // avc_render_points_fwd_train (forward-type operands, f16) and avc_render_points_bwd (gradient-type operands, bf16).
 #include "avc_common.h"
 #include "../../include/avc.h"
+#include <type_traits>
 
 // ---------------------------------------------------------------------------------------------
 // partial[split][ta][tb] = sum over the split's 32-point blocks, sum_kappa A[blk][ta][kappa] x B[blk][tb][kappa]
@@ -190,6 +191,306 @@ __device__ __forceinline__ void weight_grad_body(char* lds, const WgRegions& rg,
   }
 }
 
+// ---------------------------------------------------------------------------------------------
+// The products the full nets launch (packing.build_layout), with everything the block loop branches on in the run-time bodies made
+// a compile-time constant: the tile counts, the wave split, the operand types and whether the pair has a bias.  What depends on the
+// wave is chosen ONCE, before the loop (weight_grad_shipped, weight_grad_shipped_9x9).  The block loop is then one straight-line
+// region: one counted vmcnt immediate, the barrier, the copy of block blk + WG_DEPTH - 1, the transpose reads, the MFMAs.  Every
+// accumulator still receives k-step 0, then k-step 1 of each block, blocks ascending, and the bias sums keep the order of their
+// additions: the same bits as the run-time bodies.
+// ---------------------------------------------------------------------------------------------
+template <int N>
+__device__ __forceinline__ void wait_vmcnt_imm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
+
+// The MC copies one wave issues per block of a TA + TB tile product (chunk c = wv + 8 j of the block, j < MC).  The copies of a
+// split are issued block after block, so instruction j keeps the address of its chunk in the next block to copy and steps by its
+// region's bytes per block: the addresses of weight_grad_body's issue().
+template <int MC, int TA, int TYA, int TYB>
+struct WgCopies {
+  const char* next[MC];
+  long step[MC];
+  unsigned src_lo;
+  int wv;
+  __device__ __forceinline__ WgCopies(const WgRegions& rg, int pa, int pb, long b0, int wv_, int lane) : wv(wv_) {
+    src_lo = (((lane >> 2) & 3) * 32 + 4 * (lane >> 4) + (lane & 3)) * 16;
+#pragma unroll
+    for (int j = 0; j < MC; ++j) {
+      const int c = wv + 8 * j, tix = c >> 1;
+      const bool in_a = tix < TA;
+      step[j] = in_a ? rg.stride[TYA] : rg.stride[TYB];
+      next[j] = (in_a ? rg.base[TYA] + (long)(pa + tix) * 2048 : rg.base[TYB] + (long)(pb + tix - TA) * 2048) + b0 * step[j] + (c & 1) * 256;
+    }
+  }
+  __device__ __forceinline__ void issue(char* lds, int slot) {
+#pragma unroll
+    for (int j = 0; j < MC; ++j) {
+      asm("" : "+s"(next[j]));   // the running address stays a scalar; the lanes share one offset register
+      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(next[j] + src_lo),
+                                       (__attribute__((address_space(3))) void*)(lds + slot * WG_BUF_BYTES + (wv + 8 * j) * 1024), 16, 0,
+                                       WG_DMA_AUX);
+      next[j] += step[j];
+    }
+  }
+};
+
+// The ring of weight_grad_body around contract(buffer of the block): the last WG_DEPTH - 1 blocks of a split, which issue no copy
+// and wait for fewer, run in a peeled tail, so that the steady state waits with ONE immediate and issues unconditionally.
+template <int MC, class Copies, class Contract>
+__device__ __forceinline__ void wg_ring(char* lds, Copies& cp, long b0, long b1, Contract&& contract) {
+  constexpr int depth = WG_DEPTH;
+  const int n = (int)(b1 - b0);
+  for (int d = 0; d < depth - 1; ++d)
+    if (d < n) cp.issue(lds, d);
+  int slot = 0;
+  auto block = [&](auto ahead) {
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // my reads of block blk - 1 are done
+    __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_sched_barrier(0);
+    if constexpr (decltype(ahead)::value) cp.issue(lds, slot == 0 ? depth - 1 : slot - 1);
+    contract(lds + slot * WG_BUF_BYTES);
+    if (++slot == depth) slot = 0;
+  };
+  int i = 0;
+  for (; i + depth - 1 < n; ++i) {
+    wait_vmcnt_imm<(depth - 2) * MC>();   // LDS-DMA completes in issue order: block b0 + i has landed
+    block(std::true_type{});
+  }
+  for (; i < n; ++i) {
+    int younger = n - 1 - i;
+    if (younger > depth - 2) younger = depth - 2;
+    wait_vmcnt(younger * MC);
+    block(std::false_type{});
+  }
+}
+
+__device__ __forceinline__ int wg_lane_off(int lane) {   // weight_grad_body's lane_off
+  return (((lane >> 5) * 2) * 16 + (((lane >> 4) & 1) * 2 + (lane & 1)) * 4 + ((lane & 15) >> 2)) * 16 + 8 * ((lane & 3) >> 1);
+}
+__device__ __forceinline__ void wg_store_tile(float* dst, int tile, int lane, const facc& v16) {
+  f4* d4 = reinterpret_cast<f4*>(dst + ((long)tile * 64 + lane) * 16);
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    f4 v;
+    v[0] = v16[4 * q]; v[1] = v16[4 * q + 1]; v[2] = v16[4 * q + 2]; v[3] = v16[4 * q + 3];
+    d4[q] = v;
+  }
+}
+// bsum + the 16 values of the two fragments of an A tile, in weight_grad_body's order
+__device__ __forceinline__ float wg_row_sum(float bsum, b8 s0, b8 s1) {
+#pragma unroll
+  for (int j = 0; j < 8; ++j) bsum += (float)s0[j] + (float)s1[j];
+  return bsum;
+}
+
+// weight_grad_body<NI, NK> with WA for one TA x TB product.  LASTA / LASTB = this wave has its last A / B slot (the seventh A tile
+// of a 7 x 8 product exists only for wa = 0, the ninth B tile of 8 x 9 only for wb = 0), HI = it issues the larger of the two
+// possible numbers of copies per block.  k-step 0 of every tile is read first and its MFMAs go over all accumulators before
+// k-step 1's, so that no MFMA waits for the one before it.  The bias row sums of A slot i are the job of wave column wb = i: the
+// fragments are picked by a select; a wave that is responsible for no slot sums something it never stores.
+template <int NI, int NK, int TA, int TB, int WA, int TYA, int TYB, bool BIAS, bool LASTA, bool LASTB, bool HI>
+__device__ __forceinline__ void weight_grad_fixed(char* lds, const WgRegions& rg, int pa, int pb, long nblk, float* __restrict__ partial,
+                                                  float* __restrict__ bias_partial, int out_elems, int bias_elems) {
+  constexpr int WB = 8 / WA, nchunk = 2 * (TA + TB);
+  constexpr int MC = HI ? (nchunk + 7) / 8 : nchunk / 8;              // DMA instructions this wave issues per block
+  constexpr int NIW = LASTA ? NI : NI - 1, NKW = LASTB ? NK : NK - 1;   // A / B slots of this wave
+  static_assert(WA * (NI - 1) < TA && WA * (NI - 2) + WA - 1 < TA && WB * (NK - 1) < TB && WB * (NK - 2) + WB - 1 < TB,
+                "only the last slot of either side may be missing for some waves");
+  const int lane = threadIdx.x & 63;
+  const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) & 7;
+  const int wa = wv % WA, wb = wv / WA;
+  const int split = blockIdx.x, nsplit = gridDim.x;
+  const long b0 = nblk * split / nsplit, b1 = nblk * (split + 1) / nsplit;
+  WgCopies<MC, TA, TYA, TYB> cp(rg, pa, pb, b0, wv, lane);
+  const int lane_off = wg_lane_off(lane);
+  facc acc[NI * NK];
+#pragma unroll
+  for (int q = 0; q < NI * NK; ++q)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[q][r] = 0.f;
+  float bsum = 0.f;
+  wg_ring<MC>(lds, cp, b0, b1, [&](char* slot_buf) {
+    lds_char* buf = (lds_char*)slot_buf + lane_off;
+    b8 a[NI][2], bv[NK][2];
+    auto read = [&](int t) {
+#pragma unroll
+      for (int i = 0; i < NIW; ++i) a[i][t] = tr_frag(buf + (wa + WA * i) * 2048, t);
+#pragma unroll
+      for (int k = 0; k < NKW; ++k) bv[k][t] = tr_frag(buf + (TA + wb + WB * k) * 2048, t);
+    };
+    auto convert = [&](int t) {
+      if constexpr (TYA == 0) {
+#pragma unroll
+        for (int i = 0; i < NIW; ++i) a[i][t] = f16_to_bf16(a[i][t]);
+      }
+      if constexpr (TYB == 0) {
+#pragma unroll
+        for (int k = 0; k < NKW; ++k) bv[k][t] = f16_to_bf16(bv[k][t]);
+      }
+    };
+    auto mfmas = [&](int t) {
+#pragma unroll
+      for (int i = 0; i < NIW; ++i)
+#pragma unroll
+        for (int k = 0; k < NKW; ++k) acc[i * NK + k] = MF<b8>::mma(a[i][t], bv[k][t], acc[i * NK + k]);
+    };
+    // While an LDS-DMA is in flight the compiler waits for ALL outstanding LDS reads at the first use of any of them (it cannot
+    // count past a FLAT-encoded operation), so the order is pinned: the reads of k-step 0, their conversion (the one full wait),
+    // then the reads of k-step 1 under the MFMAs of k-step 0.
+    read(0);
+    __builtin_amdgcn_sched_barrier(0);
+    convert(0);
+    __builtin_amdgcn_sched_barrier(0);
+    read(1);
+    mfmas(0);
+    __builtin_amdgcn_sched_barrier(0);
+    convert(1);
+    mfmas(1);
+    if constexpr (BIAS) {
+      b8 s0 = a[0][0], s1 = a[0][1];
+#pragma unroll
+      for (int i = 1; i < NIW; ++i) { s0 = wb == i ? a[i][0] : s0; s1 = wb == i ? a[i][1] : s1; }
+      bsum = wg_row_sum(bsum, s0, s1);
+    }
+  });
+  float* dst = partial + (long)split * out_elems;
+#pragma unroll
+  for (int i = 0; i < NIW; ++i)
+#pragma unroll
+    for (int k = 0; k < NKW; ++k) wg_store_tile(dst, (wa + WA * i) * TB + wb + WB * k, lane, acc[i * NK + k]);
+  if constexpr (BIAS) {
+    if (wb < NIW) {
+      const float s = xhalf_sum(bsum);
+      if (lane < 32) bias_partial[(long)split * bias_elems + (wa + WA * wb) * 32 + lane] = s;
+    }
+  }
+}
+
+// the roles of this wave in a shipped product, picked once
+template <int NI, int NK, int TA, int TB, int WA, int TYA, int TYB, bool BIAS>
+__device__ __forceinline__ void weight_grad_shipped(char* lds, const WgRegions& rg, int pa, int pb, long nblk, float* __restrict__ partial,
+                                                    float* __restrict__ bias_partial, int out_elems, int bias_elems) {
+  constexpr int WB = 8 / WA, nchunk = 2 * (TA + TB);
+  constexpr bool role_a = WA * (NI - 1) + WA - 1 >= TA, role_b = WB * (NK - 1) + WB - 1 >= TB, role_hi = (nchunk & 7) != 0;
+  const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) & 7;
+  const bool lasta = !role_a || wv % WA + WA * (NI - 1) < TA, lastb = !role_b || wv / WA + WB * (NK - 1) < TB;
+  const bool hi = !role_hi || wv < (nchunk & 7);
+#define WG_ROLE(LA, LB, H)                                                                                                            \
+  if ((LA || role_a) && (LB || role_b) && (H || role_hi) && lasta == LA && lastb == LB && hi == H)                                  \
+    return weight_grad_fixed<NI, NK, TA, TB, WA, TYA, TYB, BIAS, LA || !role_a, LB || !role_b, H || !role_hi>(                        \
+        lds, rg, pa, pb, nblk, partial, bias_partial, out_elems, bias_elems);
+  WG_ROLE(true, true, true) WG_ROLE(true, true, false) WG_ROLE(true, false, true) WG_ROLE(true, false, false)
+  WG_ROLE(false, true, true) WG_ROLE(false, true, false) WG_ROLE(false, false, true) WG_ROLE(false, false, false)
+#undef WG_ROLE
+}
+
+// weight_grad_body_9x9 (below) for one role of the wave (wa, wb):
+//   ROLE 0: wave (0, 0): B tiles 0, 2, .., 8 against A tiles 0 and 4, and B tile 8 against the ninth A tile;
+//   ROLE 1: waves (1..3, 0): B tiles 0, 2, .., 8 against A tiles wa and wa + 4;
+//   ROLE 2: waves (1..3, 1): B tiles 1, 3, 5, 7 against A tiles wa and wa + 4, B tiles 2 wa + 1 and 2 wa against the ninth A tile;
+//   ROLE 3: wave (0, 1): as ROLE 2, and the bias row sums of the ninth A tile.
+// A wave of column 1 takes its four B tiles in the order 2 wa + 1, 2 wa + 3, .. (mod 8), so that the one that also meets the ninth A
+// tile is slot 0 for every wa: which tile an accumulator belongs to is an address, not a register number.
+template <int ROLE, int TYA, int TYB, bool BIAS>
+__device__ __forceinline__ void weight_grad_fixed_9x9(char* lds, const WgRegions& rg, int pa, int pb, long nblk, float* __restrict__ partial,
+                                                      float* __restrict__ bias_partial, int out_elems, int bias_elems) {
+  constexpr int TA = 9, TB = 9;
+  constexpr bool COL1 = ROLE >= 2, HAS_X = ROLE != 1;
+  constexpr int MC = COL1 ? 4 : 5;      // 36 chunks: five copies per block for waves 0..3, four for waves 4..7
+  constexpr int NR = COL1 ? 4 : 5;      // B tiles against A tiles wa, wa + 4
+  constexpr int XK = COL1 ? 0 : 4;      // the one of them that also meets the ninth A tile
+  const int lane = threadIdx.x & 63;
+  const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) & 7;
+  const int wa = wv & 3;
+  const int split = blockIdx.x, nsplit = gridDim.x;
+  const long b0 = nblk * split / nsplit, b1 = nblk * (split + 1) / nsplit;
+  WgCopies<MC, TA, TYA, TYB> cp(rg, pa, pb, b0, wv, lane);
+  const int lane_off = wg_lane_off(lane);
+  int tb_of[NR];
+#pragma unroll
+  for (int k = 0; k < NR; ++k) tb_of[k] = COL1 ? 1 + 2 * ((wa + k) & 3) : 2 * k;
+  facc acc[2 * NR], ex[2];
+#pragma unroll
+  for (int q = 0; q < 2 * NR; ++q)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[q][r] = 0.f;
+#pragma unroll
+  for (int q = 0; q < 2; ++q)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) ex[q][r] = 0.f;
+  float bsum = 0.f, xsum = 0.f;
+  wg_ring<MC>(lds, cp, b0, b1, [&](char* slot_buf) {
+    lds_char* buf = (lds_char*)slot_buf + lane_off;
+    b8 a[2][2], sa[2], bv[2];
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+      a[0][t] = tr_frag(buf + wa * 2048, t);
+      a[1][t] = tr_frag(buf + (wa + 4) * 2048, t);
+      if constexpr (HAS_X) sa[t] = tr_frag(buf + 8 * 2048, t);
+      if constexpr (TYA == 0) {
+        a[0][t] = f16_to_bf16(a[0][t]); a[1][t] = f16_to_bf16(a[1][t]);
+        if constexpr (HAS_X) sa[t] = f16_to_bf16(sa[t]);
+      }
+    }
+    if constexpr (BIAS) bsum = wg_row_sum(bsum, a[COL1][0], a[COL1][1]);      // wave (wa, wb): row sums of A tile wa + 4 wb
+    if constexpr (BIAS && ROLE == 3) xsum = wg_row_sum(xsum, sa[0], sa[1]);
+    // B fragments are streamed one tile ahead of their MFMAs, as in weight_grad_body_9x9 (all of them do not fit beside 11 accumulators)
+    auto load_b = [&](int k, b8* f) {      // (column 1: slot NR is B tile 2 wa, which meets the ninth A tile only)
+      const int tb = k < NR ? tb_of[k < NR ? k : 0] : 2 * wa;
+      f[0] = tr_frag(buf + (TA + tb) * 2048, 0);
+      f[1] = tr_frag(buf + (TA + tb) * 2048, 1);
+    };
+    b8 nx[2];
+    load_b(0, bv);
+    nx[0] = bv[0]; nx[1] = bv[1];
+#pragma unroll
+    for (int k = 0; k < NR + COL1; ++k) {
+      if (k + 1 < NR + COL1) load_b(k + 1, nx);
+      asm volatile("" : "+v"(nx[0]), "+v"(nx[1]));
+      if constexpr (TYB == 0) { bv[0] = f16_to_bf16(bv[0]); bv[1] = f16_to_bf16(bv[1]); }
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+        if (k < NR) {
+          acc[k] = MF<b8>::mma(a[0][t], bv[t], acc[k]);
+          acc[NR + k] = MF<b8>::mma(a[1][t], bv[t], acc[NR + k]);
+          if constexpr (HAS_X) {
+            if (k == XK) ex[0] = MF<b8>::mma(sa[t], bv[t], ex[0]);
+          }
+        } else {
+          ex[1] = MF<b8>::mma(sa[t], bv[t], ex[1]);
+        }
+      }
+      bv[0] = nx[0]; bv[1] = nx[1];
+    }
+  });
+  float* dst = partial + (long)split * out_elems;
+#pragma unroll
+  for (int k = 0; k < NR; ++k) {
+    wg_store_tile(dst, wa * TB + tb_of[k], lane, acc[k]);
+    wg_store_tile(dst, (wa + 4) * TB + tb_of[k], lane, acc[NR + k]);
+  }
+  if constexpr (HAS_X) wg_store_tile(dst, 8 * TB + tb_of[XK], lane, ex[0]);
+  if constexpr (COL1) wg_store_tile(dst, 8 * TB + 2 * wa, lane, ex[1]);
+  if constexpr (BIAS) {
+    const float sx = xhalf_sum(bsum);
+    if (lane < 32) bias_partial[(long)split * bias_elems + (wa + 4 * COL1) * 32 + lane] = sx;
+    if constexpr (ROLE == 3) {
+      const float sy = xhalf_sum(xsum);
+      if (lane < 32) bias_partial[(long)split * bias_elems + 8 * 32 + lane] = sy;
+    }
+  }
+}
+template <int TYA, int TYB, bool BIAS>
+__device__ __forceinline__ void weight_grad_shipped_9x9(char* lds, const WgRegions& rg, int pa, int pb, long nblk, float* __restrict__ partial,
+                                                        float* __restrict__ bias_partial, int out_elems, int bias_elems) {
+  const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) & 7;
+#define WG_ROLE(R) weight_grad_fixed_9x9<R, TYA, TYB, BIAS>(lds, rg, pa, pb, nblk, partial, bias_partial, out_elems, bias_elems)
+  if (wv == 0) WG_ROLE(0);
+  else if (wv < 4) WG_ROLE(1);
+  else if (wv > 4) WG_ROLE(2);
+  else WG_ROLE(3);
+#undef WG_ROLE
+}
+
 // The merged last-layer product: A = [ybar[1:] (8 tiles) | d_sdf row (1 tile)], B = [hs (7) | pe (2)], 9 x 9 output tiles, so that
 // [hs | pe] is read from HBM once for the 256 feature rows AND the sdf row.  Waves 4 x 2 over the 8 x 9 part as in the generic
 // body (A tiles wa, wa + 4; B tiles wb, wb + 2, ..: 10 products for wb = 0, 8 for wb = 1); the nine products of the ninth A tile go to
@@ -351,9 +652,30 @@ __global__ __launch_bounds__(512) void weight_grad_all_kernel(WgRegions rg, WgPa
   // wide x wide: 2 x 4 (or 4 x 2) tiles per wave, the f16 operand on the side with fewer tiles per wave (it is converted to bf16
   // after the read); narrow pairs: 8 x 1 or 1 x 8 waves
 #define WG_ARGS lds, rg, d[0], d[1], d[2], d[3], d[6], d[7], nblk, partial + d[4], bp, out_elems, bias_elems
-  if (d[1] > 1 && d[3] > 2 && d[3] <= 8) {
+  // the products of the full nets: <NI, NK, TA, TB, WA, type_a, type_b, bias>, the wave split of the run-time bodies below
+#define WG_SHIPPED(...) weight_grad_shipped<__VA_ARGS__>(lds, rg, d[0], d[2], nblk, partial + d[4], bp, out_elems, bias_elems)
+  const bool gxf_bias = d[6] == 1 && d[7] == 0 && bp, fxg_plain = d[6] == 0 && d[7] == 1 && !bp;
+  if (gxf_bias && d[1] == 8 && d[3] == 8) {
+    WG_SHIPPED(4, 2, 8, 8, 2, 1, 0, true);
+  } else if (fxg_plain && d[1] == 8 && d[3] == 8) {
+    WG_SHIPPED(2, 4, 8, 8, 4, 0, 1, false);
+  } else if (gxf_bias && d[1] == 7 && d[3] == 8) {
+    WG_SHIPPED(4, 2, 7, 8, 2, 1, 0, true);
+  } else if (fxg_plain && d[1] == 7 && d[3] == 8) {
+    WG_SHIPPED(2, 4, 7, 8, 4, 0, 1, false);
+  } else if (gxf_bias && d[1] == 8 && d[3] == 9) {
+    WG_SHIPPED(2, 5, 8, 9, 4, 1, 0, true);
+  } else if (gxf_bias && d[1] == 8 && d[3] == 2) {
+    WG_SHIPPED(1, 2, 8, 2, 8, 1, 0, true);
+  } else if (fxg_plain && d[1] == 8 && d[3] == 2) {
+    WG_SHIPPED(1, 2, 8, 2, 8, 0, 1, false);
+  } else if (gxf_bias && d[1] == 1 && d[3] == 8) {
+    WG_SHIPPED(1, 1, 1, 8, 1, 1, 0, true);
+  } else if (d[1] > 1 && d[3] > 2 && d[3] <= 8) {
     if (d[7] == 0) weight_grad_body<4, 2>(WG_ARGS, 2);
     else weight_grad_body<2, 4>(WG_ARGS, 4);
+  } else if (gxf_bias && d[1] == 9 && d[3] == 9) {
+    weight_grad_shipped_9x9<1, 0, true>(lds, rg, d[0], d[2], nblk, partial + d[4], bp, out_elems, bias_elems);
   } else if (d[1] == 9 && d[3] == 9) {
     weight_grad_body_9x9(lds, rg, d[0], d[2], d[6], d[7], nblk, partial + d[4], bp, out_elems, bias_elems);
   } else if (d[1] > 1 && d[3] > 8) {
@@ -363,6 +685,7 @@ __global__ __launch_bounds__(512) void weight_grad_all_kernel(WgRegions rg, WgPa
   } else {
     weight_grad_body<1, 2>(WG_ARGS, 1);      // a single A tile: 1 x 8 waves, one (or two) B tiles each
   }
+#undef WG_SHIPPED
 #undef WG_ARGS
 }
 
