@@ -110,7 +110,10 @@ class AnimateContext:
       smpl          smpl_lbs.load_smpl_arrays(...) dict (v_template, posedirs, J_regressor, parents, lbs_weights, faces)
       vposer        VPoser-like object: decode(z[B,32]) -> {'pose_body': [B,21,3]}, encode(pose[B,63]).mean -> [B,32]
       render_fn     callable(vertices[bs,V,3] tensor, faces, angles) -> images [len(angles) * bs, 3, H, W] in [0,1], camera-major
-                    (None: the HIP rasteriser below; the reference textures the body with data/smpl_uv.obj, which its repository does not hold)
+                    (None: the HIP rasteriser below -- a white body, or the textured one when `texture` is given)
+      texture       None (default): the body is white.  The path of a textured .obj (the reference's data/smpl_uv.obj; texture.load_obj_texture,
+                    texture_size 8) or its cubes [F,8,8,8,3]: the default render_fn shows that body (mesh_render.render_rgb_batch), with or
+                    without renderer_gradient.  A precomputed codebook matches it only if it was made with the same texture.
       renderer_gradient False (default): render_fn's images carry no gradient and the generators that need one refuse to run; True: the default
                     render_fn is the differentiable HIP path (mesh_render.render_grey_batch), a given render_fn is taken to be differentiable
       posing        "torch" (default): posed_vertices is smpl_lbs.lbs, differentiated by autograd -- the arithmetic the pinned scores were
@@ -119,7 +122,8 @@ class AnimateContext:
     """
     POSINGS = ("torch", "hip")
 
-    def __init__(self, perceptor, text_feature, smpl, vposer, render_fn=None, device=None, image_size=256, renderer_gradient=False, posing="torch"):
+    def __init__(self, perceptor, text_feature, smpl, vposer, render_fn=None, device=None, image_size=256, renderer_gradient=False, posing="torch",
+                 texture=None):
         if posing not in self.POSINGS:
             raise ValueError("AnimateContext: posing is \"torch\" (smpl_lbs.lbs) or \"hip\" (smpl_lbs.pose_hip_grad), got %r" % (posing,))
         self.posing = posing
@@ -127,6 +131,10 @@ class AnimateContext:
         self.device = torch.device(device) if device is not None else smpl["v_template"].device
         self.image_size = image_size
         self.renderer_gradient = bool(renderer_gradient)
+        self.texture = None
+        if texture is not None:
+            from .texture import as_cubes
+            self.texture = as_cubes(texture, self.device)
         default = self._render_hip_grad if self.renderer_gradient else self._render_hip
         self.render_fn = render_fn if render_fn is not None else default
 
@@ -158,14 +166,16 @@ class AnimateContext:
     def _render_hip_grad(self, vertices, faces, angles):
         """models/render.py:10-39 on the HIP rasteriser: camera_mode 'look_at' at distance 2, azimuth = the angle, elevation drawn per angle
         from numpy's global generator (np.random.randn() * 0.3 degrees: the reference's draw, in its order).  White body under
-        neural_renderer's light -- the UV texture is an input of `render_fn` replacements.  The len(angles) x bs renders camera-major in one
+        neural_renderer's light, or (AnimateContext(texture=...)) the textured body through mesh_render.render_rgb_batch.  The len(angles) x bs renders camera-major in one
         call of mesh_render.render_grey_batch (one batched forward-with-save, neural_renderer's approximate backward to the vertices)."""
-        from .mesh_render import render_grey_batch
+        from .mesh_render import render_grey_batch, render_rgb_batch
         from .shapegen_render import get_points_from_angles
         eyes = [get_points_from_angles(CAMERA_DISTANCE, np.random.randn() * 0.3, a) for a in angles]     # draw order: once per angle, before the batch loop
         bs = vertices.shape[0]
         eye_all = [e.astype(np.float32) for e in eyes for _ in range(bs)]
         dir_all = [(-e / np.linalg.norm(e)).astype(np.float32) for e in eyes for _ in range(bs)]
+        if getattr(self, "texture", None) is not None:           # models/render.py:6-35: the cubes of data/smpl_uv.obj on the same cameras
+            return render_rgb_batch(vertices, faces, self.texture, eye_all, dir_all, image_size=self.image_size)
         g = render_grey_batch(vertices, faces, eye_all, dir_all, image_size=self.image_size)
         return g.unsqueeze(1).expand(-1, 3, -1, -1)
 
@@ -581,7 +591,7 @@ def run(conf, ctx, pose_assets=None, motion_assets=None, preview=False, preview_
 
 
 def main(argv=None):
-    """python -m avatarclip_amd.animate [--renderer_gradient] [--hip_posing] [--preview] --conf confs/base.conf --clip_weights ViT-B-32.pt --bpe bpe_simple_vocab_16e6.txt.gz --smpl SMPL_NEUTRAL.pkl
+    """python -m avatarclip_amd.animate [--renderer_gradient] [--hip_posing] [--smpl_uv smpl_uv.obj] [--preview] --conf confs/base.conf --clip_weights ViT-B-32.pt --bpe bpe_simple_vocab_16e6.txt.gz --smpl SMPL_NEUTRAL.pkl
     --vposer data/vposer [--codebook data/codebook.pth] [--realnvp data/pose_realnvp.pth] [--motion_vae data/motion_vae.pth]
     (AvatarAnimate/main.py with the assets its constructors load named on the command line; VPoser itself comes from the `human_body_prior` package)"""
     import argparse
@@ -596,6 +606,10 @@ def main(argv=None):
     ap.add_argument("--hip_posing", action="store_true",
                     help="pose the body with smpl_lbs.pose_hip_grad (HIP, forward and backward) instead of smpl_lbs.lbs: equal to fp32 rounding, "
                          "not bit for bit")
+    ap.add_argument("--smpl_uv", default=None,
+                    help="the textured body (data/smpl_uv.obj with its .mtl and image): every render that is scored or optimised shows it instead "
+                         "of a white body, as AvatarAnimate/models/render.py:6-35 does; a precomputed codebook matches only if it was made with the "
+                         "same texture")
     ap.add_argument("--preview", action="store_true", help="also write candidate_<i>.png and, in motion mode, motion.gif: the SMPL body in those poses")
     ap.add_argument("--preview_size", type=int, default=512)
     for name in ("clip_weights", "bpe", "smpl", "vposer"):
@@ -614,7 +628,7 @@ def main(argv=None):
     tk = tokenizer.SimpleTokenizer(args.bpe)
     text_feature = lambda text: perceptor.encode_text(tokenizer.tokenize([text], tk))[0]
     ctx = AnimateContext(perceptor, text_feature, smpl_lbs.load_smpl_arrays(args.smpl, dev), vp.to(dev).eval(), device=dev,
-                         renderer_gradient=args.renderer_gradient, posing="hip" if args.hip_posing else "torch")
+                         renderer_gradient=args.renderer_gradient, posing="hip" if args.hip_posing else "torch", texture=args.smpl_uv)
     with open(args.conf) as fh:
         conf = ConfigFactory.parse_string(fh.read())
     pose_assets = {"codebook_path": args.codebook} if args.codebook else ({"ckpt_path": args.realnvp} if args.realnvp else {})

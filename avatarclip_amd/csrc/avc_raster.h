@@ -25,18 +25,26 @@ __device__ __forceinline__ bool face_setup(const float* __restrict__ f, int is, 
   e.den = e.p2x * (e.p0y - e.p1y) + e.p0x * (e.p1y - e.p2y) + e.p1x * (e.p2y - e.p0y);
   return e.den != 0.f;
 }
-__device__ __forceinline__ float face_depth(const FaceEq& e, int xi, int yi, int is, float near, float far) {
+// the clamped barycentric weights w of pixel (xi, yi), their sum ws (at least 1e-10; w / ws = the normalised weights) and the perspective-correct
+// depth zp: what face_depth tests and the textured resolve (avc_raster_tex.hip) samples with; false: the pixel centre is outside the face
+__device__ __forceinline__ bool face_weights(const FaceEq& e, int xi, int yi, int is, float (&w)[3], float& ws, float& zp) {
   const float xp = (2.f * xi + 1.f - is) / is;
   const float yp = (2.f * yi + 1.f - is) / is;
   if (((yp - e.y0) * (e.x1 - e.x0) < (xp - e.x0) * (e.y1 - e.y0)) || ((yp - e.y1) * (e.x2 - e.x1) < (xp - e.x1) * (e.y2 - e.y1)) ||
       ((yp - e.y2) * (e.x0 - e.x2) < (xp - e.x2) * (e.y0 - e.y2)))
-    return -1.f;
+    return false;
   float w0 = ((e.p1y - e.p2y) * xi + (e.p2x - e.p1x) * yi + (e.p1x * e.p2y - e.p2x * e.p1y)) / e.den;
   float w1 = ((e.p2y - e.p0y) * xi + (e.p0x - e.p2x) * yi + (e.p2x * e.p0y - e.p0x * e.p2y)) / e.den;
   float w2 = ((e.p0y - e.p1y) * xi + (e.p1x - e.p0x) * yi + (e.p0x * e.p1y - e.p1x * e.p0y)) / e.den;
   w0 = fminf(fmaxf(w0, 0.f), 1.f); w1 = fminf(fmaxf(w1, 0.f), 1.f); w2 = fminf(fmaxf(w2, 0.f), 1.f);
-  const float ws = fmaxf(w0 + w1 + w2, 1e-10f);
-  const float zp = 1.f / ((w0 / e.z0 + w1 / e.z1 + w2 / e.z2) / ws);
+  ws = fmaxf(w0 + w1 + w2, 1e-10f);
+  zp = 1.f / ((w0 / e.z0 + w1 / e.z1 + w2 / e.z2) / ws);
+  w[0] = w0; w[1] = w1; w[2] = w2;
+  return true;
+}
+__device__ __forceinline__ float face_depth(const FaceEq& e, int xi, int yi, int is, float near, float far) {
+  float w[3], ws, zp;
+  if (!face_weights(e, xi, yi, is, w, ws, zp)) return -1.f;
   return (zp > near && zp < far) ? zp : -1.f;        // (zp > near >= 0: its bit pattern orders like its value)
 }
 // the face's box in pixel indices, one pixel of slack each way (the edge functions decide); false: off screen (or NaN)
@@ -77,3 +85,9 @@ __device__ __forceinline__ void project_vertex(const float* __restrict__ vw, int
   ndc[3 * i + 1] = behind ? 0.f : c[1] / c[2] / width;
   ndc[3 * i + 2] = behind ? 0.f : c[2];
 }
+
+// The coverage launches every forward entry point shares (avc_raster.hip): the projection (v_world != NULL: cam [N,12] -> ndc [N,V,3]), one
+// wavefront per face and the tile pass of the large faces.  They leave the winners' (depth, face) keys in the N z-buffers of `scratch`
+// ([N z-buffers][N x (F + 2) list words]); a resolve launch reads them and puts the all-ones "empty" key and list count back.
+void raster_coverage(const float* v_world, int N, int V, const int* idx, int F, const float* cam, float width, int is, float near, float far,
+                     const float* ndc, void* scratch, void* stream);

@@ -147,8 +147,9 @@ __global__ __launch_bounds__(256) void raster_resolve_pool_kernel(unsigned long 
 // The launches of all three entry points: N renders of one topology at is x is, render b with its own ndc [V,3], z-buffer and large-face list
 // (scratch = [N z-buffers][N x (F + 2) list words]).  v_world != NULL (the mesh forms, is = 2 S): ndc is projected from it (cam [N,12]) and the
 // resolve pools.  v_world == NULL (the face-list form, N = 1): ndc holds the faces [F,9] themselves, idx is NULL and the resolve does not pool.
-static void raster_forward(const float* v_world, int N, int V, const int* idx, int F, const float* cam, float width, const float* light, int is,
-                           float near, float far, const float* ndc, float* out, int* fidx, int flip_x, int channels, void* scratch, void* stream) {
+// (the coverage half is raster_coverage, which the textured entry point of avc_raster_tex.hip launches too)
+void raster_coverage(const float* v_world, int N, int V, const int* idx, int F, const float* cam, float width, int is, float near, float far,
+                     const float* ndc, void* scratch, void* stream) {
   hipStream_t s = (hipStream_t)stream;
   unsigned long long* zbufs = (unsigned long long*)scratch;
   unsigned* larges = (unsigned*)(zbufs + (long)N * is * is);
@@ -158,6 +159,13 @@ static void raster_forward(const float* v_world, int N, int V, const int* idx, i
     const int nt = (is + RS_TILE - 1) / RS_TILE;
     hipLaunchKernelGGL(raster_large_kernel, dim3(nt, nt, N), dim3(256), 0, s, ndc, V, idx, F, is, near, far, zbufs, larges);
   }
+}
+static void raster_forward(const float* v_world, int N, int V, const int* idx, int F, const float* cam, float width, const float* light, int is,
+                           float near, float far, const float* ndc, float* out, int* fidx, int flip_x, int channels, void* scratch, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  unsigned long long* zbufs = (unsigned long long*)scratch;
+  unsigned* larges = (unsigned*)(zbufs + (long)N * is * is);
+  raster_coverage(v_world, N, V, idx, F, cam, width, is, near, far, ndc, scratch, stream);
   if (v_world)
     hipLaunchKernelGGL(raster_resolve_pool_kernel, dim3((is / 2 * (is / 2) + 255) / 256, N), dim3(256), 0, s, zbufs, light, F, is, out, fidx, flip_x,
                        channels, larges);

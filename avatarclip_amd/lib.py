@@ -1,5 +1,6 @@
-"""ctypes binding of libavc.so.  include/avc.h is the one declaration of the C ABI: load() parses it and derives every
-restype / argtypes from it, and call() checks each tensor against the element type the header gives its parameter.  No
+"""ctypes binding of libavc.so.  include/avc.h declares the C ABI, csrc/avc_texture.h the textured-render entry points added beside it:
+load() parses both, merges their prototypes and derives every restype / argtypes from them, and call() checks each tensor against the
+element type the header gives its parameter.  No
 fallback: if the library is missing, lacks a symbol the header declares, or a call fails, an exception is raised."""
 import collections
 import ctypes
@@ -14,6 +15,7 @@ _lib = None
 _launches = {}           # name -> the launcher bind() made, one per launch entry point (filled by load())
 ABI_VERSION = None       # AVC_ABI_VERSION of include/avc.h (set by load())
 HEADER = os.path.normpath(os.path.join(_build.CSRC, _build.ABI_HEADER))
+TEXTURE_HEADER = os.path.join(_build.CSRC, _build.TEXTURE_HEADER)     # more entry points of the same library and revision (it defines no AVC_ABI_VERSION)
 
 c_int, c_long, c_float, c_double, c_void_p, c_char_p = (ctypes.c_int, ctypes.c_long, ctypes.c_float, ctypes.c_double,
                                                         ctypes.c_void_p, ctypes.c_char_p)
@@ -140,8 +142,17 @@ def load():
     if not os.path.exists(path):
         raise RuntimeError("libavc.so is not built (run `python -c 'import __graft_entry__ as g; g.build()'`); "
                            "there is no CPU fallback for the HIP hot path")
-    with open(HEADER) as f:
-        protos, ABI_VERSION = parse_header(f.read())
+    protos, declared_in = {}, {}
+    for header in (HEADER, TEXTURE_HEADER):
+        with open(header) as f:
+            more, abi = parse_header(f.read())
+        if header == HEADER:
+            ABI_VERSION = abi
+        twice = sorted(set(more) & set(protos))
+        if twice:
+            raise RuntimeError("%s declares %s, which %s declares already" % (header, ", ".join(twice), declared_in[twice[0]]))
+        protos.update(more)
+        declared_in.update((name, header) for name in more)
     lib = ctypes.CDLL(path)
     got = lib.avc_version()
     if got != ABI_VERSION:
@@ -150,8 +161,9 @@ def load():
     for name, proto in protos.items():
         fn = getattr(lib, name, None)
         if fn is None:                                   # an added entry point does not change the revision: a library from before it
-            raise RuntimeError("%s implements revision %d of include/avc.h but lacks %s of include/%s: rebuild the library "
-                               "(python -m avatarclip_amd.build --force)" % (path, got, name, os.path.basename(HEADER)))
+            where = ("include/" if declared_in[name] == HEADER else "csrc/") + os.path.basename(declared_in[name])
+            raise RuntimeError("%s implements revision %d of include/avc.h but lacks %s of %s: rebuild the library "
+                               "(python -m avatarclip_amd.build --force)" % (path, got, name, where))
         fn.restype = proto.restype
         fn.argtypes = proto.argtypes
     _launches.update((name, bind(proto, getattr(lib, name))) for name, proto in protos.items() if proto.launch)
@@ -167,7 +179,7 @@ def call(name, *args, stream=None):
     try:
         launch = _launches[name]
     except KeyError:
-        raise AttributeError("include/avc.h declares no launch entry point %s" % name) from None
+        raise AttributeError("include/avc.h and csrc/avc_texture.h declare no launch entry point %s" % name) from None
     launch(*args, stream=stream)
 
 

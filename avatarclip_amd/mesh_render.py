@@ -1,5 +1,7 @@
 """Differentiable renders of a mesh for AvatarAnimate's CLIP-guided optimisers (AvatarAnimate/models/render.py:10-39):
-N grey renders of N vertex sets of one topology in one call, with autograd to the vertices.
+N grey renders of N vertex sets of one topology in one call, with autograd to the vertices -- and, opt-in, the same renders of the textured
+body (render_rgb_batch: neural_renderer's texture sampling on `avc_rasterize_mesh_tex_save` / `_tex_grad`, csrc/avc_raster_tex.hip; the cubes
+come from texture.load_obj_texture).
 
 Forward: neural_renderer's conventions as `smpl_prior.MeshPrior.render_grey` applies them (vertices @ rot_mat, fill_back, ambient 0.5 +
 directional 0.5 face light, 60 degree field of view, 2 x super-sampling) on the HIP rasteriser (`avc_rasterize_mesh_save`,
@@ -117,3 +119,78 @@ def render_grey_batch(v_world, faces, eyes, directions, image_size=256, eps=DEFA
     width = float(np.tan(np.deg2rad(VIEWING_ANGLE)))
     image, ndc, fidx = _RasterFn.apply(v, light2, cam, faces2, vf_ptr, vf_ent, int(image_size), width, float(eps))
     return (image, ndc, fidx) if return_state else image
+
+
+class _RasterTexFn(torch.autograd.Function):
+    """_RasterFn on the textured entry points: image [N,S,S,3]; the unlit colours of the super-sampled pixels are saved for the backward"""
+
+    @staticmethod
+    def forward(ctx, v_world, light2, cam, faces2, vf_ptr, vf_ent, textures, S, width, eps):
+        N, V = v_world.shape[:2]
+        F2 = faces2.shape[0]
+        Ft, ts = textures.shape[:2]
+        dev = v_world.device
+        vw, lt = v_world.detach().float().contiguous(), light2.detach().float().contiguous()
+        ndc = torch.empty(N, V, 3, device=dev, dtype=torch.float32)
+        image = torch.empty(N, S, S, 3, device=dev, dtype=torch.float32)
+        unlit = torch.empty(N, 2 * S, 2 * S, 3, device=dev, dtype=torch.float32)
+        fidx = torch.empty(N, 2 * S, 2 * S, device=dev, dtype=torch.int32)
+        scratch = _scratch_for(dev, (N, F2, S), N * L.load().avc_rasterize_scratch_bytes(F2, 2 * S))
+        _checked("avc_rasterize_mesh_tex_save", vw, N, V, faces2, F2, cam, width, lt, textures, Ft, ts, TEXTURE_EPS, S, NEAR, FAR, ndc, image, unlit,
+                 fidx, scratch)
+        ctx.save_for_backward(vw, lt, cam, faces2, vf_ptr, vf_ent, ndc, fidx, unlit)
+        ctx.S, ctx.width, ctx.eps = S, width, eps
+        ctx.mark_non_differentiable(ndc, fidx, unlit)
+        return image, ndc, fidx, unlit
+
+    @staticmethod
+    def backward(ctx, g_image, _g_ndc, _g_fidx, _g_unlit):
+        vw, lt, cam, faces2, vf_ptr, vf_ent, ndc, fidx, unlit = ctx.saved_tensors
+        N, V = vw.shape[:2]
+        F2 = faces2.shape[0]
+        g = g_image.float().contiguous()
+        face_grad = torch.empty(N, F2, 6, device=vw.device, dtype=torch.float32)
+        grad_ndc = torch.empty(N, V, 3, device=vw.device, dtype=torch.float32)
+        grad_light = torch.empty(N, F2, device=vw.device, dtype=torch.float32)
+        L.call("avc_rasterize_mesh_tex_grad", g, ndc, N, V, faces2, F2, lt, unlit, fidx, ctx.S, ctx.eps, vf_ptr, vf_ent, face_grad, grad_ndc, grad_light)
+        gv = project_vjp(vw, cam, ctx.width, grad_ndc) if ctx.needs_input_grad[0] else None
+        return gv, grad_light, None, None, None, None, None, None, None, None
+
+
+TEXTURE_EPS = 1e-4          # the sampling clamp ts - 1 - eps (neural_renderer's rasteriser default)
+
+
+def check_textures(textures, n_faces):
+    """the refusals of render_rgb_batch, before any launch: cubes [F,ts,ts,ts,3] for exactly the mesh's faces, ts >= 2, constants"""
+    if not torch.is_tensor(textures) or textures.dim() != 5 or textures.shape[-1] != 3 or len(set(textures.shape[1:4])) != 1:
+        raise ValueError("textures are cubes [F,ts,ts,ts,3], got %s" % (list(textures.shape) if torch.is_tensor(textures) else type(textures).__name__))
+    if textures.shape[0] != n_faces:
+        raise ValueError("textures hold the cubes of %d faces, the mesh has %d faces" % (textures.shape[0], n_faces))
+    if textures.shape[1] < 2:
+        raise ValueError("texture_size = %d; a texture cube needs at least 2 texels per axis (texel i is blended with i + 1)" % textures.shape[1])
+    if textures.requires_grad:
+        raise ValueError("the texture cubes are constants of the render: a gradient to them is not implemented, pass textures.detach()")
+
+
+def render_rgb_batch(v_world, faces, textures, eyes, directions, image_size=256, eps=DEFAULT_EPS, return_state=False):
+    """render_grey_batch of the textured body: textures [F,ts,ts,ts,3] float32 on the device (texture.load_obj_texture's cubes; constants) ->
+    RGB images [N,3,S,S] with autograd to v_world.  return_state: also (ndc [N,V,3], face index [N,2S,2S] y up, unlit colours [N,2S,2S,3] y up)."""
+    dev = v_world.device
+    n_faces = len(faces)
+    check_textures(textures, n_faces)
+    if dev.type != "cuda" or textures.device != dev:
+        raise RuntimeError("render_rgb_batch rasterises on the MI355X (no CPU fallback): vertices on %s, textures on %s" % (dev, textures.device))
+    B, V = v_world.shape[:2]
+    N = len(eyes)
+    if B == 0 or N % B or len(directions) != N:
+        raise ValueError("k cameras per vertex set: %d vertex sets, %d eyes, %d directions" % (B, N, len(directions)))
+    faces2, f, vf_ptr, vf_ent = _topology(faces, V, dev)
+    v = v_world.float() @ torch.tensor(ROT_MAT, dtype=torch.float32, device=dev)
+    light2 = torch.stack([face_light(v[i], f) for i in range(B)])
+    if N != B:
+        v, light2 = v.repeat(N // B, 1, 1), light2.repeat(N // B, 1)
+    cam = h2d.upload(np.stack([camera_frame(e, d) for e, d in zip(eyes, directions)]).reshape(-1), dev).reshape(N, 12)
+    width = float(np.tan(np.deg2rad(VIEWING_ANGLE)))
+    image, ndc, fidx, unlit = _RasterTexFn.apply(v, light2, cam, faces2, vf_ptr, vf_ent, textures.float().contiguous(), int(image_size), width, float(eps))
+    image = image.permute(0, 3, 1, 2)
+    return (image, ndc, fidx, unlit) if return_state else image

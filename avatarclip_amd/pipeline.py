@@ -93,6 +93,7 @@ class PipelineSpec:
     codebook: Optional[str] = None
     realnvp: Optional[str] = None
     motion_vae: Optional[str] = None
+    smpl_uv: Optional[str] = None            # the textured body (.obj + .mtl + image) the scoring renders of shape and motion show; None: white
     # ---- knobs of the stage functions
     pose_type: str = "stand_pose"
     image_size: int = 256
@@ -227,6 +228,26 @@ def required_assets(spec, stage):
     return []
 
 
+def texture_fingerprint(path):
+    """what --smpl_uv adds to the settings of the stages that render the body: nothing when it is not given (the fingerprints of runs
+    without a texture do not move), else the digest of the loaded cubes -- which covers the .obj, its .mtl and the image"""
+    if path is None:
+        return {}
+    from .texture import load_obj_texture
+    return {"smpl_uv": _digest_object(load_obj_texture(path)[2])}
+
+
+def check_texture(path):
+    """the pre-flight of --smpl_uv: the .obj, its .mtl and its image load"""
+    if path is None:
+        return
+    from .texture import load_obj_texture
+    try:
+        load_obj_texture(path)
+    except (ValueError, OSError) as e:
+        raise SystemExit("--smpl_uv = %s cannot be loaded: %s" % (path, e))
+
+
 _CONF_OF = {"init": ("init",), "appearance": ("appearance",), "mesh": ("appearance",), "motion": ("animate",)}
 
 
@@ -255,6 +276,11 @@ def check(spec, manifest=None):
         problems.append("--pose_type is stand_pose or t_pose, got %r" % (spec.pose_type,))
     if spec.posing not in ("torch", "hip"):
         problems.append("--posing is torch or hip, got %r" % (spec.posing,))
+    if spec.smpl_uv is not None and any(st in sel for st in ("shape", "motion")):
+        try:
+            check_texture(spec.smpl_uv)
+        except SystemExit as e:
+            problems.append(str(e))
     confs_ok = {}
     for which in sorted({w for st in sel for w in _CONF_OF.get(st, ())}):
         c = getattr(spec, which + "_conf")
@@ -354,8 +380,8 @@ def stage_settings(spec, stage):
     """what `stage` reads besides files: prompts, knobs, the effective conf text"""
     s = spec
     if stage == "shape":
-        return {"neutral_txt": s.neutral_txt, "target_txt": s.target_txt, "latent_dim": SHAPE_LATENT_DIM,
-                "text_embeddings": _hook_digests(s, ("neutral_txt", "target_txt"))}
+        return dict({"neutral_txt": s.neutral_txt, "target_txt": s.target_txt, "latent_dim": SHAPE_LATENT_DIM,
+                     "text_embeddings": _hook_digests(s, ("neutral_txt", "target_txt"))}, **texture_fingerprint(s.smpl_uv))
     if stage == "dataset":
         return {"pose_type": s.pose_type, "image_size": int(s.image_size)}
     if stage == "init":
@@ -371,6 +397,7 @@ def stage_settings(spec, stage):
             out["text_feature"] = _digest_object(s.text_feature(conf.get_string("general.text")))
         if s.vposer is not None and not isinstance(s.vposer, (str, os.PathLike)):
             out["vposer"] = _digest_object(s.vposer)
+        out.update(texture_fingerprint(s.smpl_uv))
         return out
     if stage == "drive":
         return {"name": s.name}
@@ -544,7 +571,8 @@ def stage_shape(run):
     tower = run.tower(retrieval=True)
     nembed = run.text_embedding("neutral_txt", SG.parse_prompt(s.neutral_txt)[0], tower)
     tembed = run.text_embedding("target_txt", SG.parse_prompt(s.target_txt)[0], tower)
-    v, _, best, cos = SG.shape_gen(model_AE, faces, tower, codebook, clip_codebook, nembed, tembed)
+    render_fn = SG.textured_render_fn(faces, s.smpl_uv, dev) if s.smpl_uv is not None else None
+    v, _, best, cos = SG.shape_gen(model_AE, faces, tower, codebook, clip_codebook, nembed, tembed, render_fn=render_fn)
     obj, doc = os.path.join(run.dir("shape"), "coarse_shape.obj"), os.path.join(run.dir("shape"), "shape.json")
     SG.writeOBJ(obj, v, faces)
     cos = [float(c) for c in cos.reshape(-1).cpu()]
@@ -607,7 +635,7 @@ def stage_motion(run):
     pose, motion = _generator_types(conf)
     image, main_text, retrieval = _animate_needs(s, conf)
     smpl, vp = smpl_lbs.load_smpl_arrays(s.smpl, dev), run.vposer()
-    kw = dict(device=dev, renderer_gradient=bool(s.renderer_gradient), posing=s.posing)
+    kw = dict(device=dev, renderer_gradient=bool(s.renderer_gradient), posing=s.posing, texture=s.smpl_uv)
     feature_of = lambda tower: s.text_feature if s.text_feature is not None else (lambda text: run.encode_text(tower, text)[0])
     main = run.tower() if image or main_text else None
     ctx = A.AnimateContext(main, feature_of(main), smpl, vp, **kw)

@@ -11,7 +11,9 @@ text - neutral text" (main.py:93-123), decode that code into a mesh and write it
 Inputs the reference downloads or ships outside the repository (the VAE / codebook blobs of ShapeGen/data, the SMPL template, the CLIP
 weights + merge table) are arguments here.  The body render that is embedded uses the HIP rasteriser with neural_renderer's lighting
 of a white body (`smpl_prior.MeshPrior`), camera distance 2, elevation 0, azimuth 150 degrees (utils.py:10-27); the reference textures
-the body with `data/smpl_uv.obj` first, which is not part of the repository either -- `render_fn` takes any replacement."""
+the body with `data/smpl_uv.obj` first, which is not part of the repository either: `--smpl_uv PATH` renders that textured body
+(texture.load_obj_texture + mesh_render.render_rgb_batch), and `render_fn` takes any other replacement.  The shipped shape codebook holds
+embeddings of textured renders: it matches this stage only with the texture it was made with."""
 import argparse
 import os
 
@@ -101,6 +103,23 @@ def render_body(vertices, faces, device="cuda", image_size=256, camera_distance=
     return torch.stack(imgs)
 
 
+def textured_render_fn(faces, smpl_uv, device="cuda", image_size=256, camera_distance=2.0, elevation=0.0, angles=(150,)):
+    """shape_gen's `render_fn` for --smpl_uv: render_body's cameras on the textured body (utils.py:6-28: nr.load_obj(data/smpl_uv.obj,
+    load_texture=True, texture_size=8) -> nr.Renderer) -> [len(angles), 3, S, S].  The .obj is loaded once; its faces must be the mesh's."""
+    from .mesh_render import ROT_MAT, render_rgb_batch
+    from .texture import as_cubes
+    cubes = as_cubes(smpl_uv, device)
+    eyes = [get_points_from_angles(camera_distance, elevation, a).astype(np.float32) for a in angles]
+    dirs = [(-e / np.linalg.norm(e)).astype(np.float32) for e in eyes]
+    unrot = torch.tensor(ROT_MAT, dtype=torch.float32, device=device).t()      # render_body applies no rot_mat (apply_rot_mat=False); ROT_MAT is orthogonal
+
+    @torch.no_grad()
+    def render_fn(vertices):
+        v = torch.as_tensor(np.asarray(vertices, np.float32), device=device) @ unrot
+        return render_rgb_batch(v[None], faces, cubes, eyes, dirs, image_size=image_size)
+    return render_fn
+
+
 def writeOBJ(file, V, F):
     """utils.py:35-57 (vertices + 1-based triangle indices)"""
     with open(file, 'w') as fh:
@@ -137,6 +156,9 @@ def main(argv=None):
     ap.add_argument('--neutral_txt', type=str, default='a 3d rendering of a person in unreal engine')
     ap.add_argument('--target_txt', type=str, default='a 3d rendering of a strong man in unreal engine')
     ap.add_argument('--output_folder', type=str, default='./output/coarse_shape')
+    ap.add_argument('--smpl_uv', type=str, default=None,
+                    help="the textured body (data/smpl_uv.obj with its .mtl and image): the scoring render shows it instead of a white body, as "
+                         "ShapeGen/utils.py:6-28 does; the codebook matches only if it was made with the same texture")
     args = ap.parse_args(argv)
     if not args.clip_weights or not args.clip_bpe:
         raise SystemExit("the CLIP ViT-B/32 checkpoint and its BPE merge table are inputs (--clip_weights / --clip_bpe)")
@@ -150,7 +172,8 @@ def main(argv=None):
     nembed = perceptor.encode_text(tokenizer.tokenize([ntxt], tok).to(dev)).float()
     tembed = perceptor.encode_text(tokenizer.tokenize([ttxt], tok).to(dev)).float()
     print("Start generating coarse body shape given the target text: {}".format(args.target_txt))
-    v, _, best, _ = shape_gen(model_AE, faces, perceptor, codebook, clip_codebook, nembed, tembed)
+    render_fn = textured_render_fn(faces, args.smpl_uv, dev) if args.smpl_uv is not None else None
+    v, _, best, _ = shape_gen(model_AE, faces, perceptor, codebook, clip_codebook, nembed, tembed, render_fn=render_fn)
     os.makedirs(args.output_folder, exist_ok=True)
     output_fname = os.path.join(args.output_folder, '_'.join(args.target_txt.split(' ')) + '.obj')
     writeOBJ(output_fname, v, faces)

@@ -12,6 +12,7 @@ Every section RUNS THE THIRD-PARTY CODE ITSELF -- never this repo's restatement 
   f-1   SMPL body model via smplx (main.py:290-335)                          --smpl + the `smplx` package        third_party_smpl.npz
   f-1   neural_renderer silhouette prior (models/utils.py:108-125)           --neural-renderer (package, CUDA)   third_party_nr.npz
   f-2   PyMCubes marching cubes (models/renderer.py:31)                      --pymcubes (package `mcubes`)       third_party_mcubes.npz
+  f-4   neural_renderer's texture path (models/render.py:6-35)               --neural-renderer, as f-1           third_party_nr_texture.npz
 
 tests/test_third_party_pins.py consumes the files: absent -> the tests skip (today's state, the rows stay "unpinned"); present -> the CPU
 oracles (oracle/clip_vit_oracle.py, clip_text_oracle.py, lbs_oracle.py, nr_oracle.py, mcubes_oracle.py) and, under -m gpu, the HIP kernels are
@@ -176,8 +177,46 @@ def pin_neural_renderer(out_dir, stand_in=False):
             img, _, _ = renderer(torch.matmul(v.clone(), rot), faces, textures)
             images.append(img.detach().cpu().numpy().transpose(0, 2, 3, 1).squeeze(0)[:, ::-1].copy())
         source = "neural_renderer"
+        pin_neural_renderer_texture(nr, out_dir)
     path = os.path.join(out_dir, "third_party_nr.npz")
     np.savez_compressed(path, source=np.array(source), cameras=np.array(NR_CAMERAS, np.float32), images=np.stack(images).astype(np.float32))
+    return path
+
+
+def pin_neural_renderer_texture(nr, out_dir, S=32):
+    """The texture path of neural_renderer itself ("Textured body renders"), only where the package can be imported:
+    nr.load_obj(load_texture=True, texture_size=8) on the .obj / .mtl / image fixture of tests/test_texture_cpu.py, and nr.Renderer's RGB
+    forward and backward on the hand-made mesh, cameras and cubes of tests/test_gpu_raster_tex.py -> third_party_nr_texture.npz, which that
+    test compares mesh_render.render_rgb_batch against (until it exists the test reports "unpinned")."""
+    import tempfile
+    from tests import test_gpu_raster_tex as G
+    from tests import test_texture_cpu as C
+    with tempfile.TemporaryDirectory() as d:
+        obj = C._fixture(d)
+        lv, lf, lt = nr.load_obj(obj, load_texture=True, texture_size=8)
+    mesh_v, mesh_f = G.mesh()
+    cubes = G.inputs(8)[4]
+    eyes = np.stack([e for e, _ in G.CAMS]).astype(np.float32)
+    dirs = np.stack([(a - e) / np.linalg.norm(a - e) for e, a in G.CAMS]).astype(np.float32)
+    rot = torch.tensor([[1., 0., 0.], [0., 0., -1.], [0., 1., 0.]]).cuda()
+    faces = torch.from_numpy(mesh_f.astype(np.int32)).cuda().unsqueeze(0)
+    textures = torch.from_numpy(cubes.copy()).cuda().unsqueeze(0)
+    grad = torch.randn(len(eyes), 3, S, S, generator=torch.Generator().manual_seed(0))
+    images, grads = [], []
+    for i in range(len(eyes)):
+        v = torch.from_numpy(mesh_v).cuda().unsqueeze(0).requires_grad_(True)
+        renderer = nr.Renderer(camera_mode="look", image_size=S).cuda()
+        renderer.eye = torch.from_numpy(eyes[i]).cuda()
+        renderer.camera_direction = torch.from_numpy(dirs[i]).cuda()
+        img, _, _ = renderer(torch.matmul(v, rot), faces, textures)
+        img.backward(grad[i:i + 1].cuda())
+        images.append(img.detach().cpu().numpy()[0])
+        grads.append(v.grad.cpu().numpy()[0])
+    path = os.path.join(out_dir, "third_party_nr_texture.npz")
+    np.savez_compressed(path, source=np.array("neural_renderer"), loader_vertices=lv.cpu().numpy(), loader_faces=lf.cpu().numpy(),
+                        loader_textures=lt.cpu().numpy(), vertices=np.tile(mesh_v, (len(eyes), 1, 1)), faces=mesh_f, textures=cubes, eyes=eyes,
+                        directions=dirs, image_size=np.array(S), images=np.stack(images).astype(np.float32), grad_images=grad.numpy(),
+                        grad_vertices=np.stack(grads).astype(np.float32))
     return path
 
 
