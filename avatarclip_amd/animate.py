@@ -1,7 +1,7 @@
 """AvatarAnimate's candidate-pose and motion generators (reference: AvatarAnimate/models/pose_generation.py,
-motion_generation.py, builder.py, main.py) on this repository's kernels: every render goes through the HIP rasteriser (`smpl_prior.MeshPrior`,
-camera_mode 'look_at'), every CLIP embedding through the HIP ViT / text towers (`clip_vit.ClipVisionB32`, batched scoring path), SMPL posing
-through `smpl_lbs`.  The reference's third-party blobs are INPUTS, not part of the tree: the VPoser body prior (`human_body_prior`), the pose
+motion_generation.py, builder.py, main.py) on this repository's kernels: every render goes through the HIP rasteriser (`mesh_render.render_batch`:
+one batched call for the white body and the textured one alike, camera_mode 'look_at'), every CLIP embedding through the HIP ViT / text towers
+(`clip_vit.ClipVisionB32`, batched scoring path), SMPL posing through `smpl_lbs`.  The reference's third-party blobs are INPUTS, not part of the tree: the VPoser body prior (`human_body_prior`), the pose
 codebook / conditional RealNVP / motion-VAE checkpoints, the SMPL model, the UV texture.  `AnimateContext` takes them as objects / state dicts with
 the reference's names, so the reference's files load unmodified where somebody holds them; the tests drive everything with seeded stand-ins and pin
 the arithmetic to the reference's OWN classes and methods (`oracle/gen_golden_animate.py` extracts them with `ast`).
@@ -166,18 +166,17 @@ class AnimateContext:
     def _render_hip_grad(self, vertices, faces, angles):
         """models/render.py:10-39 on the HIP rasteriser: camera_mode 'look_at' at distance 2, azimuth = the angle, elevation drawn per angle
         from numpy's global generator (np.random.randn() * 0.3 degrees: the reference's draw, in its order).  White body under
-        neural_renderer's light, or (AnimateContext(texture=...)) the textured body through mesh_render.render_rgb_batch.  The len(angles) x bs renders camera-major in one
-        call of mesh_render.render_grey_batch (one batched forward-with-save, neural_renderer's approximate backward to the vertices)."""
-        from .mesh_render import render_grey_batch, render_rgb_batch
+        neural_renderer's light, or (AnimateContext(texture=...); models/render.py:6-35) the cubes of data/smpl_uv.obj on the same cameras.
+        The len(angles) x bs renders camera-major in one call of mesh_render.render_batch (one batched forward-with-save, neural_renderer's
+        approximate backward to the vertices) -> [len(angles) * bs, 3, S, S] either way."""
+        from .mesh_render import render_batch
         from .shapegen_render import get_points_from_angles
         eyes = [get_points_from_angles(CAMERA_DISTANCE, np.random.randn() * 0.3, a) for a in angles]     # draw order: once per angle, before the batch loop
         bs = vertices.shape[0]
         eye_all = [e.astype(np.float32) for e in eyes for _ in range(bs)]
         dir_all = [(-e / np.linalg.norm(e)).astype(np.float32) for e in eyes for _ in range(bs)]
-        if getattr(self, "texture", None) is not None:           # models/render.py:6-35: the cubes of data/smpl_uv.obj on the same cameras
-            return render_rgb_batch(vertices, faces, self.texture, eye_all, dir_all, image_size=self.image_size)
-        g = render_grey_batch(vertices, faces, eye_all, dir_all, image_size=self.image_size)
-        return g.unsqueeze(1).expand(-1, 3, -1, -1)
+        texture = getattr(self, "texture", None)                 # tests/test_gpu_raster_grad.py calls this unbound, on a namespace with image_size alone
+        return render_batch(vertices, faces, eye_all, dir_all, texture, image_size=self.image_size)
 
     def release_graphs(self):
         """Runner.train_clip_iteration's call at the top of every generator iteration: a graph-replayed encode_image that never reached backward

@@ -10,10 +10,11 @@ text - neutral text" (main.py:93-123), decode that code into a mesh and write it
 
 Inputs the reference downloads or ships outside the repository (the VAE / codebook blobs of ShapeGen/data, the SMPL template, the CLIP
 weights + merge table) are arguments here.  The body render that is embedded uses the HIP rasteriser with neural_renderer's lighting
-of a white body (`smpl_prior.MeshPrior`), camera distance 2, elevation 0, azimuth 150 degrees (utils.py:10-27); the reference textures
-the body with `data/smpl_uv.obj` first, which is not part of the repository either: `--smpl_uv PATH` renders that textured body
-(texture.load_obj_texture + mesh_render.render_rgb_batch), and `render_fn` takes any other replacement.  The shipped shape codebook holds
-embeddings of textured renders: it matches this stage only with the texture it was made with."""
+of a white body (`mesh_render.render_grey_batch`), camera distance 2, elevation 0, azimuth 150 degrees (utils.py:10-27); the reference
+textures the body with `data/smpl_uv.obj` first, which is not part of the repository either: `--smpl_uv PATH` renders that textured body
+(texture.load_obj_texture + mesh_render.render_rgb_batch), and `render_fn` takes any other replacement.  Both take the batched path with
+`apply_rot_mat=False`: ShapeGen's bodies stand in the renderer's frame.  The shipped shape codebook holds embeddings of textured renders: it
+matches this stage only with the texture it was made with."""
 import argparse
 import os
 
@@ -90,33 +91,34 @@ def load_codebook(fname, device="cuda"):
     raise ValueError("empty codebook file %s" % fname)
 
 
+def look_at_cameras(camera_distance, elevation, angles, dtype=np.float64):
+    """camera_mode 'look_at' the origin, one camera per azimuth -> (eyes rounded to dtype, the viewing directions derived from those)"""
+    eyes = [get_points_from_angles(camera_distance, elevation, a).astype(dtype) for a in angles]
+    return eyes, [-e / np.linalg.norm(e) for e in eyes]
+
+
+@torch.no_grad()
 def render_body(vertices, faces, device="cuda", image_size=256, camera_distance=2.0, elevation=0.0, angles=(150,)):
     """utils.py:10-27 `render_one_batch` on the HIP rasteriser: [len(angles), 3, S, S] in [0, 1] (white body, neural_renderer's
-    default light, camera_mode 'look_at' the origin)"""
-    from .smpl_prior import MeshPrior
-    prior = MeshPrior(np.asarray(vertices, np.float32), faces, device=device, image_size=image_size, apply_rot_mat=False)
-    imgs = []
-    for a in angles:
-        eye = get_points_from_angles(camera_distance, elevation, a)
-        grey = prior.render_grey(eye, -eye / np.linalg.norm(eye))
-        imgs.append(grey[None].repeat(3, 1, 1))
-    return torch.stack(imgs)
+    default light, camera_mode 'look_at' the origin; no rot_mat: the body stands in the renderer's frame)"""
+    from .mesh_render import render_batch
+    eyes, dirs = look_at_cameras(camera_distance, elevation, angles)
+    v = torch.as_tensor(np.asarray(vertices, np.float32), device=device).reshape(1, -1, 3)
+    return render_batch(v, faces, eyes, dirs, image_size=image_size, apply_rot_mat=False)
 
 
 def textured_render_fn(faces, smpl_uv, device="cuda", image_size=256, camera_distance=2.0, elevation=0.0, angles=(150,)):
     """shape_gen's `render_fn` for --smpl_uv: render_body's cameras on the textured body (utils.py:6-28: nr.load_obj(data/smpl_uv.obj,
     load_texture=True, texture_size=8) -> nr.Renderer) -> [len(angles), 3, S, S].  The .obj is loaded once; its faces must be the mesh's."""
-    from .mesh_render import ROT_MAT, render_rgb_batch
+    from .mesh_render import render_rgb_batch
     from .texture import as_cubes
     cubes = as_cubes(smpl_uv, device)
-    eyes = [get_points_from_angles(camera_distance, elevation, a).astype(np.float32) for a in angles]
-    dirs = [(-e / np.linalg.norm(e)).astype(np.float32) for e in eyes]
-    unrot = torch.tensor(ROT_MAT, dtype=torch.float32, device=device).t()      # render_body applies no rot_mat (apply_rot_mat=False); ROT_MAT is orthogonal
+    eyes, dirs = look_at_cameras(camera_distance, elevation, angles, np.float32)      # float32 eyes: the rounding these renders have always had
 
     @torch.no_grad()
     def render_fn(vertices):
-        v = torch.as_tensor(np.asarray(vertices, np.float32), device=device) @ unrot
-        return render_rgb_batch(v[None], faces, cubes, eyes, dirs, image_size=image_size)
+        v = torch.as_tensor(np.asarray(vertices, np.float32), device=device)[None]
+        return render_rgb_batch(v, faces, cubes, eyes, dirs, image_size=image_size, apply_rot_mat=False)
     return render_fn
 
 

@@ -7,6 +7,9 @@ DESIGN.md section 8 operation by operation (csrc/avc_raster_grad.hip is tested a
   crossing w_x, w_in = floor / ceil(w_x), w_out = w_in + dir; out run (if I(w_in) = f) from w_out to the border, Delta = (c(w) - c(w_in)) G(w);
   in run from w_in to the opposite side (pixels of f), Delta = (c(w) - c(w_out)) G(w); where Delta > 0 the w-components of a and b get
   -= Delta / d, d = the displacement that moves the edge through pixel w (in NDC, pushed away from zero by eps).
+
+The walk is written once (`walk`), with Delta as a hook: `pseudo_grad` is the walk with the grey term above, tests/nr_texture_restatement.py
+hands it the three-channel term of the textured body.  tests/golden/nr_walk.npz pins its sums (tests/test_texture_cpu.py).
 """
 import numpy as np
 
@@ -25,6 +28,24 @@ def is_back(tri):
     return (y2 - y0) * (x1 - x0) < (y1 - y0) * (x2 - x0)
 
 
+def signed_area(p):
+    """twice the signed area of a face's pixel coordinates p [3,2]: the denominator of its barycentrics"""
+    return p[2, 0] * (p[0, 1] - p[1, 1]) + p[0, 0] * (p[1, 1] - p[2, 1]) + p[1, 0] * (p[2, 1] - p[0, 1])
+
+
+def face_weights(p, zs, xi, yi):
+    """face_weights of csrc/avc_raster.h at pixels (xi, yi) (float32, any broadcastable shapes) for a face's pixel coordinates p [3,2] and
+    vertex depths zs [3]: the clamped barycentrics [3,...], their sum (>= 1e-10) and the depth zp"""
+    den = signed_area(p)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        w0 = np.clip(((p[1, 1] - p[2, 1]) * xi + (p[2, 0] - p[1, 0]) * yi + (p[1, 0] * p[2, 1] - p[2, 0] * p[1, 1])) / den, 0, 1)
+        w1 = np.clip(((p[2, 1] - p[0, 1]) * xi + (p[0, 0] - p[2, 0]) * yi + (p[2, 0] * p[0, 1] - p[0, 0] * p[2, 1])) / den, 0, 1)
+        w2 = np.clip(((p[0, 1] - p[1, 1]) * xi + (p[1, 0] - p[0, 0]) * yi + (p[0, 0] * p[1, 1] - p[1, 0] * p[0, 1])) / den, 0, 1)
+        ws = np.maximum(w0 + w1 + w2, f32(1e-10))
+        zp = f32(1) / ((w0 / zs[0] + w1 / zs[1] + w2 / zs[2]) / ws)
+    return np.stack([w0, w1, w2]).astype(f32), ws.astype(f32), zp.astype(f32)
+
+
 def rasterize_index(ndc, faces, n, near=0.1, far=100.0):
     """the forward rasteriser (oracle/nr_oracle.rasterize) returning the face-index map [n, n], y up, -1 = background"""
     nd = np.asarray(ndc, f32)
@@ -38,8 +59,7 @@ def rasterize_index(ndc, faces, n, near=0.1, far=100.0):
             continue
         xs, ys, zs = t[:, 0], t[:, 1], t[:, 2]
         p = f32(0.5) * (t[:, :2] * nf + nf - f32(1))
-        den = p[2, 0] * (p[0, 1] - p[1, 1]) + p[0, 0] * (p[1, 1] - p[2, 1]) + p[1, 0] * (p[2, 1] - p[0, 1])
-        if den == 0 or not np.isfinite(p).all():
+        if signed_area(p) == 0 or not np.isfinite(p).all():
             continue
         lo_x = max(int(np.floor(p[:, 0].min())) - 1, 0); hi_x = min(int(np.ceil(p[:, 0].max())) + 1, n - 1)
         lo_y = max(int(np.floor(p[:, 1].min())) - 1, 0); hi_y = min(int(np.ceil(p[:, 1].max())) + 1, n - 1)
@@ -52,12 +72,7 @@ def rasterize_index(ndc, faces, n, near=0.1, far=100.0):
         out = ((yp - ys[0]) * (xs[1] - xs[0]) < (xp - xs[0]) * (ys[1] - ys[0])) | \
               ((yp - ys[1]) * (xs[2] - xs[1]) < (xp - xs[1]) * (ys[2] - ys[1])) | \
               ((yp - ys[2]) * (xs[0] - xs[2]) < (xp - xs[2]) * (ys[0] - ys[2]))
-        w0 = np.clip(((p[1, 1] - p[2, 1]) * xi + (p[2, 0] - p[1, 0]) * yi + (p[1, 0] * p[2, 1] - p[2, 0] * p[1, 1])) / den, 0, 1)
-        w1 = np.clip(((p[2, 1] - p[0, 1]) * xi + (p[0, 0] - p[2, 0]) * yi + (p[2, 0] * p[0, 1] - p[0, 0] * p[2, 1])) / den, 0, 1)
-        w2 = np.clip(((p[0, 1] - p[1, 1]) * xi + (p[1, 0] - p[0, 0]) * yi + (p[0, 0] * p[1, 1] - p[1, 0] * p[0, 1])) / den, 0, 1)
-        ws = np.maximum(w0 + w1 + w2, f32(1e-10))
-        with np.errstate(divide="ignore"):
-            zp = f32(1) / ((w0 / zs[0] + w1 / zs[1] + w2 / zs[2]) / ws)
+        _, _, zp = face_weights(p, zs, xi, yi)
         ok = (~out) & (zp > near) & (zp < far)
         sz = zbuf[lo_y:hi_y + 1, lo_x:hi_x + 1]
         si = fidx[lo_y:hi_y + 1, lo_x:hi_x + 1]
@@ -91,18 +106,16 @@ def _expand(starts, lengths):
     return rep, k
 
 
-def pseudo_grad(ndc, faces, light, fidx, G, eps=1e-4, count=None, abs_sum=None):
-    """the rules on a super-sampled pixel gradient G [n, n] (y up) -> grad_ndc [V, 3] (float64 sums of float32 terms; z = 0).
+def walk(ndc, faces, fidx, delta_fn, eps=1e-4, count=None, abs_sum=None):
+    """the rules' scan-line walk with the colour term as a hook: delta_fn((rows, cols) of the run's pixels, (rows, cols) of their reference
+    pixel: w_in for an out run, w_out for an in run) -> Delta float32.  -> grad_ndc [V, 3] (float64 sums of float32 terms; z = 0).
     count: optional dict, gets 'out' and 'in' = the number of run pixels visited.  abs_sum: optional float64 array [V, 3], gets the sum of
     |term| over the terms of every vertex component (a scale for the rounding of any order of summation)."""
     nd = np.asarray(ndc, f32)
     faces = np.asarray(faces)
-    lt = np.asarray(light, f32)
     fidx = np.asarray(fidx)
-    G = np.asarray(G, f32)
     n = fidx.shape[0]
     nf, eps = f32(n), f32(eps)
-    c_map = np.where(fidx >= 0, lt[np.maximum(fidx, 0)], f32(0))
     P = pixel_coords(nd, n)
     grad = np.zeros((nd.shape[0], 3), np.float64)
     visits = {"out": 0, "in": 0}
@@ -157,8 +170,7 @@ def pseudo_grad(ndc, faces, light, fidx, G, eps=1e-4, count=None, abs_sum=None):
                     rr, k = _expand(sel, lens)
                     r = sel[rr]
                     w = i_out[r] + dir_ * k
-                    yx = at(u0[r], w)
-                    delta = (c_map[yx] - lt[f]) * G[yx]
+                    delta = delta_fn(at(u0[r], w), at(u0[r], i_in[r]))
                     visits["out"] += w.size
                     pos = delta > 0
                     if pos.any():
@@ -172,18 +184,29 @@ def pseudo_grad(ndc, faces, light, fidx, G, eps=1e-4, count=None, abs_sum=None):
                 r_hi = np.minimum(np.fmax(w_in, lim), f32(n - 1)).astype(np.int64)
                 rr, k = _expand(np.arange(u0.size), r_hi - r_lo + 1)
                 w = r_lo[rr] + k
-                yx = at(u0[rr], w)
                 visits["in"] += w.size
-                mine = fidx[yx] == f
+                mine = fidx[at(u0[rr], w)] == f
                 rr, w = rr[mine], w[mine]
-                yx = at(u0[rr], w)
-                delta = (lt[f] - c_map[at(u0[rr], i_out[rr])]) * G[yx]
+                delta = delta_fn(at(u0[rr], w), at(u0[rr], i_out[rr]))
                 pos = delta > 0
                 if pos.any():
                     update(rr[pos], w[pos], delta[pos])
     if count is not None:
         count.update(visits)
     return grad
+
+
+def grey_delta(fidx, light, G):
+    """the grey colour term as a hook for walk(): (c(w) - c(w_ref)) G(w), c = light[I] (0 on background)"""
+    lt = np.asarray(light, f32)
+    c_map = np.where(fidx >= 0, lt[np.maximum(fidx, 0)], f32(0))
+    return lambda px, ref: (c_map[px] - c_map[ref]) * G[px]
+
+
+def pseudo_grad(ndc, faces, light, fidx, G, eps=1e-4, count=None, abs_sum=None):
+    """the rules on a super-sampled pixel gradient G [n, n] (y up) -> grad_ndc [V, 3]: the walk with the grey colour term"""
+    fidx = np.asarray(fidx)
+    return walk(ndc, faces, fidx, grey_delta(fidx, light, np.asarray(G, f32)), eps, count, abs_sum)
 
 
 def light_grad(fidx, G, F):

@@ -5,8 +5,8 @@ not from the code under test: the loader here walks face by face and texel by te
 against neural_renderer itself.
 
 The winner of every pixel is an INPUT here (the face-index map): coverage and depth are the grey kernels' business, pinned by
-tests/test_gpu_raster_grad.py.  The backward's scan-line walk is tests/nr_grad_restatement.pseudo_grad's, with the colour term
-(c(w) - c(w_ref)) G(w) replaced by a hook; tests/test_texture_cpu.py checks that with the grey hook it returns pseudo_grad's sums bit for bit.
+tests/test_gpu_raster_grad.py.  The backward's scan-line walk is tests/nr_grad_restatement.walk, the one pseudo_grad runs with the grey
+colour term: this module holds only the three-channel hook (rgb_delta) and its maps.  The barycentrics are R.face_weights, the rasteriser's.
 """
 import os
 
@@ -108,19 +108,8 @@ def load_obj_texture(path, ts=8):
 
 # ------------------------------------------------------------------------------------------------------------------- the per-pixel sample
 def weights(tri, xs, ys, n):
-    """face_weights of csrc/avc_raster.h at pixels (xs, ys) of an n x n grid for a face's NDC vertices tri [3,3]: the clamped barycentrics
-    [3,P], their sum (>= 1e-10) and the depth zp"""
-    nf = f32(n)
-    p = f32(0.5) * (tri[:, :2] * nf + nf - f32(1))
-    den = p[2, 0] * (p[0, 1] - p[1, 1]) + p[0, 0] * (p[1, 1] - p[2, 1]) + p[1, 0] * (p[2, 1] - p[0, 1])
-    xi, yi = np.asarray(xs).astype(f32), np.asarray(ys).astype(f32)
-    w0 = np.clip(((p[1, 1] - p[2, 1]) * xi + (p[2, 0] - p[1, 0]) * yi + (p[1, 0] * p[2, 1] - p[2, 0] * p[1, 1])) / den, 0, 1)
-    w1 = np.clip(((p[2, 1] - p[0, 1]) * xi + (p[0, 0] - p[2, 0]) * yi + (p[2, 0] * p[0, 1] - p[0, 0] * p[2, 1])) / den, 0, 1)
-    w2 = np.clip(((p[0, 1] - p[1, 1]) * xi + (p[1, 0] - p[0, 0]) * yi + (p[0, 0] * p[1, 1] - p[1, 0] * p[0, 1])) / den, 0, 1)
-    ws = np.maximum(w0 + w1 + w2, f32(1e-10))
-    zs = tri[:, 2]
-    zp = f32(1) / ((w0 / zs[0] + w1 / zs[1] + w2 / zs[2]) / ws)
-    return np.stack([w0, w1, w2]).astype(f32), ws.astype(f32), zp.astype(f32)
+    """R.face_weights at the integer pixels (xs, ys) of an n x n grid for a face's NDC vertices tri [3,3]"""
+    return R.face_weights(R.pixel_coords(tri, n), tri[:, 2], np.asarray(xs).astype(f32), np.asarray(ys).astype(f32))
 
 
 def cube_of(textures, f):
@@ -178,96 +167,6 @@ def pooled_image(unlit, fidx, light):
 
 
 # --------------------------------------------------------------------------------------------------------------------------- the backward
-def walk(ndc, faces, fidx, delta_fn, eps=1e-4, abs_sum=None):
-    """tests/nr_grad_restatement.pseudo_grad's scan-line walk with the colour term as a hook: delta_fn((rows, cols) of the run's pixels,
-    (rows, cols) of their reference pixel) -> Delta float32.  -> grad_ndc [V,3] (float64 sums of float32 terms; z = 0)"""
-    nd = np.asarray(ndc, f32)
-    faces = np.asarray(faces)
-    fidx = np.asarray(fidx)
-    n = fidx.shape[0]
-    nf, eps = f32(n), f32(eps)
-    P = R.pixel_coords(nd, n)
-    grad = np.zeros((nd.shape[0], 3), np.float64)
-    for f, face in enumerate(faces):
-        if R.is_back(nd[face]):
-            continue
-        p = P[face]
-        if not np.isfinite(p).all():
-            continue
-        for e in range(3):
-            a, b, o = e, (e + 1) % 3, (e + 2) % 3
-            for axis in (0, 1):
-                ui, wi_ = (0, 1) if axis == 0 else (1, 0)
-                comp = 1 if axis == 0 else 0
-                ua, wa, ub, wb, uo, wo = p[a, ui], p[a, wi_], p[b, ui], p[b, wi_], p[o, ui], p[o, wi_]
-                dir_ = (-1 if ua < ub else 1) if axis == 0 else (1 if ua < ub else -1)
-                lo = max(np.ceil(min(ua, ub)), f32(0))
-                hi = min(max(ua, ub), f32(n - 1))
-                if not (lo <= n - 1) or not (hi > -1):
-                    continue
-                u0 = np.arange(int(lo), int(hi) + 1)
-                if u0.size == 0:
-                    continue
-                fu = u0.astype(f32)
-                with np.errstate(divide="ignore", invalid="ignore"):
-                    wx = (wb - wa) / (ub - ua) * (fu - ua) + wa
-                    w_in = np.floor(wx) if dir_ > 0 else np.ceil(wx)
-                    w_out = w_in + f32(dir_)
-                    ok = (w_in >= 0) & (w_in < nf) & (w_out >= 0) & (w_out < nf)
-                if not ok.any():
-                    continue
-                u0, fu, wx, w_in, w_out = u0[ok], fu[ok], wx[ok], w_in[ok], w_out[ok]
-                i_in, i_out = w_in.astype(np.int64), w_out.astype(np.int64)
-                at = (lambda u, w: (w, u)) if axis == 0 else (lambda u, w: (u, w))     # (row y, column x) of scan-line position w
-
-                def update(r, w, delta):
-                    dw = w.astype(f32) - wx[r]
-                    fr = fu[r]
-                    with np.errstate(divide="ignore", invalid="ignore"):
-                        for vert, m, d in ((a, ub != fr, (ub - ua) / (ub - fr) * dw * f32(2) / nf),
-                                           (b, ua != fr, (ub - ua) / (fr - ua) * dw * f32(2) / nf)):
-                            d = np.where(d > 0, d + eps, d - eps).astype(f32)
-                            term = (delta / d).astype(f32)
-                            grad[face[vert], comp] -= term[m].astype(np.float64).sum()
-                            if abs_sum is not None:
-                                abs_sum[face[vert], comp] += np.abs(term[m]).astype(np.float64).sum()
-
-                # out runs
-                sel = np.nonzero(fidx[at(u0, i_in)] == f)[0]
-                if sel.size:
-                    lens = (n - i_out[sel]) if dir_ > 0 else (i_out[sel] + 1)
-                    rr, k = R._expand(sel, lens)
-                    r = sel[rr]
-                    w = i_out[r] + dir_ * k
-                    delta = delta_fn(at(u0[r], w), at(u0[r], i_in[r]))
-                    pos = delta > 0
-                    if pos.any():
-                        update(r[pos], w[pos], delta[pos])
-                # in runs
-                with np.errstate(divide="ignore", invalid="ignore"):
-                    two = (fu - ua) * (fu - uo) < 0
-                    wx2 = np.where(two, (wo - wa) / (uo - ua) * (fu - ua) + wa, (wb - wo) / (ub - uo) * (fu - uo) + wo).astype(f32)
-                    lim = np.ceil(wx2) if dir_ > 0 else np.floor(wx2)
-                r_lo = np.maximum(np.fmin(w_in, lim), f32(0)).astype(np.int64)
-                r_hi = np.minimum(np.fmax(w_in, lim), f32(n - 1)).astype(np.int64)
-                rr, k = R._expand(np.arange(u0.size), r_hi - r_lo + 1)
-                w = r_lo[rr] + k
-                mine = fidx[at(u0[rr], w)] == f
-                rr, w = rr[mine], w[mine]
-                delta = delta_fn(at(u0[rr], w), at(u0[rr], i_out[rr]))
-                pos = delta > 0
-                if pos.any():
-                    update(rr[pos], w[pos], delta[pos])
-    return grad
-
-
-def grey_delta(fidx, light, G):
-    """the grey colour term as a hook for walk(): (c(w) - c(w_ref)) G(w), c = light[I] (0 on background)"""
-    lt = np.asarray(light, f32)
-    c_map = np.where(fidx >= 0, lt[np.maximum(fidx, 0)], f32(0))
-    return lambda px, ref: (c_map[px] - c_map[ref]) * G[px]
-
-
 def G_map3(grad_image):
     """G_c at the super-sampled pixels [n,n,3], y up, from grad_image [S,S,3]"""
     g = np.asarray(grad_image, f32)[::-1]
@@ -287,7 +186,7 @@ def backward(ndc, faces2, light, fidx, unlit, grad_image, eps=1e-4, abs_sum=None
     fidx = np.asarray(fidx)
     G = G_map3(grad_image)
     C = lit_map(np.asarray(unlit, f32), fidx, light)
-    gn = walk(ndc, faces2, fidx, rgb_delta(C, G), eps, abs_sum)
+    gn = R.walk(ndc, faces2, fidx, rgb_delta(C, G), eps, abs_sum=abs_sum)
     gu = G * np.asarray(unlit, f32)
     per_pixel = ((gu[..., 0] + gu[..., 1]) + gu[..., 2]).astype(np.float64)
     m = fidx >= 0

@@ -144,18 +144,36 @@ def test_restatement_fill_back_copy_samples_what_the_face_shows_from_the_other_s
     assert np.array_equal(T.cube_of(tex, 6)[1, 2, 3], tex[2, 3, 2, 1])
 
 
-def test_the_walk_with_the_grey_hook_is_pseudo_grad_bit_for_bit():
-    """tests/nr_texture_restatement.walk restates nr_grad_restatement.pseudo_grad's scan-line walk around a colour hook: same sums, same order"""
+def test_the_one_walk_returns_the_sums_recorded_before_the_two_were_merged():
+    """tests/golden/nr_walk.npz holds what pseudo_grad and nr_texture_restatement.backward returned while each had a scan-line walk of its own
+    and its own barycentrics (commit 57481df); R.walk with either hook and R.face_weights return the same bits.  The recipe, S = 16, for the
+    cases below of tests.test_gpu_raster_grad.synthetic_case: fidx = R.rasterize_index(ndc, F2, 2 S) (stored as int16), G = R.G_map(grads[0]),
+    `grad` = R.pseudo_grad(ndc, F2, light, fidx, G, abs_sum=`abs_sum`, count=c), `visits` = (c["out"], c["in"]).  For "borders" also: unlit =
+    RandomState(5).uniform(0, 1, (2 S, 2 S, 3)) and g3 = RandomState(6).randn(S, S, 3), both float32, (`tex_grad`, `tex_grad_light`) =
+    T.backward(ndc, F2, light, fidx, unlit, g3, abs_sum=`tex_abs_sum`); and (`weights`, `weights_sum`, `weights_zp`) = T.weights(ndc[F2[f]],
+    xs, ys, 2 S) at the pixels of the lowest face index f in fidx."""
     from tests.test_gpu_raster_grad import synthetic_case
+    gold = np.load(os.path.join(ROOT, "tests", "golden", "nr_walk.npz"))
+    S = 16
     for case in ("borders", "degenerate", "behind_camera"):
-        S = 16
         vw, ndc, faces, F2, light, zero, grads = synthetic_case(case, S)
         fidx = R.rasterize_index(ndc, F2, 2 * S)
-        G = R.G_map(grads[0])
-        a, b = np.zeros((len(ndc), 3)), np.zeros((len(ndc), 3))
-        want = R.pseudo_grad(ndc, F2, light, fidx, G, abs_sum=a)
-        got = T.walk(ndc, F2, fidx, T.grey_delta(fidx, light, G), abs_sum=b)
-        assert np.abs(want).max() > 0 and np.array_equal(got, want) and np.array_equal(a, b), case
+        assert np.array_equal(fidx, gold[case + "_fidx"]), case
+        a, c = np.zeros((len(ndc), 3)), {}
+        got = R.pseudo_grad(ndc, F2, light, fidx, R.G_map(grads[0]), abs_sum=a, count=c)
+        assert np.abs(gold[case + "_grad"]).max() > 0 and np.array_equal(got, gold[case + "_grad"]), case
+        assert np.array_equal(a, gold[case + "_abs_sum"]) and [c["out"], c["in"]] == gold[case + "_visits"].tolist(), case
+        if case == "borders":
+            unlit = np.random.RandomState(5).uniform(0, 1, (2 * S, 2 * S, 3)).astype(f32)
+            g3 = np.random.RandomState(6).randn(S, S, 3).astype(f32)
+            b = np.zeros((len(ndc), 3))
+            gn, gl = T.backward(ndc, F2, light, fidx, unlit, g3, abs_sum=b)
+            assert np.abs(gold["borders_tex_grad"]).max() > 0 and np.array_equal(gn, gold["borders_tex_grad"])
+            assert np.array_equal(gl, gold["borders_tex_grad_light"]) and np.array_equal(b, gold["borders_tex_abs_sum"])
+            f = int(np.unique(fidx[fidx >= 0])[0])
+            ys, xs = np.nonzero(fidx == f)
+            for got_w, name in zip(T.weights(ndc[F2[f]], xs, ys, 2 * S), ("weights", "weights_sum", "weights_zp")):
+                assert got_w.dtype == f32 and np.array_equal(got_w, gold["borders_" + name]), name
 
 
 def test_rgb_backward_of_an_all_ones_texture_is_the_grey_backward_of_the_channel_sum():
