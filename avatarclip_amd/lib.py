@@ -1,6 +1,6 @@
-"""ctypes binding of libavc.so.  include/avc.h declares the C ABI, csrc/avc_texture.h the textured-render entry points added beside it:
-load() parses both, merges their prototypes and derives every restype / argtypes from them, and call() checks each tensor against the
-element type the header gives its parameter.  No
+"""ctypes binding of libavc.so.  include/avc.h declares the C ABI, csrc/avc_texture.h the textured-render entry points and
+csrc/avc_codebook.h the k-means entry points added beside it: load() parses the tuple headers() returns, merges their prototypes and derives every
+restype / argtypes from them, and call() checks each tensor against the element type the header gives its parameter.  No
 fallback: if the library is missing, lacks a symbol the header declares, or a call fails, an exception is raised."""
 import collections
 import ctypes
@@ -16,6 +16,13 @@ _launches = {}           # name -> the launcher bind() made, one per launch entr
 ABI_VERSION = None       # AVC_ABI_VERSION of include/avc.h (set by load())
 HEADER = os.path.normpath(os.path.join(_build.CSRC, _build.ABI_HEADER))
 TEXTURE_HEADER = os.path.join(_build.CSRC, _build.TEXTURE_HEADER)     # more entry points of the same library and revision (it defines no AVC_ABI_VERSION)
+CODEBOOK_HEADER = os.path.join(_build.CSRC, _build.CODEBOOK_HEADER)   # the k-means entry points, likewise
+
+
+def headers():
+    """the tuple of headers load() parses, in this order (read when called); a name that two of them declare is refused"""
+    return (HEADER, TEXTURE_HEADER, CODEBOOK_HEADER)
+
 
 c_int, c_long, c_float, c_double, c_void_p, c_char_p = (ctypes.c_int, ctypes.c_long, ctypes.c_float, ctypes.c_double,
                                                         ctypes.c_void_p, ctypes.c_char_p)
@@ -143,7 +150,7 @@ def load():
         raise RuntimeError("libavc.so is not built (run `python -c 'import __graft_entry__ as g; g.build()'`); "
                            "there is no CPU fallback for the HIP hot path")
     protos, declared_in = {}, {}
-    for header in (HEADER, TEXTURE_HEADER):
+    for header in headers():
         with open(header) as f:
             more, abi = parse_header(f.read())
         if header == HEADER:
@@ -179,7 +186,7 @@ def call(name, *args, stream=None):
     try:
         launch = _launches[name]
     except KeyError:
-        raise AttributeError("include/avc.h and csrc/avc_texture.h declare no launch entry point %s" % name) from None
+        raise AttributeError("include/avc.h, csrc/avc_texture.h and csrc/avc_codebook.h declare no launch entry point %s" % name) from None
     launch(*args, stream=stream)
 
 

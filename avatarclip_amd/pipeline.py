@@ -23,6 +23,8 @@ Every stage is a call into the module that implements it; none of their arithmet
   * ONE CLIP tower (clip_vit.ClipVision) and ONE tokenizer, built on first use and handed to shape_gen, Runner.init_clip and
     AnimateContext.  The shipped codebooks hold ViT-B/32 embeddings (README, "ViT-B/32 or ViT-B/16"): with a ViT-B/16 main
     checkpoint give the ViT-B/32 one as `retrieval_clip_weights`; it then serves `shape` and a VPoserCodebook pose generator.
+    A codebook written by `avatarclip_amd.codebook` carries a sidecar `<file>.json`: when it names the main tower's variant the
+    warning about a ViT-B/16 tower is not raised, and one naming another variant or another texture is a line of `check`.
   * `check`: every asset of every selected stage, both generator types of the AvatarAnimate conf and the renderer gradient of a
     CLIP-guided generator are verified BEFORE the first stage; all problems come in one ValueError.
   * out_dir/pipeline.json: per stage its status, wall seconds, outputs (size, sha256) and a fingerprint = sha256 over the stage's
@@ -248,6 +250,37 @@ def check_texture(path):
         raise SystemExit("--smpl_uv = %s cannot be loaded: %s" % (path, e))
 
 
+def _sidecar_names(codebook, tower):
+    """a codebook file whose sidecar (codebook.py: <file>.json) says that `tower`'s variant made its embeddings"""
+    from . import codebook as CB
+    side = CB.read_sidecar(codebook) if codebook is not None else None
+    return side is not None and side.get("tower") == CB.variant_name(tower)
+
+
+def check_codebooks(spec, stages):
+    """the pre-flight of the codebooks that carry a sidecar: one line per codebook made by another tower variant or with another texture than
+    the stage will search it with.  A codebook without a sidecar adds nothing (and no checkpoint is read for it)."""
+    from . import clip_vit
+    from . import codebook as CB
+    from .texture import load_obj_texture
+    books = [(st, path) for st, path in (("shape", spec.codebook_fname), ("motion", spec.codebook)) if st in stages and path is not None]
+    books = [(st, path) for st, path in books if CB.read_sidecar(path) is not None]
+    if not books:
+        return []
+    weights = spec.retrieval_clip_weights if spec.retrieval_clip_weights is not None else spec.clip_weights
+    if weights is None or not os.path.exists(weights):
+        return []                                           # (reported as a missing asset)
+    try:
+        variant = clip_vit.vision_variant(clip_vit.load_state_dict(weights))
+    except Exception as e:
+        return ["%s cannot be read to compare its tower with the codebooks' sidecars: %s" % (weights, e)]
+    try:
+        cubes = None if spec.smpl_uv is None else load_obj_texture(spec.smpl_uv)[2]
+    except (ValueError, OSError):
+        return []                                           # (reported by check_texture)
+    return ["%s (stage %s)" % (p, st) for st, path in books for p in CB.check_provenance(path, variant, cubes)]
+
+
 _CONF_OF = {"init": ("init",), "appearance": ("appearance",), "mesh": ("appearance",), "motion": ("animate",)}
 
 
@@ -306,6 +339,9 @@ def check(spec, manifest=None):
                 problems.append("%s is not set (stage %s)" % (flag(f), st))
             elif not os.path.exists(path):
                 problems.append("%s = %s does not exist (stage %s)" % (flag(f), path, st))
+    pose_book = ("motion" in sel and "animate" in confs_ok and _generator_types(confs_ok["animate"])[0] == "VPoserCodebook"
+                 and spec.text_feature is None)            # (a hooked text feature: no tower of this run meets the pose codebook)
+    problems += check_codebooks(spec, [st for st in sel if st == "shape" or (st == "motion" and pose_book)])
     if "motion" in sel and "animate" in confs_ok:
         from . import animate as A
         conf = confs_ok["animate"]
@@ -514,8 +550,9 @@ class Run:
             self._tokenizer = SimpleTokenizer(self.spec.bpe)
         return self._tokenizer
 
-    def tower(self, retrieval=False):
-        """the main tower; retrieval=True: the tower that searches the shipped codebooks -- the second checkpoint's when one is given"""
+    def tower(self, retrieval=False, codebook=None):
+        """the main tower; retrieval=True: the tower that searches the codebooks -- the second checkpoint's when one is given.  `codebook`:
+        the file the stage is about to search; when its sidecar (codebook.py) names the main tower's variant there is nothing to warn about"""
         global _B16_WARNED
         from . import clip_vit
         key = "retrieval" if retrieval and self.spec.retrieval_clip_weights is not None else "main"
@@ -523,7 +560,7 @@ class Run:
             sd = clip_vit.load_state_dict(self.spec.retrieval_clip_weights if key == "retrieval" else self.spec.clip_weights)
             self._towers[key] = clip_vit.ClipVision(sd, self.device)
         t = self._towers[key]
-        if retrieval and key == "main" and t.patch == 16 and not _B16_WARNED:
+        if retrieval and key == "main" and t.patch == 16 and not _B16_WARNED and not _sidecar_names(codebook, t):
             _B16_WARNED = True
             warnings.warn("the main CLIP checkpoint is ViT-B/16 and no --retrieval_clip_weights is given: the shipped shape and pose codebooks hold "
                           "ViT-B/32 embeddings and are searched with the wrong tower (README, paragraph \"ViT-B/32 or ViT-B/16\")")
@@ -568,7 +605,7 @@ def stage_shape(run):
     v_template, faces = read_obj(s.template_obj)
     model_AE = SG.create_load_AE(v_template.size, SHAPE_LATENT_DIM, v_template, s.AE_path_fname, dev)
     codebook, clip_codebook = SG.load_codebook(s.codebook_fname, dev)
-    tower = run.tower(retrieval=True)
+    tower = run.tower(retrieval=True, codebook=s.codebook_fname)
     nembed = run.text_embedding("neutral_txt", SG.parse_prompt(s.neutral_txt)[0], tower)
     tembed = run.text_embedding("target_txt", SG.parse_prompt(s.target_txt)[0], tower)
     render_fn = SG.textured_render_fn(faces, s.smpl_uv, dev) if s.smpl_uv is not None else None
@@ -644,7 +681,7 @@ def stage_motion(run):
         second = run.tower(retrieval=True)
         pose_ctx = A.AnimateContext(second, feature_of(second), smpl, vp, **kw)
     elif pose == "VPoserCodebook" and main is not None:
-        run.tower(retrieval=True)      # (the main tower again: warns once when it is a ViT-B/16)
+        run.tower(retrieval=True, codebook=s.codebook)      # (the main tower again: warns once when it is a ViT-B/16 that did not make the codebook)
     pose_assets = {"VPoserCodebook": {"codebook_path": s.codebook}, "VPoserRealNVP": {"ckpt_path": s.realnvp}}.get(pose, {})
     motion_assets = {"ckpt_path": s.motion_vae} if motion == "MotionOptimizer" else {}
     poses, _ = A.run(conf, ctx, pose_assets=pose_assets, motion_assets=motion_assets, pose_ctx=pose_ctx)
