@@ -24,13 +24,6 @@ template <typename P> __device__ __forceinline__ P launder(P p) {
   asm volatile("" : "+s"(p));
   return p;
 }
-template <typename V>
-__device__ __forceinline__ V zero_frag() {
-  V z;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) z[j] = (typename MF<V>::S)0.f;
-  return z;
-}
 // abar' = gbar_a g_h sp''(h) with gbar_a = gbar_h / s and g_h sp'' = g_a beta (1 - s): everything on the right is a tile
 // of the panels.  s -> 0 makes both gbar_h and g_a vanish; the guard keeps 0/0 out.
 __device__ __forceinline__ float second_term(float gbar_h, float g_a, float s) {
@@ -299,16 +292,13 @@ __device__ __forceinline__ void bwd_sweeps(StageT<BWD_G>& sg, const BwdArgs& a, 
     b8 gb1[N::HK];
     layer_sq1<b8, 3, N::HT>(sg, Wb, o.v[OFF_W0G], nxt<N, OFF_WM0>(sg, Wb, o), gb0, AVC_SECOND(gb1, L::P_H1, L::G_GBH1));
     b8 gbm[N::HK];
-    if constexpr (N::NMID == 2) {
-      layer_sq1<b8, N::HK, N::HT>(sg, Wb, o.v[OFF_WM0], nxt<N, OFF_WM1>(sg, Wb, o), gb1, AVC_SECOND(gbm, L::P_HM, L::G_GBHM));
-      b8 gbm1[N::HK];
+    layer_sq1<b8, N::HK, N::HT>(sg, Wb, o.v[OFF_WM0], nxt<N, (N::NMID == 2 ? OFF_WM1 : OFF_WS)>(sg, Wb, o), gb1,
+                                AVC_SECOND(gbm, L::P_HM, L::G_GBHM));
+    b8 gbm1[N::HK];   // behind the second middle layer (NMID == 2)
+    if constexpr (N::NMID == 2)
       layer_sq1<b8, N::HK, N::HT>(sg, Wb, o.v[OFF_WM1], nxt<N, OFF_WS>(sg, Wb, o), gbm,
                                   AVC_SECOND(gbm1, L::P_HM + N::HT, L::G_GBHM + N::HT));
-      layer_sq1<b8, N::HK, N::ST>(sg, Wb, o.v[OFF_WS], nxt<N, OFF_WLT>(sg, Wb, o), gbm1, AVC_SECOND_S(gbs, L::P_HS));
-    } else {
-      layer_sq1<b8, N::HK, N::HT>(sg, Wb, o.v[OFF_WM0], nxt<N, OFF_WS>(sg, Wb, o), gb1, AVC_SECOND(gbm, L::P_HM, L::G_GBHM));
-      layer_sq1<b8, N::HK, N::ST>(sg, Wb, o.v[OFF_WS], nxt<N, OFF_WLT>(sg, Wb, o), gbm, AVC_SECOND_S(gbs, L::P_HS));
-    }
+    layer_sq1<b8, N::HK, N::ST>(sg, Wb, o.v[OFF_WS], nxt<N, OFF_WLT>(sg, Wb, o), (N::NMID == 2 ? gbm1 : gbm), AVC_SECOND_S(gbs, L::P_HS));
   }
   // ------------------------------------------------------------------ phase F: reverse sweep (ii) (bf16)
   {
@@ -351,17 +341,14 @@ __device__ __forceinline__ void bwd_sweeps(StageT<BWD_G>& sg, const BwdArgs& a, 
     const Next first = nxt<N, OFF_CHT>(sg, a.Wb0, o);   // prefetch the first tile of the next block iteration
     // ... and the next block's delta_o and masks (issued after the first group barrier of the last layer)
 #define AVC_F_LASTHOOK AVC_HOOK(load_blk_in<N>(a, blk0_next + wv, nblk, lane, bi);)
-    if constexpr (N::NMID == 2) {
-      layer_sq1<b8, N::SK, N::HT>(sg, Wb, o.v[OFF_WST], nxt<N, OFF_WM1T>(sg, Wb, o), as_,
-                                 AVC_REVERSE(am, L::P_HM + N::HT, L::G_GBHM + N::HT, L::P_GAM + N::HT, L::G_ABM + N::HT));
+    constexpr int TOP = (N::NMID - 1) * N::HT;   // the last middle layer's tiles within hm / gbar_hm / g_am / abar_m
+    layer_sq1<b8, N::SK, N::HT>(sg, Wb, o.v[OFF_WST], nxt<N, (N::NMID == 2 ? OFF_WM1T : OFF_WM0T)>(sg, Wb, o), as_,
+                               AVC_REVERSE(am, L::P_HM + TOP, L::G_GBHM + TOP, L::P_GAM + TOP, L::G_ABM + TOP));
+    if constexpr (N::NMID == 2)
       layer_sq1<b8, N::HK, N::HT>(sg, Wb, o.v[OFF_WM1T], nxt<N, OFF_WM0T>(sg, Wb, o), am,
                                  AVC_REVERSE(am0, L::P_HM, L::G_GBHM, L::P_GAM, L::G_ABM));
-      layer_sq1<b8, N::HK, N::HT>(sg, Wb, o.v[OFF_WM0T], first, am0, AVC_REVERSE(am, L::P_H1, L::G_GBH1, L::P_GA1, L::G_AB1), AVC_F_LASTHOOK);
-    } else {
-      layer_sq1<b8, N::SK, N::HT>(sg, Wb, o.v[OFF_WST], nxt<N, OFF_WM0T>(sg, Wb, o), as_,
-                                 AVC_REVERSE(am, L::P_HM, L::G_GBHM, L::P_GAM, L::G_ABM));
-      layer_sq1<b8, N::HK, N::HT>(sg, Wb, o.v[OFF_WM0T], first, am, AVC_REVERSE(am0, L::P_H1, L::G_GBH1, L::P_GA1, L::G_AB1), AVC_F_LASTHOOK);
-    }
+    layer_sq1<b8, N::HK, N::HT>(sg, Wb, o.v[OFF_WM0T], first, (N::NMID == 2 ? am0 : am),
+                               AVC_REVERSE((N::NMID == 2 ? am : am0), L::P_H1, L::G_GBH1, L::P_GA1, L::G_AB1), AVC_F_LASTHOOK);
   }
 #undef AVC_RELU_BWD
 #undef AVC_SECOND

@@ -144,16 +144,35 @@ __device__ __forceinline__ void hook_tile(Hook&& hook, int t, int nt) {
   if constexpr (std::is_invocable_v<Hook, int, int>) hook(t, nt);
 }
 
+// ---- THE walk: the one place where the schedule above is written down.  Every layer form below is a wrapper of it.
+//   mma(j, t, two, a0, a1)  runs the chain of output tile t (tile j of the staged group) into a0 and, when `two`, that of tile t + 1 into a1
+//   pre(t)                  AVC_PRE: the global loads the epilogue of tile t needs, returned raw; NoPre: there are none
+//   epi(t, acc, data)       the epilogue of tile t (AVC_EPID); with NoPre it is epi(t, acc) (AVC_EPI)
 // PAIRED = two output tiles per MFMA stream.  Measured per 4 Mi points (profiles/r03_ab_kernels.txt): forward 6.16 -> 6.01 ms and
 // training forward 8.25 -> 7.84 ms with it (and 26 / 36 spilled registers become 0 / 12); the SDF-only kernel loses 6 % (its 168
 // registers leave no room for the second accumulator: 16 -> 28 spills) and the backward kernel 3 %: those keep one chain
 // (layer_s1, layer_sq1); the forward kernels pair everywhere (layer_s, layer_sq, layer2_s).
-template <bool PAIRED, typename V, int KS, int NT, class ST, typename Epi, typename Hook = NoHook, class Bias = NoBias>
-__device__ __forceinline__ void layer_sp(ST& st, const V* __restrict__ blob, int offw, const Next& after, const V (&in)[KS],
-                                         Epi&& epi, Hook&& hook = NoHook{}, const Bias& bias = NoBias{}) {
+// Loads one chain ahead: the loads of the pending epilogue(s) (panel tiles read back by the sweeps) go out BEFORE the chain(s) of the
+// current step and are consumed after them.  The backward kernel keeps only ~16 KiB of reads in flight per CU when every epilogue
+// loads and immediately waits; one chain (~600 cycles) of head start costs no extra live set beyond the loaded registers themselves.
+// (pre(t) before the chain of tile t itself -- two chains + one epilogue of head start, two load sets live -- measured slower for the
+// three-array loads of the reverse sweep: register pressure)
+#define AVC_PRE(...) [&](int t) __attribute__((always_inline)) { __VA_ARGS__ }
+#define AVC_EPID(DT, ...) [&](int t, const facc& acc, const DT& d) __attribute__((always_inline)) { __VA_ARGS__ }
+struct NoPre { __host__ __device__ __forceinline__ int operator()(int) const { return 0; } };   // (__host__: its result type is asked for outside device code)
+template <bool PAIRED, int KS, int NT, class ST, typename V, typename Mma, typename Pre, typename Epi, typename Hook>
+__device__ __forceinline__ void layer_walk(ST& st, const V* __restrict__ blob, int offw, const Next& after, Mma&& mma, Pre&& pre,
+                                           Epi&& epi, Hook&& hook) {
   constexpr int G = ST::template group<KS>();
   constexpr int NG = (NT + G - 1) / G;
+  constexpr bool LOADS = !std::is_same_v<std::decay_t<Pre>, NoPre>;
+  typedef std::invoke_result_t<Pre&, int> D;
+  auto finish = [&](int t, const facc& acc, const D& d) __attribute__((always_inline)) {
+    if constexpr (LOADS) epi(t, acc, d);
+    else epi(t, acc);
+  };
   facc prev0, prev1;
+  D d0{}, d1{};
   int tp = -1, np = 0;   // first tile / number of tiles whose epilogue is pending (compile-time after unrolling)
 #pragma unroll
   for (int g = 0; g < NG; ++g) {
@@ -174,12 +193,16 @@ __device__ __forceinline__ void layer_sp(ST& st, const V* __restrict__ blob, int
         const bool two = PAIRED && (j + 1 < G) && (t + 1 < NT);
         hook_tile(hook, t, NT);
         if (two) hook_tile(hook, t + 1, NT);
+        if (LOADS && np > 0) {
+          d0 = pre(tp);
+          if (np > 1) d1 = pre(tp + 1);
+          __builtin_amdgcn_sched_barrier(0);   // the loads go out before the chains
+        }
         facc a0, a1;
-        if (two) tile_mma_pair<V, KS>(st, j, in, a0, a1, bias, t);
-        else a0 = tile_mma<V, KS>(st, j, in, bias, t);
+        mma(j, t, two, a0, a1);
         if (np > 0) {
-          epi(tp, prev0);
-          if (np > 1) epi(tp + 1, prev1);
+          finish(tp, prev0, d0);
+          if (np > 1) finish(tp + 1, prev1, d1);
           if (two) { interleave_mfma_valu<KS>(); interleave_mfma_valu<KS>(); } else interleave_mfma_valu<KS>();
         }
         prev0 = a0;
@@ -190,177 +213,51 @@ __device__ __forceinline__ void layer_sp(ST& st, const V* __restrict__ blob, int
     }
     st.par ^= 1;
   }
-  epi(tp, prev0);
-  if (np > 1) epi(tp + 1, prev1);
+  if constexpr (LOADS) {
+    d0 = pre(tp);
+    if (np > 1) d1 = pre(tp + 1);
+  }
+  finish(tp, prev0, d0);
+  if (np > 1) finish(tp + 1, prev1, d1);
   __builtin_amdgcn_sched_barrier(0);
+}
+// one input array: the shared wrapper of the four forms below
+template <bool PAIRED, typename V, int KS, int NT, class ST, typename Pre, typename Epi, typename Hook, class Bias>
+__device__ __forceinline__ void layer_sp(ST& st, const V* __restrict__ blob, int offw, const Next& after, const V (&in)[KS],
+                                         Pre&& pre, Epi&& epi, Hook&& hook, const Bias& bias) {
+  layer_walk<PAIRED, KS, NT>(st, blob, offw, after, [&](int j, int t, bool two, facc& a0, facc& a1) __attribute__((always_inline)) {
+    if (two) tile_mma_pair<V, KS>(st, j, in, a0, a1, bias, t);
+    else a0 = tile_mma<V, KS>(st, j, in, bias, t);
+  }, pre, epi, hook);
 }
 template <typename V, int KS, int NT, class ST, typename Epi, typename Hook = NoHook, class Bias = NoBias>
 __device__ __forceinline__ void layer_s(ST& st, const V* __restrict__ blob, int offw, const Next& after, const V (&in)[KS],
                                         Epi&& epi, Hook&& hook = NoHook{}, const Bias& bias = NoBias{}) {
-  layer_sp<true, V, KS, NT>(st, blob, offw, after, in, epi, hook, bias);
+  layer_sp<true, V, KS, NT>(st, blob, offw, after, in, NoPre{}, epi, hook, bias);
 }
 template <typename V, int KS, int NT, class ST, typename Epi, typename Hook = NoHook, class Bias = NoBias>
 __device__ __forceinline__ void layer_s1(ST& st, const V* __restrict__ blob, int offw, const Next& after, const V (&in)[KS],
                                          Epi&& epi, Hook&& hook = NoHook{}, const Bias& bias = NoBias{}) {
-  layer_sp<false, V, KS, NT>(st, blob, offw, after, in, epi, hook, bias);   // always one accumulator chain
-}
-// ---- the same layer with the epilogue's global loads issued BEFORE the MFMA chain they trail: pre(t) returns the raw loads
-// ---- (panel tiles read back by the backward sweeps), epi(t, acc, data) consumes them after the chain of tile t+1.  The
-// ---- backward kernel keeps only ~16 KiB of reads in flight per CU when every epilogue loads and immediately waits; one
-// ---- chain (~600 cycles) of head start costs no extra live set beyond the loaded registers themselves.
-#define AVC_PRE(...) [&](int t) __attribute__((always_inline)) { __VA_ARGS__ }
-#define AVC_EPID(DT, ...) [&](int t, const facc& acc, const DT& d) __attribute__((always_inline)) { __VA_ARGS__ }
-// pre(t-1) goes out before the chain of tile t (one chain of head start, one load set live).  (pre(t) before the chain of tile t -- two
-// chains + one epilogue of head start, two sets live -- measured slower for the three-array loads of the reverse sweep: register
-// pressure)
-template <bool PAIRED, typename V, int KS, int NT, class ST, typename Pre, typename Epi, typename Hook>
-__device__ __forceinline__ void layer_sq_(ST& st, const V* __restrict__ blob, int offw, const Next& after, const V (&in)[KS],
-                                         Pre&& pre, Epi&& epi, Hook&& hook) {
-  constexpr int G = ST::template group<KS>();
-  constexpr int NG = (NT + G - 1) / G;
-  if constexpr (PAIRED) {
-    // two output tiles per MFMA stream: the loads of the previous pair's epilogues go out before the chains of the current pair
-    facc prev0, prev1;
-    decltype(pre(0)) d0{}, d1{};
-    int tp = -1, np = 0;
-#pragma unroll
-    for (int g = 0; g < NG; ++g) {
-      AVC_SYNC();
-      if (g + 1 < NG) {
-        Next n;
-        n.ptr = blob + (offw >> 3) + (long)((g + 1) * G * KS) * 64;
-        n.chunks = KS * ((NT - (g + 1) * G) < G ? (NT - (g + 1) * G) : G);
-        stage_issue(st, n, st.par ^ 1);
-      } else {
-        stage_issue(st, after, st.par ^ 1);
-      }
-      hook_call(hook, g);
-#pragma unroll
-      for (int j = 0; j < G; j += 2) {
-        const int t = g * G + j;
-        if (t < NT) {
-          const bool two = (j + 1 < G) && (t + 1 < NT);
-          hook_tile(hook, t, NT);
-          if (two) hook_tile(hook, t + 1, NT);
-          if (np > 0) {
-            d0 = pre(tp);
-            if (np > 1) d1 = pre(tp + 1);
-            __builtin_amdgcn_sched_barrier(0);   // the loads go out before the chains
-          }
-          facc a0, a1;
-          if (two) tile_mma_pair<V, KS>(st, j, in, a0, a1, NoBias{}, t);
-          else a0 = tile_mma<V, KS>(st, j, in);
-          if (np > 0) {
-            epi(tp, prev0, d0);
-            if (np > 1) epi(tp + 1, prev1, d1);
-            if (two) { interleave_mfma_valu<KS>(); interleave_mfma_valu<KS>(); } else interleave_mfma_valu<KS>();
-          }
-          prev0 = a0;
-          if (two) prev1 = a1;
-          tp = t; np = two ? 2 : 1;
-          __builtin_amdgcn_sched_barrier(0);
-        }
-      }
-      st.par ^= 1;
-    }
-    d0 = pre(tp);
-    if (np > 1) d1 = pre(tp + 1);
-    epi(tp, prev0, d0);
-    if (np > 1) epi(tp + 1, prev1, d1);
-    __builtin_amdgcn_sched_barrier(0);
-    return;
-  }
-  facc prev;
-  decltype(pre(0)) dprev{};
-#pragma unroll
-  for (int g = 0; g < NG; ++g) {
-    AVC_SYNC();
-    if (g + 1 < NG) {
-      Next n;
-      n.ptr = blob + (offw >> 3) + (long)((g + 1) * G * KS) * 64;
-      n.chunks = KS * ((NT - (g + 1) * G) < G ? (NT - (g + 1) * G) : G);
-      stage_issue(st, n, st.par ^ 1);
-    } else {
-      stage_issue(st, after, st.par ^ 1);
-    }
-    hook_call(hook, g);
-#pragma unroll
-    for (int j = 0; j < G; ++j) {
-      const int t = g * G + j;
-      if (t < NT) {
-        hook_tile(hook, t, NT);
-        if (t > 0) {
-          dprev = pre(t - 1);
-          __builtin_amdgcn_sched_barrier(0);   // the loads go out before the chain
-        }
-        facc acc = tile_mma<V, KS>(st, j, in);
-        if (t > 0) { epi(t - 1, prev, dprev); interleave_mfma_valu<KS>(); }
-        prev = acc;
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    }
-    st.par ^= 1;
-  }
-  dprev = pre(NT - 1);
-  epi(NT - 1, prev, dprev);
-  __builtin_amdgcn_sched_barrier(0);
+  layer_sp<false, V, KS, NT>(st, blob, offw, after, in, NoPre{}, epi, hook, bias);   // always one accumulator chain
 }
 template <typename V, int KS, int NT, class ST, typename Pre, typename Epi, typename Hook = NoHook>
 __device__ __forceinline__ void layer_sq(ST& st, const V* __restrict__ blob, int offw, const Next& after, const V (&in)[KS],
                                          Pre&& pre, Epi&& epi, Hook&& hook = NoHook{}) {
-  layer_sq_<true, V, KS, NT>(st, blob, offw, after, in, pre, epi, hook);
+  layer_sp<true, V, KS, NT>(st, blob, offw, after, in, pre, epi, hook, NoBias{});
 }
 template <typename V, int KS, int NT, class ST, typename Pre, typename Epi, typename Hook = NoHook>
 __device__ __forceinline__ void layer_sq1(ST& st, const V* __restrict__ blob, int offw, const Next& after, const V (&in)[KS],
                                           Pre&& pre, Epi&& epi, Hook&& hook = NoHook{}) {
-  layer_sq_<false, V, KS, NT>(st, blob, offw, after, in, pre, epi, hook);   // always one accumulator chain
+  layer_sp<false, V, KS, NT>(st, blob, offw, after, in, pre, epi, hook, NoBias{});   // always one accumulator chain
 }
+// the K dimension split over two input arrays (tiles of KA + KB k-steps)
 template <typename V, int KA, int KB, int NT, class ST, typename Epi, typename Hook = NoHook, class Bias = NoBias>
 __device__ __forceinline__ void layer2_s(ST& st, const V* __restrict__ blob, int offw, const Next& after, const V (&ina)[KA],
                                          const V (&inb)[KB], Epi&& epi, Hook&& hook = NoHook{}, const Bias& bias = NoBias{}) {
-  constexpr int KS = KA + KB;
-  constexpr int G = ST::template group<KS>();
-  constexpr int NG = (NT + G - 1) / G;
-  facc prev0, prev1;
-  int tp = -1, np = 0;
-#pragma unroll
-  for (int g = 0; g < NG; ++g) {
-    AVC_SYNC();
-    if (g + 1 < NG) {
-      Next n;
-      n.ptr = blob + (offw >> 3) + (long)((g + 1) * G * KS) * 64;
-      n.chunks = KS * ((NT - (g + 1) * G) < G ? (NT - (g + 1) * G) : G);
-      stage_issue(st, n, st.par ^ 1);
-    } else {
-      stage_issue(st, after, st.par ^ 1);
-    }
-    hook_call(hook, g);
-#pragma unroll
-    for (int j = 0; j < G; j += 2) {
-      const int t = g * G + j;
-      if (t < NT) {
-        const bool two = (j + 1 < G) && (t + 1 < NT);
-        hook_tile(hook, t, NT);
-        if (two) hook_tile(hook, t + 1, NT);
-        facc a0, a1;
-        if (two) tile_mma2_pair<V, KA, KB>(st, j, ina, inb, a0, a1, bias, t);
-        else a0 = tile_mma2<V, KA, KB>(st, j, ina, inb, bias, t);
-        if (np > 0) {
-          epi(tp, prev0);
-          if (np > 1) epi(tp + 1, prev1);
-          if (two) { interleave_mfma_valu<KS>(); interleave_mfma_valu<KS>(); } else interleave_mfma_valu<KS>();
-        }
-        prev0 = a0;
-        if (two) prev1 = a1;
-        tp = t; np = two ? 2 : 1;
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    }
-    st.par ^= 1;
-  }
-  epi(tp, prev0);
-  if (np > 1) epi(tp + 1, prev1);
-  __builtin_amdgcn_sched_barrier(0);
+  layer_walk<true, KA + KB, NT>(st, blob, offw, after, [&](int j, int t, bool two, facc& a0, facc& a1) __attribute__((always_inline)) {
+    if (two) tile_mma2_pair<V, KA, KB>(st, j, ina, inb, a0, a1, bias, t);
+    else a0 = tile_mma2<V, KA, KB>(st, j, ina, inb, bias, t);
+  }, NoPre{}, epi, hook);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -442,6 +339,14 @@ template <typename V> __device__ __forceinline__ AVC_GLOBAL V* tile_addr(const P
   asm("" : "+s"(tb));
   return (AVC_GLOBAL V*)(tb + pp.off);
 }
+// an all-zero fragment: the second half of an operand tile that has one k-step of content
+template <typename V>
+__device__ __forceinline__ V zero_frag() {
+  V z;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) z[j] = (typename MF<V>::S)0.f;
+  return z;
+}
 // KEEP = read back soon by the same kernel (normal cache policy), otherwise streamed past the caches (consumed by a later launch)
 // (No predicate: wavefronts past the end of the point set write to the SINK block that follows the last real block of the
 // panel buffer -- a branch around every store splits the scheduling regions of the epilogues and costs ~110 spilled registers.)
@@ -481,6 +386,10 @@ __device__ __forceinline__ FragPair<V> tile_load(const PanelPtr& pp, int tile) {
 
 // SDF value only (avc_sdf_forward): same layers as sdf_trunk but every activation array dies as soon as the next layer
 // has consumed it, which keeps the kernel at two wavefronts per SIMD.
+#define AVC_SDF_ACT(OUT)                                                                      \
+  AVC_EPI(float a[16];                                                                        \
+          softplus2_tile(acc, a);                                                             \
+          acc_to_frags(a, OUT[2 * t], OUT[2 * t + 1]);)
 template <class N, class ST, typename TP>
 __device__ __forceinline__ float sdf_only(ST& sg, const h8* __restrict__ Wf, TP T, const AvcOffsets& o,
                                           int h, const float (&x)[3]) {
@@ -499,31 +408,15 @@ __device__ __forceinline__ float sdf_only(ST& sg, const h8* __restrict__ Wf, TP 
     {
       h8 pef[3];
       pe_to_frags_f16(pe, x, h, pef);
-      layer_s1<h8, 3, N::HT>(sg, Wf, o.v[OFF_W0], nxt<N, OFF_WM0>(sg, Wf, o), pef, AVC_EPI(
-        float a[16];
-        softplus2_tile(acc, a);
-        acc_to_frags(a, h1[2 * t], h1[2 * t + 1]);
-      ), NoHook{}, TabBias{T + o.v[OFF_B0], h});
+      layer_s1<h8, 3, N::HT>(sg, Wf, o.v[OFF_W0], nxt<N, OFF_WM0>(sg, Wf, o), pef, AVC_SDF_ACT(h1),
+                             NoHook{}, TabBias{T + o.v[OFF_B0], h});
     }
-    if constexpr (N::NMID == 2) {
-      h8 hm0[N::HK];
-      layer_s1<h8, N::HK, N::HT>(sg, Wf, o.v[OFF_WM0], nxt<N, OFF_WM1>(sg, Wf, o), h1, AVC_EPI(
-        float a[16];
-        softplus2_tile(acc, a);
-        acc_to_frags(a, hm0[2 * t], hm0[2 * t + 1]);
-      ), NoHook{}, TabBias{T + o.v[OFF_BM0], h});
-      layer_s1<h8, N::HK, N::HT>(sg, Wf, o.v[OFF_WM1], nxt<N, OFF_WS>(sg, Wf, o), hm0, AVC_EPI(
-        float a[16];
-        softplus2_tile(acc, a);
-        acc_to_frags(a, hlast[2 * t], hlast[2 * t + 1]);
-      ), NoHook{}, TabBias{T + o.v[OFF_BM1], h});
-    } else {
-      layer_s1<h8, N::HK, N::HT>(sg, Wf, o.v[OFF_WM0], nxt<N, OFF_WS>(sg, Wf, o), h1, AVC_EPI(
-        float a[16];
-        softplus2_tile(acc, a);
-        acc_to_frags(a, hlast[2 * t], hlast[2 * t + 1]);
-      ), NoHook{}, TabBias{T + o.v[OFF_BM0], h});
-    }
+    h8 hm0[N::HK];   // between the two middle layers (NMID == 2)
+    layer_s1<h8, N::HK, N::HT>(sg, Wf, o.v[OFF_WM0], nxt<N, (N::NMID == 2 ? OFF_WM1 : OFF_WS)>(sg, Wf, o), h1,
+                               AVC_SDF_ACT((N::NMID == 2 ? hm0 : hlast)), NoHook{}, TabBias{T + o.v[OFF_BM0], h});
+    if constexpr (N::NMID == 2)
+      layer_s1<h8, N::HK, N::HT>(sg, Wf, o.v[OFF_WM1], nxt<N, OFF_WS>(sg, Wf, o), hm0, AVC_SDF_ACT(hlast),
+                                 NoHook{}, TabBias{T + o.v[OFF_BM1], h});
   }
   layer_s1<h8, N::HK, N::ST>(sg, Wf, o.v[OFF_WS], no_next(), hlast, AVC_EPI(
     float w[16];
@@ -532,3 +425,4 @@ __device__ __forceinline__ float sdf_only(ST& sg, const h8* __restrict__ Wf, TP 
   ), NoHook{}, TabBias{T + o.v[OFF_BS], h});
   return xhalf_sum(part) + T[o.v[OFF_BL0]];
 }
+#undef AVC_SDF_ACT

@@ -2,7 +2,8 @@
 //   avc_sdf_forward       SDF only (row 0 of the last layer) -- the no-grad evaluations of the hierarchical sampler
 //                         (renderer.py:337-338,187) and of extract_fields (renderer.py:10-25)
 //   avc_render_points_fwd sdf + normal (d sdf/dx) + 6 colour channels per sample point (renderer.py:221-232)
-// The layers of THIS file run two output tiles per MFMA stream (independent accumulator chains; layer_s, layer_sq, layer2_s of avc_mlp.h):
+// The layers of mlp_render_kernel run two output tiles per MFMA stream (independent accumulator chains: layer_s, layer_sq, layer2_s, the
+// PAIRED wrappers of avc_mlp.h's layer_walk; mlp_sdf_kernel keeps one chain, layer_s1):
 // forward 6.21 -> 6.02 ms, training forward 8.20 -> 7.90 ms per 4 Mi points; the backward kernel loses 4 % with it and keeps one chain
 // (profiles/r03_ab_kernels.txt).
 #include "avc_mlp.h"
@@ -146,26 +147,19 @@ __global__ __launch_bounds__(64 * FWD_WPB) void mlp_render_kernel(PointSrc ps, l
         h8 h1[N::HK];
         layer_s<h8, 3, N::HT>(sg, Wf, o.v[OFF_W0], nxt<N, OFF_WM0>(sg, Wf, o), pef, AVC_F_ACT(h1), AVC_HOOK(
           if constexpr (TRAIN) {
-            h8 zf;
-            _Pragma("unroll") for (int j = 0; j < 8; ++j) zf[j] = (_Float16)0.f;
             tile_store<false>(tiles, L::P_H0, pef[0], pef[1]);
-            tile_store<false>(tiles, L::P_H0 + 1, pef[2], zf);
+            tile_store<false>(tiles, L::P_H0 + 1, pef[2], zero_frag<h8>());
           }), AVC_F_BIAS(OFF_B0));
         h8 hm0[N::HK];
-        if constexpr (N::NMID == 2) {
-          layer_s<h8, N::HK, N::HT>(sg, Wf, o.v[OFF_WM0], nxt<N, OFF_WM1>(sg, Wf, o), h1, AVC_F_ACT(hm0),
-                                    AVC_STORE_HOOK(true, N::HT, L::P_H1, h1), AVC_F_BIAS(OFF_BM0));
-          h8 hm1[N::HK];
+        layer_s<h8, N::HK, N::HT>(sg, Wf, o.v[OFF_WM0], nxt<N, (N::NMID == 2 ? OFF_WM1 : OFF_WS)>(sg, Wf, o), h1, AVC_F_ACT(hm0),
+                                  AVC_STORE_HOOK(true, N::HT, L::P_H1, h1), AVC_F_BIAS(OFF_BM0));
+        h8 hm1[N::HK];   // behind the second middle layer (NMID == 2)
+        if constexpr (N::NMID == 2)
           layer_s<h8, N::HK, N::HT>(sg, Wf, o.v[OFF_WM1], nxt<N, OFF_WS>(sg, Wf, o), hm0, AVC_F_ACT(hm1),
                                     AVC_STORE_HOOK(true, N::HT, L::P_HM, hm0), AVC_F_BIAS(OFF_BM1));
-          layer_s<h8, N::HK, N::ST>(sg, Wf, o.v[OFF_WS], nxt<N, OFF_WL>(sg, Wf, o), hm1, AVC_F_LAST(),
-                                    AVC_STORE_HOOK(true, N::HT, L::P_HM + N::HT, hm1), AVC_F_BIAS(OFF_BS));
-        } else {
-          layer_s<h8, N::HK, N::HT>(sg, Wf, o.v[OFF_WM0], nxt<N, OFF_WS>(sg, Wf, o), h1, AVC_F_ACT(hm0),
-                                    AVC_STORE_HOOK(true, N::HT, L::P_H1, h1), AVC_F_BIAS(OFF_BM0));
-          layer_s<h8, N::HK, N::ST>(sg, Wf, o.v[OFF_WS], nxt<N, OFF_WL>(sg, Wf, o), hm0, AVC_F_LAST(),
-                                    AVC_STORE_HOOK(true, N::HT, L::P_HM, hm0), AVC_F_BIAS(OFF_BS));
-        }
+        layer_s<h8, N::HK, N::ST>(sg, Wf, o.v[OFF_WS], nxt<N, OFF_WL>(sg, Wf, o), (N::NMID == 2 ? hm1 : hm0), AVC_F_LAST(),
+                                  AVC_STORE_HOOK(true, N::HT, L::P_HM + (N::NMID - 1) * N::HT, (N::NMID == 2 ? hm1 : hm0)),
+                                  AVC_F_BIAS(OFF_BS));
       }
       sdf = xhalf_sum(part) + T[o.v[OFF_BL0]];
       // feature = rows 1..H of the last layer on u = [h_s ; pe]/sqrt2 (1/sqrt2 folded into the packed weights)
@@ -194,17 +188,13 @@ __global__ __launch_bounds__(64 * FWD_WPB) void mlp_render_kernel(PointSrc ps, l
 #define AVC_F_GSTORE(PG, G) AVC_HOOKG(if constexpr (TRAIN) tiles_store_part<false, N::HT>(tiles, PG, G, grp_, ngrp_);)
       h8 g[N::HK];
       h8 g2[N::HK];
-      if constexpr (N::NMID == 2) {
-        layer_sq<h8, N::SK, N::HT>(sg, Wf, o.v[OFF_WST], nxt<N, OFF_WM1T>(sg, Wf, o), g_s, AVC_F_NSTEP(g, L::P_HM + N::HT));
+      layer_sq<h8, N::SK, N::HT>(sg, Wf, o.v[OFF_WST], nxt<N, (N::NMID == 2 ? OFF_WM1T : OFF_WM0T)>(sg, Wf, o), g_s,
+                                 AVC_F_NSTEP((N::NMID == 2 ? g : g2), L::P_HM + (N::NMID - 1) * N::HT));
+      if constexpr (N::NMID == 2)
         layer_sq<h8, N::HK, N::HT>(sg, Wf, o.v[OFF_WM1T], nxt<N, OFF_WM0T>(sg, Wf, o), g, AVC_F_NSTEP(g2, L::P_HM),
                                    AVC_F_GSTORE(L::P_GAM + N::HT, g));
-        layer_sq<h8, N::HK, N::HT>(sg, Wf, o.v[OFF_WM0T], nxt<N, OFF_W0T>(sg, Wf, o), g2, AVC_F_NSTEP(g, L::P_H1),
-                                   AVC_F_GSTORE(L::P_GAM, g2));
-      } else {
-        layer_sq<h8, N::SK, N::HT>(sg, Wf, o.v[OFF_WST], nxt<N, OFF_WM0T>(sg, Wf, o), g_s, AVC_F_NSTEP(g2, L::P_HM));
-        layer_sq<h8, N::HK, N::HT>(sg, Wf, o.v[OFF_WM0T], nxt<N, OFF_W0T>(sg, Wf, o), g2, AVC_F_NSTEP(g, L::P_H1),
-                                   AVC_F_GSTORE(L::P_GAM, g2));
-      }
+      layer_sq<h8, N::HK, N::HT>(sg, Wf, o.v[OFF_WM0T], nxt<N, OFF_W0T>(sg, Wf, o), g2, AVC_F_NSTEP(g, L::P_H1),
+                                 AVC_F_GSTORE(L::P_GAM, g2));
       float part[3] = {0.f, 0.f, 0.f};
       const auto wpe = T + o.v[OFF_WL0_PE] + h * 24;
       // the PE derivatives are RE-computed here from an opaque copy of x: hipcc otherwise merges this call with the one at the top
@@ -247,32 +237,18 @@ __global__ __launch_bounds__(64 * FWD_WPB) void mlp_render_kernel(PointSrc ps, l
 #define AVC_F_RSTORE(PT, R)                                                                   \
   AVC_HOOKG(if constexpr (TRAIN) tiles_store_part<false, N::HT>(tiles, PT, R, grp_, ngrp_);)
       h8 r1[N::HK];
-      h8 r2[N::HK];
-      if constexpr (N::NCMID == 1) {
-        layer2_s<h8, N::HK, 1, N::HT>(sg, Wf, o.v[OFF_C0], nxt<N, OFF_CM0>(sg, Wf, o), feat, xn, AVC_F_RELU(r1, 0), AVC_HOOK(
-          if constexpr (TRAIN) {
-            h8 zf;
-            _Pragma("unroll") for (int j = 0; j < 8; ++j) zf[j] = (_Float16)0.f;
-            tile_store<false>(tiles, L::P_XN, xn[0], zf);
-          }), AVC_F_BIAS(OFF_CB0));
+      layer2_s<h8, N::HK, 1, N::HT>(sg, Wf, o.v[OFF_C0], nxt<N, (N::NCMID == 1 ? OFF_CM0 : OFF_CH)>(sg, Wf, o), feat, xn, AVC_F_RELU(r1, 0),
+        AVC_HOOK(if constexpr (TRAIN) tile_store<false>(tiles, L::P_XN, xn[0], zero_frag<h8>());), AVC_F_BIAS(OFF_CB0));
+      h8 r2[N::HK];   // behind the middle layer (NCMID == 1)
+      if constexpr (N::NCMID == 1)
         layer_s<h8, N::HK, N::HT>(sg, Wf, o.v[OFF_CM0], nxt<N, OFF_CH>(sg, Wf, o), r1, AVC_F_RELU(r2, 1),
                                   AVC_F_RSTORE(L::P_R1, r1), AVC_F_BIAS(OFF_CBM0));
-      } else {
-        layer2_s<h8, N::HK, 1, N::HT>(sg, Wf, o.v[OFF_C0], nxt<N, OFF_CH>(sg, Wf, o), feat, xn, AVC_F_RELU(r1, 0), AVC_HOOK(
-          if constexpr (TRAIN) {
-            h8 zf;
-            _Pragma("unroll") for (int j = 0; j < 8; ++j) zf[j] = (_Float16)0.f;
-            tile_store<false>(tiles, L::P_XN, xn[0], zf);
-          }), AVC_F_BIAS(OFF_CB0));
-#pragma unroll
-        for (int s = 0; s < N::HK; ++s) r2[s] = r1[s];
-      }
       // the first tile of the next block iteration is prefetched under the head layer
-      layer_s<h8, N::HK, 1>(sg, Wf, o.v[OFF_CH], nxt<N, OFF_W0>(sg, Wf0, o), r2, AVC_EPI(
+      layer_s<h8, N::HK, 1>(sg, Wf, o.v[OFF_CH], nxt<N, OFF_W0>(sg, Wf0, o), (N::NCMID == 1 ? r2 : r1), AVC_EPI(
         float b[16];
         load16(T + o.v[OFF_CBH], 0, h, b);
         _Pragma("unroll") for (int r = 0; r < 4; ++r) rgb[r] = sigmoidf_(acc[r] + b[r]);
-      ), AVC_F_RSTORE((N::NCMID == 1 ? L::P_R2 : L::P_R1), r2));
+      ), AVC_F_RSTORE((N::NCMID == 1 ? L::P_R2 : L::P_R1), (N::NCMID == 1 ? r2 : r1)));
     }
     if (valid) {
       if (h == 0) {

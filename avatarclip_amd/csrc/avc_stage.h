@@ -185,10 +185,8 @@ __device__ __forceinline__ void tile_mma2_pair(const ST& st, int j, const V (&in
 // Where the accumulator of an output tile starts: zero, or the tile's bias row read from the fp32 table in LDS straight into
 // the accumulator registers (the C operand of the first MFMA) -- one VALU add per output element less in the epilogue, on an
 // engine whose VALU time adds to its MFMA time.
-// MFMAs of tile j of the current group (KS k-steps per tile) against the register-resident B operands
-template <typename V, int KS, class ST, class B = NoBias>
-__device__ __forceinline__ facc tile_mma(const ST& st, int j, const V (&in)[KS], const B& bias = NoBias{}, int t = 0) {
-  const V* a = reinterpret_cast<const V*>(st.lds + st.par * ST::BUF_BYTES + j * KS * 1024) + st.lane;
+template <class B>
+__device__ __forceinline__ facc acc_init(const B& bias, int t) {
   facc acc;
   if constexpr (B::on) {
     float b[16];
@@ -199,21 +197,20 @@ __device__ __forceinline__ facc tile_mma(const ST& st, int j, const V (&in)[KS],
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[r] = 0.f;
   }
+  return acc;
+}
+// MFMAs of tile j of the current group (KS k-steps per tile) against the register-resident B operands
+// (acc_init stands before the fragment address: the other order gives mlp_sdf_kernel two scratch registers' names swapped)
+template <typename V, int KS, class ST, class B = NoBias>
+__device__ __forceinline__ facc tile_mma(const ST& st, int j, const V (&in)[KS], const B& bias = NoBias{}, int t = 0) {
+  const facc acc = acc_init(bias, t);
+  const V* a = reinterpret_cast<const V*>(st.lds + st.par * ST::BUF_BYTES + j * KS * 1024) + st.lane;
   return mma_chain_lds<V, KS>(a, in, acc);
 }
 template <typename V, int KA, int KB, class ST, class B = NoBias>
 __device__ __forceinline__ facc tile_mma2(const ST& st, int j, const V (&ina)[KA], const V (&inb)[KB], const B& bias = NoBias{}, int t = 0) {
+  facc acc = acc_init(bias, t);
   const V* a = reinterpret_cast<const V*>(st.lds + st.par * ST::BUF_BYTES + j * (KA + KB) * 1024) + st.lane;
-  facc acc;
-  if constexpr (B::on) {
-    float b[16];
-    load16(bias.tab, t, bias.h, b);
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = b[r];
-  } else {
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-  }
   acc = mma_chain_lds<V, KA>(a, ina, acc);
   return mma_chain_lds<V, KB>(a + KA * 64, inb, acc);
 }
