@@ -13,7 +13,7 @@
 //      Z = floor(((c_z - near) * far) / (c_z * (far - near)) * (2^24 - 1) + 0.5)   24 bits of NDC z: 0 at near, 2^24 - 1 at far
 //      1/w = (float)(1 / c_z)
 //    A vertex is INVALID (Z = -1) unless near < c_z <= far and -PV_GUARD <= X, Y <= 256 R + PV_GUARD (NaN fails the comparisons).
-//    A face with an invalid vertex is dropped, not clipped.
+//    A face with an invalid vertex is dropped, not clipped (csrc/avc_preview_clip.hip clips it: the same device functions, csrc/avc_preview.h).
 // 2. avc_preview_raster.  A face is oriented first: area2 = (x1 - x0)(y2 - y0) - (y1 - y0)(x2 - x0); 0: skipped; < 0: vertices 1 and 2
 //    change places (both windings are drawn, the depth test alone decides visibility).  With edge i the one opposite vertex i, from a to b
 //    (edge 0: 1 -> 2, edge 1: 2 -> 0, edge 2: 0 -> 1), the weight of a pixel centre p is w_i = (bx - ax)(py - ay) - (by - ay)(px - ax)
@@ -44,110 +44,30 @@
 //    averaged and rounded to nearest (floor(x + 0.5), clamped to [0, 255]).  The keys are set back to all-ones on the way, the large-face
 //    lists by one strided fill after it: the scratch leaves as it came, every byte 0xFF.
 // 4. avc_skin_blend4: out[t, m] = sum_k weights[m, k] (joint_mats[t, joints[m, k]] (rest[m], 1)), k = 0..3 in this order, fp32.
-#include "avc_common.h"
+#include "avc_preview.h"         // the device functions shared with csrc/avc_preview_clip.hip: set-up, weights, key, the passes' pieces
 #include "../../include/avc.h"
 
 #pragma clang fp contract(off)   // the projection must be the restatement's operation by operation
-
-#define PV_THREADS 256
-#define PV_GUARD 65536           // sub-pixel units beyond the raster on each side within which a vertex stays valid (256 raster pixels)
-#define PV_SERIAL 4              // pixel centres in a face's box up to which its own lane finishes it
-#define PV_LARGE 1024            // ... from which it goes to the tile-parallel pass
-#define PV_TILE 16
-#define PV_EMPTY 0xFFFFFFFFFFFFFFFFull
-#define PV_ZMAX 16777215.0       // 2^24 - 1
-
-typedef int i4 __attribute__((ext_vector_type(4)));
 
 // ------------------------------------------------------------------------------------------------------------- projection
 __global__ __launch_bounds__(PV_THREADS) void pv_project_kernel(const float* __restrict__ v, int V, const float* __restrict__ cams, double width,
                                                                 double near, double far, int R, i4* __restrict__ proj) {
   const int i = blockIdx.x * PV_THREADS + threadIdx.x, n = blockIdx.y;
   if (i >= V) return;
-  const float* cam = cams + 12 * (long)n;
-  const float* p = v + 3 * ((long)n * V + i);
-  const double d0 = (double)p[0] - (double)cam[0], d1 = (double)p[1] - (double)cam[1], d2 = (double)p[2] - (double)cam[2];
   double c[3];
-#pragma unroll
-  for (int j = 0; j < 3; ++j) c[j] = (d0 * (double)cam[3 + 3 * j] + d1 * (double)cam[4 + 3 * j]) + d2 * (double)cam[5 + 3 * j];
+  pv_camera_point(v + 3 * ((long)n * V + i), cams + 12 * (long)n, c);
   i4 o = {0, 0, -1, 0};
   if (c[2] > near && c[2] <= far) {
-    const double s = c[2] * width, half = (double)R * 0.5;
-    const double X = floor((c[0] / s + 1.0) * half * 256.0 + 0.5), Y = floor((1.0 - c[1] / s) * half * 256.0 + 0.5);
+    double X, Y, Z;
+    pv_snap(c[0], c[1], c[2], width, near, far, R, X, Y, Z);
     const double hi = 256.0 * (double)R + (double)PV_GUARD;
-    if (X >= -(double)PV_GUARD && X <= hi && Y >= -(double)PV_GUARD && Y <= hi) {
-      double Z = floor(((c[2] - near) * far) / (c[2] * (far - near)) * PV_ZMAX + 0.5);
-      Z = fmin(fmax(Z, 0.0), PV_ZMAX);
+    if (X >= -(double)PV_GUARD && X <= hi && Y >= -(double)PV_GUARD && Y <= hi)
       o = i4{(int)X, (int)Y, (int)Z, (int)__float_as_uint((float)(1.0 / c[2]))};
-    }
   }
   proj[(long)n * V + i] = o;
 }
 
-// ------------------------------------------------------------------------------------------------------------- the face
-struct PvFace {
-  int x0, y0, x1, y1, x2, y2, z0, z1, z2;
-  int b0, b1, b2;                  // 0 for a top-left edge, 1 otherwise: covered <=> w_i >= b_i
-  long long area2;
-  double inv_area2;
-  int xa, xb, ya, yb;              // pixels whose centres can be covered (clamped to the raster)
-  int i0, i1, i2;                  // the vertices, in oriented order
-};
-__device__ __forceinline__ long long pv_edge(int ax, int ay, int bx, int by, int px, int py) {
-  return (long long)(bx - ax) * (long long)(py - ay) - (long long)(by - ay) * (long long)(px - ax);
-}
-__device__ __forceinline__ int pv_bias(int ax, int ay, int bx, int by) { return (by < ay || (by == ay && bx > ax)) ? 0 : 1; }
-
-// false: dropped (a corner outside [0, V), an invalid corner, zero area) or no pixel centre inside the raster can be covered
-__device__ __forceinline__ bool pv_setup(const i4* __restrict__ proj, const int* __restrict__ tris, int f, int V, int R, PvFace& e) {
-  e.i0 = tris[3 * (long)f];
-  e.i1 = tris[3 * (long)f + 1];
-  e.i2 = tris[3 * (long)f + 2];
-  if ((unsigned)e.i0 >= (unsigned)V || (unsigned)e.i1 >= (unsigned)V || (unsigned)e.i2 >= (unsigned)V) return false;
-  i4 a = proj[e.i0], b = proj[e.i1], c = proj[e.i2];
-  if (a[2] < 0 || b[2] < 0 || c[2] < 0) return false;
-  long long area2 = pv_edge(a[0], a[1], b[0], b[1], c[0], c[1]);
-  if (area2 == 0) return false;
-  if (area2 < 0) {
-    const i4 t = b; b = c; c = t;
-    const int ti = e.i1; e.i1 = e.i2; e.i2 = ti;
-    area2 = -area2;
-  }
-  e.x0 = a[0]; e.y0 = a[1]; e.z0 = a[2];
-  e.x1 = b[0]; e.y1 = b[1]; e.z1 = b[2];
-  e.x2 = c[0]; e.y2 = c[1]; e.z2 = c[2];
-  e.area2 = area2;
-  e.inv_area2 = 1.0 / (double)area2;
-  e.b0 = pv_bias(e.x1, e.y1, e.x2, e.y2);
-  e.b1 = pv_bias(e.x2, e.y2, e.x0, e.y0);
-  e.b2 = pv_bias(e.x0, e.y0, e.x1, e.y1);
-  // centre 256 i + 128 in [lo, hi]  <=>  ceil((lo - 128) / 256) <= i <= floor((hi - 128) / 256)   (>> of an int: floor)
-  e.xa = max(0, (min(e.x0, min(e.x1, e.x2)) + 127) >> 8); e.xb = min(R - 1, (max(e.x0, max(e.x1, e.x2)) - 128) >> 8);
-  e.ya = max(0, (min(e.y0, min(e.y1, e.y2)) + 127) >> 8); e.yb = min(R - 1, (max(e.y0, max(e.y1, e.y2)) - 128) >> 8);
-  return e.xb >= e.xa && e.yb >= e.ya;
-}
-// the three weights at pixel (xi, yi); true: covered
-__device__ __forceinline__ bool pv_weights(const PvFace& e, int xi, int yi, long long& w0, long long& w1, long long& w2) {
-  const int px = 256 * xi + 128, py = 256 * yi + 128;
-  w0 = pv_edge(e.x1, e.y1, e.x2, e.y2, px, py);
-  w1 = pv_edge(e.x2, e.y2, e.x0, e.y0, px, py);
-  w2 = e.area2 - w0 - w1;
-  return w0 >= e.b0 && w1 >= e.b1 && w2 >= e.b2;
-}
-// the key of face f at a covered pixel
-__device__ __forceinline__ unsigned long long pv_key(const PvFace& e, long long w0, long long w1, long long w2, int f) {
-  const long long sum = w0 * e.z0 + w1 * e.z1 + w2 * e.z2;
-  long long q = (long long)((double)sum * e.inv_area2);
-  long long r = sum - q * e.area2;
-  if (r < 0) { --q; r += e.area2; }
-  if (r >= e.area2) ++q;
-  return ((unsigned long long)q << 32) | (unsigned)f;
-}
-
 // ------------------------------------------------------------------------------------------------------------- raster
-// per frame: zbuf [R*R] keys, then large = [count - 1 (0xFFFFFFFF: none), face indices ...]
-__device__ __forceinline__ unsigned long long* pv_zbuf(void* scratch, long stride, int n) { return (unsigned long long*)((char*)scratch + stride * n); }
-
 __global__ __launch_bounds__(PV_THREADS) void pv_raster_kernel(const i4* __restrict__ proj_all, const int* __restrict__ tris, int F, int V, int R,
                                                                void* __restrict__ scratch, long stride) {
   const int n = blockIdx.y, lane = threadIdx.x & 63;
@@ -157,22 +77,9 @@ __global__ __launch_bounds__(PV_THREADS) void pv_raster_kernel(const i4* __restr
   unsigned* large = (unsigned*)(zbuf + (long)R * R);
   PvFace e;
   const bool ok = f < F && pv_setup(proj, tris, f, V, R, e);
-  int w = 0, cnt = 0;
-  if (ok) {
-    w = e.xb - e.xa + 1;
-    cnt = w * (e.yb - e.ya + 1);
-  }
-  if (ok && cnt <= PV_SERIAL) {
-    for (int k = 0; k < cnt; ++k) {
-      const int xi = e.xa + k % w, yi = e.ya + k / w;
-      long long w0, w1, w2;
-      if (pv_weights(e, xi, yi, w0, w1, w2)) atomicMin(&zbuf[(long)yi * R + xi], pv_key(e, w0, w1, w2, f));
-    }
-  }
-  if (ok && cnt > PV_LARGE) {                                 // every face once: at most F entries (a scratch that did not come in as
-    const unsigned slot = atomicAdd(&large[0], 1u) + 1u;      // 0xFF starts the count anywhere: nothing is written past the list)
-    if (slot < (unsigned)F) large[1 + slot] = (unsigned)f;
-  }
+  const int cnt = ok ? pv_centres(e) : 0;
+  if (ok && cnt <= PV_SERIAL) pv_walk(e, f, 0, 1, R, zbuf);
+  if (ok && cnt > PV_LARGE) pv_list(large, F, f);
   unsigned long long todo = __ballot(ok && cnt > PV_SERIAL && cnt <= PV_LARGE);             // wave-uniform from here on
   while (todo) {
     const int src = __ffsll((long long)todo) - 1;
@@ -180,12 +87,7 @@ __global__ __launch_bounds__(PV_THREADS) void pv_raster_kernel(const i4* __restr
     const int fs = __shfl(f, src);
     PvFace g;
     if (!pv_setup(proj, tris, fs, V, R, g)) continue;                                       // (it passed in lane src: never taken)
-    const int gw = g.xb - g.xa + 1, gn = gw * (g.yb - g.ya + 1);
-    for (int k = lane; k < gn; k += 64) {
-      const int xi = g.xa + k % gw, yi = g.ya + k / gw;
-      long long w0, w1, w2;
-      if (pv_weights(g, xi, yi, w0, w1, w2)) atomicMin(&zbuf[(long)yi * R + xi], pv_key(g, w0, w1, w2, fs));
-    }
+    pv_walk(g, fs, lane, 64, R, zbuf);
   }
 }
 
@@ -209,11 +111,7 @@ __global__ __launch_bounds__(PV_THREADS) void pv_large_kernel(const i4* __restri
     if ((unsigned)f >= (unsigned)F) continue;
     PvFace e;
     if (!pv_setup(proj, tris, f, V, R, e)) continue;
-    if (e.xb < tx0 || e.xa > tx0 + PV_TILE - 1 || e.yb < ty0 || e.ya > ty0 + PV_TILE - 1) continue;     // (uniform over the workgroup)
-    long long w0, w1, w2;
-    if (!inside || !pv_weights(e, xi, yi, w0, w1, w2)) continue;
-    const unsigned long long key = pv_key(e, w0, w1, w2, f);
-    best = key < best ? key : best;
+    pv_tile_key(e, f, tx0, ty0, xi, yi, inside, best);
   }
   if (inside && best != PV_EMPTY) {
     unsigned long long* z = &zbuf[(long)yi * R + xi];
@@ -282,36 +180,13 @@ __global__ __launch_bounds__(PV_THREADS) void pv_shade_kernel(const i4* __restri
       PvFace e;
       if (key != PV_EMPTY && (unsigned)f < (unsigned)F && pv_setup(proj, tris, f, V, R, e)) {
         id = f;
-        long long w0, w1, w2;
-        pv_weights(e, xi, yi, w0, w1, w2);
-        const float l0 = (float)w0 * __uint_as_float((unsigned)proj[e.i0][3]);
-        const float l1 = (float)w1 * __uint_as_float((unsigned)proj[e.i1][3]);
-        const float l2 = (float)w2 * __uint_as_float((unsigned)proj[e.i2][3]);
-        const float den = (l0 + l1) + l2;
-        const float* a = vw + 3 * (long)e.i0;
-        const float* b = vw + 3 * (long)e.i1;
-        const float* d = vw + 3 * (long)e.i2;
-        const float ux = b[0] - a[0], uy = b[1] - a[1], uz = b[2] - a[2], tx = d[0] - a[0], ty = d[1] - a[1], tz = d[2] - a[2];
-        const float nx = uy * tz - uz * ty, ny = uz * tx - ux * tz, nz = ux * ty - uy * tx;
-        const float nn = sqrtf((nx * nx + ny * ny) + nz * nz) * sqrtf((l[0] * l[0] + l[1] * l[1]) + l[2] * l[2]);
-        const float shade = nn > 0.f ? ambient + (1.f - ambient) * fminf(fabsf((nx * l[0] + ny * l[1]) + nz * l[2]) / nn, 1.f) : ambient;
-#pragma unroll
-        for (int ch = 0; ch < 3; ++ch) {
-          float col = grey;
-          if (colors)
-            col = ((l0 * (float)colors[(long)csize * e.i0 + ch] + l1 * (float)colors[(long)csize * e.i1 + ch]) +
-                   l2 * (float)colors[(long)csize * e.i2 + ch]) / den;
-          c[ch] = col * shade;
-        }
+        pv_shade_plain(e, proj, vw, colors, csize, l, ambient, grey, xi, yi, c);
       }
       if (face_ids) face_ids[((long)n * R + yi) * R + xi] = id;
 #pragma unroll
       for (int ch = 0; ch < 3; ++ch) acc[ch] += c[ch];
     }
-  const float inv = 1.f / (float)(ss * ss);
-#pragma unroll
-  for (int ch = 0; ch < 3; ++ch)
-    image[((long)n * S * S + p) * 3 + ch] = (unsigned char)fminf(fmaxf(floorf(acc[ch] * inv + 0.5f), 0.f), 255.f);
+  pv_store_pixel(image, (long)n * S * S + p, acc, ss);
 }
 
 extern "C" int avc_preview_shade(const int* proj, const float* v, int N, int V, const int* tris, int F, const unsigned char* colors, int csize,

@@ -1,6 +1,6 @@
 """ctypes binding of libavc.so.  include/avc.h declares the C ABI, csrc/avc_texture.h the textured-render entry points and
-csrc/avc_codebook.h the k-means entry points added beside it: load() parses the tuple headers() returns, merges their prototypes and derives every
-restype / argtypes from them, and call() checks each tensor against the element type the header gives its parameter.  No
+csrc/avc_codebook.h the k-means entry points added beside it, csrc/avc_preview_clip.h the preview's clipping entry points: load() parses the
+tuple headers() returns and then added_headers(), merges their prototypes and derives every restype / argtypes from them, and call() checks each tensor against the element type the header gives its parameter.  No
 fallback: if the library is missing, lacks a symbol the header declares, or a call fails, an exception is raised."""
 import collections
 import ctypes
@@ -19,9 +19,18 @@ TEXTURE_HEADER = os.path.join(_build.CSRC, _build.TEXTURE_HEADER)     # more ent
 CODEBOOK_HEADER = os.path.join(_build.CSRC, _build.CODEBOOK_HEADER)   # the k-means entry points, likewise
 
 
+PREVIEW_CLIP_HEADER = os.path.join(_build.CSRC, _build.PREVIEW_CLIP_HEADER)   # the preview's clipping entry points, likewise
+
+
 def headers():
     """the tuple of headers load() parses, in this order (read when called); a name that two of them declare is refused"""
     return (HEADER, TEXTURE_HEADER, CODEBOOK_HEADER)
+
+
+def added_headers():
+    """the headers load() parses after headers(), under the same rules (read when called): entry points declared beside their source
+    since the three above were fixed"""
+    return (PREVIEW_CLIP_HEADER,)
 
 
 c_int, c_long, c_float, c_double, c_void_p, c_char_p = (ctypes.c_int, ctypes.c_long, ctypes.c_float, ctypes.c_double,
@@ -150,7 +159,7 @@ def load():
         raise RuntimeError("libavc.so is not built (run `python -c 'import __graft_entry__ as g; g.build()'`); "
                            "there is no CPU fallback for the HIP hot path")
     protos, declared_in = {}, {}
-    for header in headers():
+    for header in headers() + added_headers():
         with open(header) as f:
             more, abi = parse_header(f.read())
         if header == HEADER:

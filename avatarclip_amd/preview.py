@@ -4,6 +4,7 @@ animate writes, as a GIF or a PNG.
     python -m avatarclip_amd.preview (--mesh X.ply [--pc2 M.pc2] | --glb X.glb | --smpl SMPL.npz --poses X.npy) --out P.gif|P.png
                                      [--views 36] [--size 512] [--ss 2] [--up y|z] [--elevation deg] [--fov deg]
                                      [--fps 30] [--every k] [--frames-dir D] [--orbit]
+                                     [--focus head|upper|lower|LO:HI] [--eye X Y Z --at X Y Z] [--clip]
 
 A static source (a .ply alone, a .glb without a track, one pose) makes a turn-table of --views frames; a moving one (a .pc2, a .glb with a
 track, a motion of more than one pose) plays its frames from the fixed front camera, or from a camera that goes round once with --orbit.
@@ -18,8 +19,11 @@ does); its rest pose is y up.
 The reference renders its results through pyrender and OSMesa (AvatarAnimate/visualize.py: render_pose, render_motion); this is a renderer
 of this project's own (csrc/avc_preview.hip: exact integer coverage and depth, top-left fill rule, vertex colours, flat two-sided shading
 with a headlight), not a port of that one.  A FACE WITH A VERTEX NEARER THAN `near`, BEYOND `far` OR OUTSIDE THE GUARD BAND OF 256 RASTER
-PIXELS AROUND THE IMAGE IS DROPPED, NOT CLIPPED.  frame_cameras' cameras never produce one; a camera of your own that comes close to the
-mesh will lose whole faces."""
+PIXELS AROUND THE IMAGE IS DROPPED, NOT CLIPPED, UNLESS `clip`.  frame_cameras' whole-mesh cameras never produce one; a close-up does:
+--focus frames a band of the mesh's height (head = 0.84:1, upper = 0.5:1, lower = 0:0.5, or LO:HI), --eye / --at place one fixed camera
+by hand, and both (like --clip alone) turn the frustum clipper on (csrc/avc_preview_clip.hip: such a face is cut at near, far and the four
+sides one raster pixel outside the guard band, and what is left is drawn under the face's own index), so the shoulders run out of a
+picture of the head instead of going missing.  Without these options every picture is bit for bit what it was."""
 import argparse
 import math
 import os
@@ -37,6 +41,7 @@ CHUNK_BYTES = 256 << 20                   # device memory of one chunk of frames
 GREY = 200.0                              # the colour of a mesh without colours
 _UP = {"y": (0.0, 1.0, 0.0), "z": (0.0, 0.0, 1.0)}
 _FRONT = {"y": (0.0, 0.0, 1.0), "z": (0.0, -1.0, 0.0)}   # where the avatar looks: +z in SMPL's frame, -y after drive's (x, y, z) -> (x, -z, y)
+FOCUS = {"head": (0.84, 1.0), "upper": (0.5, 1.0), "lower": (0.0, 0.5)}   # --focus: bands of the mesh's extent along `up`
 
 
 def _up_vector(up):
@@ -71,17 +76,53 @@ def bounding_sphere(vertices):
     return c.double().cpu().numpy(), float(r)
 
 
-def frame_cameras(vertices, n_views=36, elevation=10.0, up="y", fov=40.0, margin=0.05):
+def depth_range(vertices, eyes):
+    """(near, far) of the whole bounding sphere of `vertices` seen from `eyes` [n,3], near floored at far * 1e-3: render_frames' default"""
+    ctr, rad = bounding_sphere(vertices)
+    dist = np.linalg.norm(np.asarray(eyes, np.float64).reshape(-1, 3) - ctr[None], axis=1)
+    far = float(dist.max() + rad) * 1.01
+    return max(float(dist.min() - rad) * 0.99, far * 1e-3), far
+
+
+def parse_focus(text):
+    """'head' | 'upper' | 'lower' | 'LO:HI' -> (lo, hi) with 0 <= lo < hi <= 1"""
+    if text in FOCUS:
+        return FOCUS[text]
+    try:
+        lo, hi = (float(x) for x in str(text).split(":"))
+    except ValueError:
+        raise ValueError("--focus is head, upper, lower or LO:HI, got %r" % (text,)) from None
+    if not 0.0 <= lo < hi <= 1.0:
+        raise ValueError("--focus LO:HI needs 0 <= LO < HI <= 1, got %r" % (text,))
+    return lo, hi
+
+
+def frame_cameras(vertices, n_views=36, elevation=10.0, up="y", fov=40.0, margin=0.05, focus=None):
     """Auto-framed cameras: n_views eyes on a circle around the `up` axis through the centre of the bounding sphere of ALL frames
     (vertices [N,V,3] or [V,3], tensor or array), `elevation` degrees above the horizon, at the distance at which the sphere's outline
     stays `margin` (a fraction of the half image) inside the field of view `fov` (degrees, full angle).  View 0 is the front view.
-    Returns (eyes [n,3], ats [n,3], near, far) with every vertex strictly between near and far for each of the cameras."""
+    Returns (eyes [n,3], ats [n,3], near, far) with every vertex strictly between near and far for each of the cameras.
+    focus = (lo, hi), 0 <= lo < hi <= 1, frames a BAND of the mesh instead: the sphere is that of the vertices (of all frames) whose
+    coordinate along `up` lies in that fraction of the mesh's extent along `up` (none: a ValueError); near and far still come from the
+    WHOLE mesh (depth_range: a hand in front of the face is not cut away, near floored at far * 1e-3), so the rest of the mesh runs out of
+    the picture -- render such cameras with render_frames(clip=True)."""
     v = vertices if torch.is_tensor(vertices) else torch.as_tensor(np.asarray(vertices, np.float32))
     if v.numel() == 0 or v.shape[-1] != 3:
         raise ValueError("frame_cameras takes [N, V, 3] or [V, 3] vertices, V > 0")
     if not 0.0 <= margin < 1.0 or not 0.0 < fov < 180.0 or n_views < 1:
         raise ValueError("frame_cameras: margin in [0, 1), fov in (0, 180), n_views >= 1")
-    c, r = bounding_sphere(v.to(torch.float32))
+    v = v.to(torch.float32)
+    band = v
+    if focus is not None:
+        lo, hi = (float(x) for x in focus)
+        if not 0.0 <= lo < hi <= 1.0:
+            raise ValueError("frame_cameras: focus = (lo, hi) with 0 <= lo < hi <= 1, got %r" % (focus,))
+        h = v.reshape(-1, 3)[:, int(np.argmax(_up_vector(up)))]
+        h0, h1 = (float(x) for x in torch.aminmax(h))
+        band = v.reshape(-1, 3)[(h >= h0 + lo * (h1 - h0)) & (h <= h0 + hi * (h1 - h0))]
+        if band.shape[0] == 0:
+            raise ValueError("frame_cameras: no vertex lies in the band %g:%g of the mesh's height" % (lo, hi))
+    c, r = bounding_sphere(band)
     r = max(r, 1e-6)
     # the outline of a sphere at distance d is a circle of tan(asin(r / d)) around the image centre
     d = r / math.sin(math.atan((1.0 - margin) * math.tan(math.radians(fov) * 0.5)))
@@ -92,7 +133,10 @@ def frame_cameras(vertices, n_views=36, elevation=10.0, up="y", fov=40.0, margin
     el = math.radians(elevation)
     dirs = math.cos(el) * (np.cos(a)[:, None] * f[None] + np.sin(a)[:, None] * s[None]) + math.sin(el) * u[None]
     eyes = c[None] + d * dirs
-    return eyes, np.broadcast_to(c[None], eyes.shape).copy(), (d - r) * 0.99, (d + r) * 1.01
+    ats = np.broadcast_to(c[None], eyes.shape).copy()
+    if focus is not None:
+        return (eyes, ats) + depth_range(v, eyes)
+    return eyes, ats, (d - r) * 0.99, (d + r) * 1.01
 
 
 # ---------------------------------------------------------------------------------------------------------------- the renderer
@@ -110,12 +154,14 @@ def scratch_bytes(num_faces, raster_size):
 
 
 def render_frames(vertices, triangles, colors=None, eyes=None, ats=None, up="y", fov=40.0, image_size=512, ss=2, light=None, ambient=0.4,
-                  background=(255, 255, 255), return_face_ids=False, near=None, far=None, chunk_bytes=CHUNK_BYTES, scratch=None):
+                  background=(255, 255, 255), return_face_ids=False, near=None, far=None, chunk_bytes=CHUNK_BYTES, scratch=None, clip=False):
     """uint8 [N,S,S,3] device tensor (row 0 = top) of N frames of ONE topology.  vertices [N,V,3] (or [V,3]: the same mesh for every
     camera), triangles [F,3], colors uint8 [V,3|4] or None (a constant grey) -- device tensors or arrays; eyes / ats [N,3] (or [3]);
     light [N,3] or [3] direction, None = a headlight (at - eye).  near / far default to the range of the frames' bounding sphere seen from
     the eyes.  With return_face_ids also int32 [N, S ss, S ss], the winning face of every raster pixel (-1: background).  Frames are
-    rendered in chunks of at most chunk_bytes of device memory.  Faces with a vertex outside (near, far] or the guard band are dropped.
+    rendered in chunks of at most chunk_bytes of device memory.  Faces with a vertex outside (near, far] or the guard band are dropped;
+    with clip=True they are clipped at the frustum instead (avc_preview_raster_clip / avc_preview_shade_clip) and every other face is
+    drawn bit for bit as without it.
     scratch: a uint8 device tensor of at least scratch_bytes(F, S ss) bytes, all 0xFF, to use instead of a fresh one (it comes back all
     0xFF)."""
     check_raster(int(image_size), int(ss))
@@ -149,13 +195,7 @@ def render_frames(vertices, triangles, colors=None, eyes=None, ats=None, up="y",
     cams = look_frames(eyes, ats, up)
     lights = (ats - eyes) if light is None else np.broadcast_to(np.asarray(light, np.float64).reshape(-1, 3), (N, 3))
     if near is None or far is None:
-        if V:
-            ctr, rad = bounding_sphere(v)
-            dist = np.linalg.norm(eyes - ctr[None], axis=1)
-            far_d = float(dist.max() + rad) * 1.01
-            near_d = max(float(dist.min() - rad) * 0.99, far_d * 1e-3)
-        else:
-            near_d, far_d = 0.1, 10.0
+        near_d, far_d = depth_range(v, eyes) if V else (0.1, 10.0)
         near, far = (near_d if near is None else near), (far_d if far is None else far)
     if not 0.0 < near < far:
         raise ValueError("render_frames needs 0 < near < far")
@@ -183,7 +223,15 @@ def render_frames(vertices, triangles, colors=None, eyes=None, ats=None, up="y",
         vk = (v[f0:f0 + k] if v.shape[0] == N else v.expand(k, -1, -1)).contiguous()
         if V:
             L.call("avc_preview_project", vk, k, V, cams_d[f0:f0 + k], width, near, far, R, proj, stream=s)
-            L.call("avc_preview_raster", proj, k, V, t if F else None, F, R, scratch, stream=s)
+            if clip:
+                L.call("avc_preview_raster_clip", proj, vk, k, V, cams_d[f0:f0 + k], width, near, far, t if F else None, F, R, scratch, stream=s)
+            else:
+                L.call("avc_preview_raster", proj, k, V, t if F else None, F, R, scratch, stream=s)
+        if clip:
+            L.call("avc_preview_shade_clip", proj, vk if V else None, k, V, cams_d[f0:f0 + k], width, near, far, t if F else None, F, c,
+                   c.shape[1] if c is not None else 0, lights_d[f0:f0 + k], float(ambient), bg[0], bg[1], bg[2], GREY, S, ss, scratch,
+                   images[f0:f0 + k], ids[f0:f0 + k] if ids is not None else None, stream=s)
+            continue
         L.call("avc_preview_shade", proj, vk if V else None, k, V, t if F else None, F, c, c.shape[1] if c is not None else 0, lights_d[f0:f0 + k],
                float(ambient), bg[0], bg[1], bg[2], GREY, S, ss, scratch, images[f0:f0 + k], ids[f0:f0 + k] if ids is not None else None, stream=s)
     return (images, ids) if return_face_ids else images
@@ -354,14 +402,22 @@ def save_frames(images, out, fps=30.0, frames_dir=None):
 
 
 def preview(out, mesh=None, pc2=None, glb=None, views=36, size=512, ss=2, up=None, elevation=10.0, fov=40.0, fps=30.0, every=1,
-            frames_dir=None, orbit=False, margin=0.05, smpl=None, poses=None):
-    """The whole tool: one source -> frames -> a file.  Returns (out, images)."""
+            frames_dir=None, orbit=False, margin=0.05, smpl=None, poses=None, focus=None, eye=None, at=None, clip=False):
+    """The whole tool: one source -> frames -> a file.  Returns (out, images).  focus: a band for frame_cameras (a name of FOCUS, 'LO:HI'
+    or a pair); eye + at: one hand-placed fixed camera for every frame (a static source: one frame); either, or clip, turns clipping on."""
     if (smpl is None) != (poses is None):
         raise ValueError("--smpl and --poses go together: the SMPL model and the poses to put it in")
     if (mesh is not None) + (glb is not None) + (smpl is not None) != 1:
         raise ValueError("give exactly one source: --mesh X.ply [--pc2 M.pc2], --glb X.glb or --smpl SMPL.npz --poses X.npy")
     if pc2 is not None and mesh is None:
         raise ValueError("--pc2 needs the --mesh it was written for")
+    if (eye is None) != (at is None):
+        raise ValueError("--eye and --at go together: where the camera stands and what it looks at")
+    if eye is not None and focus is not None:
+        raise ValueError("--focus frames the camera itself: it does not go with --eye / --at")
+    if focus is not None:
+        focus = parse_focus(focus) if isinstance(focus, str) else tuple(focus)
+    clip = bool(clip) or focus is not None or eye is not None
     check_raster(size, ss)
     if os.path.splitext(out)[1].lower() not in (".gif", ".png"):
         raise ValueError("--out ends in .gif or .png, got %r" % out)
@@ -376,8 +432,12 @@ def preview(out, mesh=None, pc2=None, glb=None, views=36, size=512, ss=2, up=Non
     v = v if torch.is_tensor(v) else torch.from_numpy(v).cuda()
     T = v.shape[0]
     n = T if moving else int(views)
-    eyes, ats, near, far = frame_cameras(v, n if (orbit or not moving) else 1, elevation, up, fov, margin)
-    images = render_frames(v, t, c, eyes, ats, up=up, fov=fov, image_size=size, ss=ss, near=near, far=far)
+    if eye is not None:
+        eyes, ats = np.asarray(eye, np.float64).reshape(1, 3), np.asarray(at, np.float64).reshape(1, 3)
+        near = far = None                                     # render_frames' default: the whole mesh's range seen from the eye
+    else:
+        eyes, ats, near, far = frame_cameras(v, n if (orbit or not moving) else 1, elevation, up, fov, margin, focus=focus)
+    images = render_frames(v, t, c, eyes, ats, up=up, fov=fov, image_size=size, ss=ss, near=near, far=far, clip=clip)
     return save_frames(images, out, fps, frames_dir), images
 
 
@@ -399,13 +459,17 @@ def main(argv=None):
     ap.add_argument("--every", type=int, default=1, help="take every k-th frame of a motion")
     ap.add_argument("--frames-dir", default=None, help="also write every frame as a numbered PNG there")
     ap.add_argument("--orbit", action="store_true", help="a moving source: the camera goes round once while the motion plays")
+    ap.add_argument("--focus", default=None, help="a close-up of a band of the mesh's height: head (0.84:1), upper (0.5:1), lower (0:0.5) or LO:HI")
+    ap.add_argument("--eye", type=float, nargs=3, default=None, metavar=("X", "Y", "Z"), help="a hand-placed fixed camera: where it stands (with --at)")
+    ap.add_argument("--at", type=float, nargs=3, default=None, metavar=("X", "Y", "Z"), help="... and the point it looks at")
+    ap.add_argument("--clip", action="store_true", help="clip faces at the frustum instead of dropping them (implied by --focus and --eye)")
     args = ap.parse_args(argv)
     try:
         if args.views < 1 or args.every < 1 or args.fps <= 0:
             raise ValueError("--views, --every and --fps are positive")
         out, _ = preview(args.out, mesh=args.mesh, pc2=args.pc2, glb=args.glb, views=args.views, size=args.size, ss=args.ss, up=args.up,
                          elevation=args.elevation, fov=args.fov, fps=args.fps, every=args.every, frames_dir=args.frames_dir, orbit=args.orbit,
-                         smpl=args.smpl, poses=args.poses)
+                         smpl=args.smpl, poses=args.poses, focus=args.focus, eye=args.eye, at=args.at, clip=args.clip)
     except ValueError as e:
         raise SystemExit("preview: %s" % e)
     print(out)

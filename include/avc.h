@@ -425,7 +425,8 @@ int avc_rot_to_quat(const float* R, long n, float* q, void* stream);
  * (256 i + 128, 256 j + 128)); Z = floor(((c_z - near) far) / (c_z (far - near)) (2^24 - 1) + 0.5) (24 bits of NDC z).  A vertex is invalid
  * (Z = -1) unless near < c_z <= far and -2^16 <= X, Y <= 256 R + 2^16 (a guard band of 256 raster pixels).
  * A FACE WITH AN INVALID VERTEX IS DROPPED, NOT CLIPPED: a camera inside the mesh, or nearer to it than `near`, loses whole faces.
- * preview.frame_cameras never produces one; a caller's own camera can.
+ * preview.frame_cameras never produces one for the whole mesh; a close-up or a caller's own camera can.  csrc/avc_preview_clip.h declares
+ * avc_preview_raster_clip / avc_preview_shade_clip, which take the place of the two calls below and CLIP such a face instead.
  *
  * avc_preview_raster: tris [F,3] int32 (a corner outside [0, V) drops the face).  Oriented area2 = (x1 - x0)(y2 - y0) - (y1 - y0)(x2 - x0):
  * 0 skips the face, < 0 swaps vertices 1 and 2 (no back-face culling).  Edge i (opposite vertex i) runs a -> b: 1 -> 2, 2 -> 0, 0 -> 1;
