@@ -12,7 +12,7 @@ ABI_HEADER = os.path.join("..", "..", "include", "avc.h")          # the one dec
 TEXTURE_HEADER = "avc_texture.h"                                   # the textured-render entry points (lib.py parses it too), in CSRC: include/ holds avc.h alone
 CODEBOOK_HEADER = "avc_codebook.h"                                 # the k-means entry points (csrc/avc_codebook.hip), declared beside their source as well
 PREVIEW_CLIP_HEADER = "avc_preview_clip.h"                         # the preview's clipping entry points (csrc/avc_preview_clip.hip), declared beside their source
-HEADERS = ["avc_common.h", "avc_stage.h", "avc_mlp.h", "avc_bwd_body.h", "avc_offsets_gen.h", "avc_raster.h", "avc_raster_grad.h", "avc_smpl.h", ABI_HEADER,
+HEADERS = ["avc_common.h", "avc_stage.h", "avc_mlp.h", "avc_bwd_body.h", "avc_offsets_gen.h", "avc_raster.h", "avc_raster_grad.h", "avc_smpl.h", "avc_vit.h", ABI_HEADER,
            TEXTURE_HEADER, CODEBOOK_HEADER, "avc_preview.h", PREVIEW_CLIP_HEADER]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-comment"]
 

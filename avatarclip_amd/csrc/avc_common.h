@@ -226,6 +226,19 @@ __device__ __forceinline__ unsigned relu_frags(const A& acc, h8& f0, h8& f1) {
 }
 
 __device__ __forceinline__ float xhalf_sum(float v) { return v + __shfl_xor(v, 32); }
+// Sum / maximum over the wavefront -- or, W < 64, over each aligned group of W lanes of it -- by the xor butterfly W/2 .. 1: every lane
+// of the group receives the result, the same bits in each (one fixed order of additions per lane pair).
+template <int W = 64, typename T>
+__device__ __forceinline__ T wave_sum(T v) {
+#pragma unroll
+  for (int d = W / 2; d >= 1; d >>= 1) v += __shfl_xor(v, d);
+  return v;
+}
+__device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) v = fmaxf(v, __shfl_xor(v, d));
+  return v;
+}
 
 // Positional-encoding slots (host mirror: packing.pe_slot_table):
 //   half 0: q 0..2 = x_c ; q 3+6k+c = sin(2^k x_c), 6+6k+c = cos(2^k x_c) for k=0..2 ; q 21..23 = x_lo_c

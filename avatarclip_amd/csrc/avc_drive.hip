@@ -186,9 +186,7 @@ __global__ __launch_bounds__(256) void cc_count_kernel(const int* __restrict__ l
     ++n;
   }
   const int lead = __shfl(cur, 0);                       // (lanes past the end hold cur = -1, n = 0)
-  int s = cur == lead ? n : 0;
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) s += __shfl_xor(s, m);
+  const int s = wave_sum(cur == lead ? n : 0);
   if (cur != lead && n) atomicAdd(count + cur, n);
   if ((threadIdx.x & 63) == 0 && lead >= 0 && s) atomicAdd(count + lead, s);
 }

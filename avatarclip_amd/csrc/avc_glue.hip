@@ -99,8 +99,7 @@ __global__ __launch_bounds__(GLUE_THREADS) void shade_loss_fwd_kernel(GlueIn g, 
   }
   __shared__ float red[4][GLUE_THREADS / 64];
   __shared__ bool last;
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) { l1 += __shfl_xor(l1, d); ms += __shfl_xor(ms, d); bce += __shfl_xor(bce, d); sq += __shfl_xor(sq, d); }
+  l1 = wave_sum(l1); ms = wave_sum(ms); bce = wave_sum(bce); sq = wave_sum(sq);
   const int wv = threadIdx.x >> 6;
   if ((threadIdx.x & 63) == 0) { red[0][wv] = l1; red[1][wv] = ms; red[2][wv] = bce; red[3][wv] = sq; }
   __syncthreads();
@@ -122,10 +121,7 @@ __global__ __launch_bounds__(GLUE_THREADS) void shade_loss_fwd_kernel(GlueIn g, 
     for (int k = 0; k < 4; ++k) acc[k] += v[k];
   }
 #pragma unroll
-  for (int k = 0; k < 4; ++k) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) acc[k] += __shfl_xor(acc[k], d);
-  }
+  for (int k = 0; k < 4; ++k) acc[k] = wave_sum(acc[k]);
   if ((threadIdx.x & 63) == 0) {
 #pragma unroll
     for (int k = 0; k < 4; ++k) red[k][wv] = acc[k];
@@ -481,8 +477,7 @@ extern "C" int avc_coarse_z(const float* near, const float* far, const float* ji
 #define TAIL_D 512
 struct TailW { float igr_w, mask_w, clip_w, P; };
 __device__ __forceinline__ float tail_block_sum(float v, float (*red)[TAIL_D / 64], int slot) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
+  v = wave_sum(v);
   if ((threadIdx.x & 63) == 0) red[slot][threadIdx.x >> 6] = v;
   __syncthreads();
   float t = 0.f;

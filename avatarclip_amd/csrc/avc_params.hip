@@ -21,11 +21,6 @@ struct WnDesc {
   int n;
 };
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
 __device__ __forceinline__ int find_layer(const WnDesc& d, int row) {
   int l = 0;
   while (l + 1 < d.n && row >= d.row_start[l + 1]) ++l;

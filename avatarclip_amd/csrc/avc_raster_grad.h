@@ -11,12 +11,6 @@
 
 #pragma clang fp contract(off)   // the floors / ceilings of the crossings must be the fp32 restatement's
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
-  return v;
-}
-
 // one (edge, axis) of a front-facing face: the rules of DESIGN.md section 8 (tests/nr_grad_restatement.py), lanes over the runs' pixels.
 // E = edge (a = E, b = E + 1, o = E + 2, mod 3), AX = 0: u = x, w = y (vertical runs, ndc y gets the gradient), AX = 1: u = y, w = x.
 template <int E, int AX, class View>

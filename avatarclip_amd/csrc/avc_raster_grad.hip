@@ -11,7 +11,7 @@
 // Then one thread per (render, vertex) gathers its faces' sums through a vertex -> face CSR.  No float atomics: the result is deterministic.
 #include "avc_common.h"
 #include "../../include/avc.h"
-#include "avc_raster_grad.h"     // wave_sum, edge_axis, rg_face_grad_kernel<View>: the walk, shared with the textured backward (avc_raster_tex.hip)
+#include "avc_raster_grad.h"     // edge_axis, rg_face_grad_kernel<View>: the walk, shared with the textured backward (avc_raster_tex.hip)
 
 #pragma clang fp contract(off)   // the floors / ceilings of the crossings must be the fp32 restatement's
 

@@ -1,5 +1,5 @@
-// Per-ray kernels: hierarchical up-sampling and NeuS compositing (forward + reverse).  One wavefront per ray,
-// the ray's samples staged in LDS, wave scans for the cumulative product / sum.
+// Per-ray kernels: hierarchical up-sampling and NeuS compositing (forward + reverse).  One wavefront per ray (up-sampling: a group of
+// 16, 32 or 64 lanes), the ray's samples staged in LDS, scans over the wavefront / the group for the cumulative product / sum.
 //   avc_upsample_step   renderer.py:133-177 (up_sample) + :39-69 (sample_pdf, det=True) + :179-193 (cat_z_vals merge)
 //   avc_composite_fwd   renderer.py:234-286 (alpha, transmittance, colours, eikonal partials)
 //   avc_composite_bwd   its reverse
@@ -14,25 +14,18 @@
 // synchronisation there is -- a workgroup barrier here made the four rays of a block wait for each other nine times per step.
 #define WAVE_SYNC() asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory")
 
-__device__ __forceinline__ float wave_incl_scan_mul(float v, int lane) {
+// Inclusive scans over the aligned groups of W lanes of a wavefront (W a power of two; l = the lane's index in its group); the sum of
+// such a group is wave_sum<W> (avc_common.h).
+template <int W>
+__device__ __forceinline__ float incl_scan_mul(float v, int l) {
 #pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    float o = __shfl_up(v, d);
-    if (lane >= d) v *= o;
-  }
+  for (int d = 1; d < W; d <<= 1) { const float o = __shfl_up(v, d, W); if (l >= d) v *= o; }
   return v;
 }
-__device__ __forceinline__ float wave_incl_scan_add(float v, int lane) {
+template <int W>
+__device__ __forceinline__ float incl_scan_add(float v, int l) {
 #pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    float o = __shfl_up(v, d);
-    if (lane >= d) v += o;
-  }
-  return v;
-}
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
+  for (int d = 1; d < W; d <<= 1) { const float o = __shfl_up(v, d, W); if (l >= d) v += o; }
   return v;
 }
 
@@ -42,150 +35,28 @@ __device__ __forceinline__ void excl_cumprod(float* buf, int n, int per, int lan
   float loc = 1.f;
   const int b = lane * per;
   for (int k = 0; k < per; ++k) if (b + k < n) loc *= buf[b + k];
-  float inc = wave_incl_scan_mul(loc, lane);
+  float inc = incl_scan_mul<64>(loc, lane);
   float run = __shfl_up(inc, 1);
   if (lane == 0) run = 1.f;
   for (int k = 0; k < per; ++k) {
     if (b + k < n) { const float t = buf[b + k]; buf[b + k] = run; run *= t; }
   }
 }
-// inclusive cumsum in place
-__device__ __forceinline__ void incl_cumsum(float* buf, int n, int per, int lane) {
-  float loc = 0.f;
-  const int b = lane * per;
-  for (int k = 0; k < per; ++k) if (b + k < n) loc += buf[b + k];
-  float inc = wave_incl_scan_add(loc, lane);
-  float run = __shfl_up(inc, 1);
-  if (lane == 0) run = 0.f;
-  for (int k = 0; k < per; ++k) {
-    if (b + k < n) { run += buf[b + k]; buf[b + k] = run; }
-  }
-}
 
+// One up-sampling step, a group of GL lanes per ray: GL = 16 for n + m <= 64 (the reference's 64-spp confs: n = 32 .. 56, m = 8 -- four
+// rays per wavefront), GL = 32 for n + m <= 128 (the 128-spp conf: two), GL = 64 -- a whole wavefront per ray -- for everything larger,
+// for m > 16 and as the cross-check partner of the tests.  A lane owns every GL-th sample in the elementwise phases and a contiguous
+// chunk of <= 4 in the scans.  With one ray per wavefront most of a step's instructions are scan / search / synchronisation overhead
+// executed for 32-56 live lanes (8 in the inversion); a group pays that overhead once for its ray and the wavefront carries four of
+// them (profiles/r04_ab_kernels.txt).  The row of new depths holds 16 entries for the grouped sizes (m <= 16) and 64 for GL = 64.
+template <int GL>
 __global__ __launch_bounds__(256) void upsample_kernel(const float* __restrict__ rays_o, const float* __restrict__ rays_d,
-                                                       const float* __restrict__ z_in, const float* __restrict__ sdf_in,
-                                                       int R, int n, int m, float inv_s, float* __restrict__ z_out,
-                                                       float* __restrict__ sdf_out, float* __restrict__ z_new,
-                                                       int* __restrict__ slot_new) {
-  __shared__ float sz[RPB][MAXS], ss[RPB][MAXS], sa[RPB][MAXS], sc[RPB][MAXS], sn[RPB][64];
-  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  // (wavefronts past the last ray redo ray R - 1 without storing)
-  const bool active = blockIdx.x * RPB + w < R;
-  const int ray = active ? blockIdx.x * RPB + w : R - 1;
-  float* Z = sz[w]; float* Sd = ss[w]; float* A = sa[w]; float* C = sc[w]; float* NZ = sn[w];
-  const float ox = rays_o[3 * ray], oy = rays_o[3 * ray + 1], oz = rays_o[3 * ray + 2];
-  const float dx = rays_d[3 * ray], dy = rays_d[3 * ray + 1], dz = rays_d[3 * ray + 2];
-  for (int i = lane; i < n; i += 64) { Z[i] = z_in[(long)ray * n + i]; Sd[i] = sdf_in[(long)ray * n + i]; }
-  WAVE_SYNC();
-  const int nm1 = n - 1;
-  // raw cos of every section (renderer.py:143)
-  for (int i = lane; i < nm1; i += 64) C[i] = (Sd[i + 1] - Sd[i]) / (Z[i + 1] - Z[i] + 1e-5f);
-  WAVE_SYNC();
-  for (int i = lane; i < nm1; i += 64) {
-    const float z0 = Z[i], z1 = Z[i + 1];
-    const float px0 = ox + dx * z0, py0 = oy + dy * z0, pz0 = oz + dz * z0;
-    const float px1 = ox + dx * z1, py1 = oy + dy * z1, pz1 = oz + dz * z1;
-    const float r0 = sqrtf(px0 * px0 + py0 * py0 + pz0 * pz0), r1 = sqrtf(px1 * px1 + py1 * py1 + pz1 * pz1);
-    const float inside = (r0 < 1.0f || r1 < 1.0f) ? 1.f : 0.f;
-    const float prev = (i == 0) ? 0.f : C[i - 1];
-    float cv = fminf(prev, C[i]);
-    cv = fminf(fmaxf(cv, -1e3f), 0.f) * inside;
-    const float mid = (Sd[i] + Sd[i + 1]) * 0.5f;
-    const float dist = z1 - z0;
-    const float pe = mid - cv * dist * 0.5f, ne = mid + cv * dist * 0.5f;
-    const float pc = sigmoidf_(pe * inv_s), nc = sigmoidf_(ne * inv_s);
-    A[i] = (pc - nc + 1e-5f) / (pc + 1e-5f);
-  }
-  WAVE_SYNC();
-  // transmittance: exclusive cumprod of (1 - alpha + 1e-7)  -> reuse C
-  for (int i = lane; i < nm1; i += 64) C[i] = 1.f - A[i] + 1e-7f;
-  WAVE_SYNC();
-  const int per = (nm1 + 63) / 64;
-  excl_cumprod(C, nm1, per, lane);
-  WAVE_SYNC();
-  // weights + 1e-5, pdf, cdf (sample_pdf, renderer.py:42-45)
-  float loc = 0.f;
-  for (int i = lane; i < nm1; i += 64) { const float wv = A[i] * C[i] + 1e-5f; A[i] = wv; loc += wv; }
-  const float tot = wave_sum(loc);
-  WAVE_SYNC();
-  for (int i = lane; i < nm1; i += 64) A[i] = A[i] / tot;
-  WAVE_SYNC();
-  incl_cumsum(A, nm1, per, lane);
-  WAVE_SYNC();
-  // cdf = [0, A[0..nm1-1]] has n entries; invert at the m deterministic u's (torch.linspace semantics)
-  if (lane < m) {
-    const float start = 0.5f / m, end = 1.f - 0.5f / m;
-    const float step = (m > 1) ? (end - start) / (float)(m - 1) : 0.f;
-    const float u = (lane < m / 2) ? start + step * lane : end - step * (m - 1 - lane);
-    // searchsorted(cdf, u, right=True): number of cdf entries <= u
-    int lo = 0, hi = n;
-    while (lo < hi) {
-      const int midi = (lo + hi) >> 1;
-      const float cv = (midi == 0) ? 0.f : A[midi - 1];
-      if (cv <= u) lo = midi + 1; else hi = midi;
-    }
-    const int below = max(lo - 1, 0), above = min(lo, n - 1);
-    const float cb = (below == 0) ? 0.f : A[below - 1];
-    const float ca = (above == 0) ? 0.f : A[above - 1];
-    float denom = ca - cb;
-    if (denom < 1e-5f) denom = 1.f;
-    const float t = (u - cb) / denom;
-    NZ[lane] = Z[below] + t * (Z[above] - Z[below]);
-  }
-  WAVE_SYNC();
-  // merge (both lists ascending; ties keep the old sample first, like a stable sort of cat([z, new_z]))
-  float* zo = z_out + (long)ray * (n + m);
-  float* so = sdf_out + (long)ray * (n + m);
-  for (int i = lane; i < n; i += 64) {
-    const float zv = Z[i];
-    int lo = 0, hi = m;  // count new < zv
-    while (lo < hi) { const int k = (lo + hi) >> 1; if (NZ[k] < zv) lo = k + 1; else hi = k; }
-    if (active) { zo[i + lo] = zv; so[i + lo] = Sd[i]; }
-  }
-  if (lane < m) {
-    const float zv = NZ[lane];
-    int lo = 0, hi = n;  // count old <= zv
-    while (lo < hi) { const int k = (lo + hi) >> 1; if (Z[k] <= zv) lo = k + 1; else hi = k; }
-    if (active) {
-      zo[lane + lo] = zv;
-      so[lane + lo] = 0.f;
-      z_new[(long)ray * m + lane] = zv;
-      slot_new[(long)ray * m + lane] = lane + lo;
-    }
-  }
-}
-
-// The same step with SEVERAL rays per wavefront: a group of GL lanes per ray (GL = 16 for n + m <= 64, the reference's 64-spp confs:
-// n = 32 .. 56, m = 8 -- four rays per wavefront; GL = 32 for n + m <= 128, the 128-spp conf: two), a lane owns every GL-th sample in
-// the elementwise phases and a contiguous chunk of <= 4 in the scans.  With one ray per wavefront most of a step's ~600 instructions
-// are scan / search / synchronisation overhead executed for 32-56 live lanes (8 in the inversion); a group pays that overhead once for
-// its ray and the wavefront carries four of them (profiles/r04_ab_kernels.txt).
-template <int GL>
-__device__ __forceinline__ float grp_incl_scan_mul(float v, int gl) {
-#pragma unroll
-  for (int d = 1; d < GL; d <<= 1) { const float o = __shfl_up(v, d, GL); if (gl >= d) v *= o; }
-  return v;
-}
-template <int GL>
-__device__ __forceinline__ float grp_incl_scan_add(float v, int gl) {
-#pragma unroll
-  for (int d = 1; d < GL; d <<= 1) { const float o = __shfl_up(v, d, GL); if (gl >= d) v += o; }
-  return v;
-}
-template <int GL>
-__device__ __forceinline__ float grp_sum(float v) {
-#pragma unroll
-  for (int d = GL / 2; d >= 1; d >>= 1) v += __shfl_xor(v, d);
-  return v;
-}
-template <int GL>
-__global__ __launch_bounds__(256) void upsample_grp_kernel(const float* __restrict__ rays_o, const float* __restrict__ rays_d,
                                                          const float* __restrict__ z_in, const float* __restrict__ sdf_in,
                                                          int R, int n, int m, float inv_s, float* __restrict__ z_out,
                                                          float* __restrict__ sdf_out, float* __restrict__ z_new,
                                                          int* __restrict__ slot_new) {
   constexpr int US = 4 * GL, RPBG = 256 / GL;      // samples a group can hold, rays per 256-thread block
-  __shared__ float sz[RPBG][US], ss[RPBG][US], sa[RPBG][US], sc[RPBG][US], sn[RPBG][16];
+  __shared__ float sz[RPBG][US], ss[RPBG][US], sa[RPBG][US], sc[RPBG][US], sn[RPBG][GL == 64 ? 64 : 16];
   const int lane = threadIdx.x & 63, gl = lane & (GL - 1);
   const int slot = (threadIdx.x >> 6) * (64 / GL) + lane / GL;
   // (groups past the last ray redo ray R - 1 without storing)
@@ -221,7 +92,7 @@ __global__ __launch_bounds__(256) void upsample_grp_kernel(const float* __restri
   {
     float loc = 1.f;
     for (int k = 0; k < per; ++k) if (b + k < nm1) loc *= 1.f - A[b + k] + 1e-7f;
-    const float inc = grp_incl_scan_mul<GL>(loc, gl);
+    const float inc = incl_scan_mul<GL>(loc, gl);
     float run = __shfl_up(inc, 1, GL);
     if (gl == 0) run = 1.f;
     for (int k = 0; k < per; ++k)
@@ -231,12 +102,12 @@ __global__ __launch_bounds__(256) void upsample_grp_kernel(const float* __restri
   // weights + 1e-5, pdf, cdf (sample_pdf, renderer.py:42-45)
   float loc = 0.f;
   for (int i = gl; i < nm1; i += GL) { const float wv = A[i] * C[i] + 1e-5f; A[i] = wv; loc += wv; }
-  const float tot = grp_sum<GL>(loc);
+  const float tot = wave_sum<GL>(loc);
   WAVE_SYNC();
   {
     float s = 0.f;
     for (int k = 0; k < per; ++k) if (b + k < nm1) s += A[b + k] / tot;
-    const float inc = grp_incl_scan_add<GL>(s, gl);
+    const float inc = incl_scan_add<GL>(s, gl);
     float run = __shfl_up(inc, 1, GL);
     if (gl == 0) run = 0.f;
     for (int k = 0; k < per; ++k)
@@ -285,8 +156,9 @@ __global__ __launch_bounds__(256) void upsample_grp_kernel(const float* __restri
   }
 }
 
-// lanes_per_ray: 0 = chosen from (n, m) -- 16 lanes per ray for n + m <= 64, 32 for n + m <= 128, a whole wavefront otherwise; 64 = one
-// wavefront per ray for every n (the A/B partner and the cross-check of the tests).  The switch is an argument, not library state.
+// lanes_per_ray: 0 = chosen from (n, m) -- 16 lanes per ray for n + m <= 64, 32 for n + m <= 128, both only for m <= 16, the 64-lane
+// instantiation otherwise; 64 = that instantiation for every n (the A/B partner and the cross-check of the tests).  The switch is an
+// argument, not library state.
 extern "C" int avc_upsample_step_lanes(const float* rays_o, const float* rays_d, const float* z_in, const float* sdf_in,
                                        int R, int n, int m, float inv_s, float* z_out, float* sdf_out, float* z_new,
                                        int* slot_new, int lanes_per_ray, void* stream) {
@@ -295,14 +167,14 @@ extern "C" int avc_upsample_step_lanes(const float* rays_o, const float* rays_d,
   if (R <= 0) return 0;
   const bool grouped = lanes_per_ray == 0 && m <= 16;
   if (grouped && n + m <= 64)
-    hipLaunchKernelGGL(upsample_grp_kernel<16>, dim3((R + 15) / 16), dim3(256), 0, (hipStream_t)stream, rays_o, rays_d, z_in, sdf_in, R, n, m,
+    hipLaunchKernelGGL(upsample_kernel<16>, dim3((R + 15) / 16), dim3(256), 0, (hipStream_t)stream, rays_o, rays_d, z_in, sdf_in, R, n, m,
                        inv_s, z_out, sdf_out, z_new, slot_new);
   else if (grouped && n + m <= 128)
-    hipLaunchKernelGGL(upsample_grp_kernel<32>, dim3((R + 7) / 8), dim3(256), 0, (hipStream_t)stream, rays_o, rays_d, z_in, sdf_in, R, n, m,
+    hipLaunchKernelGGL(upsample_kernel<32>, dim3((R + 7) / 8), dim3(256), 0, (hipStream_t)stream, rays_o, rays_d, z_in, sdf_in, R, n, m,
                        inv_s, z_out, sdf_out, z_new, slot_new);
   else
-    hipLaunchKernelGGL(upsample_kernel, dim3((R + RPB - 1) / RPB), dim3(256), 0, (hipStream_t)stream, rays_o, rays_d, z_in,
-                       sdf_in, R, n, m, inv_s, z_out, sdf_out, z_new, slot_new);
+    hipLaunchKernelGGL(upsample_kernel<64>, dim3((R + 3) / 4), dim3(256), 0, (hipStream_t)stream, rays_o, rays_d, z_in, sdf_in, R, n, m,
+                       inv_s, z_out, sdf_out, z_new, slot_new);
   return avc_check_launch("avc_upsample_step");
 }
 extern "C" int avc_upsample_step(const float* rays_o, const float* rays_d, const float* z_in, const float* sdf_in,
@@ -391,10 +263,7 @@ __global__ __launch_bounds__(256) void composite_fwd_kernel(
   c0 = wave_sum(c0); c1 = wave_sum(c1); c2 = wave_sum(c2);
   x0 = wave_sum(x0); x1 = wave_sum(x1); x2 = wave_sum(x2);
   ws = wave_sum(ws); e_num = wave_sum(e_num); e_den = wave_sum(e_den);
-  if (wstat) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) wm = fmaxf(wm, __shfl_xor(wm, o));
-  }
+  if (wstat) wm = wave_max(wm);
   if (nsum) { n0 = wave_sum(n0); n1 = wave_sum(n1); n2 = wave_sum(n2); }
   if (lane == 0 && active) {
     if (wstat) { wstat[ray] = ws; wstat[(long)R + ray] = wm; }    // planar [2][R]: both rows are the [R,1] tensors render() returns
@@ -562,9 +431,7 @@ __global__ __launch_bounds__(1024) void colsum_kernel(const float* __restrict__ 
     for (int c = 0; c < C; ++c) acc[c] += x[r * C + c];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   for (int c = 0; c < C; ++c) {
-    float v = acc[c];
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
+    const float v = wave_sum(acc[c]);
     if (lane == 0) red[c][wv] = v;
   }
   __syncthreads();

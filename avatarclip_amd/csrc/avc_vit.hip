@@ -1,19 +1,22 @@
-// CLIP ViT-B/32 image-encoder kernels (perceptor.encode_image, main.py:512; OpenAI clip/model.py VisionTransformer).
-//   avc_vit_linear   Y[M,N] = act(X[M,K] W[N,K]^T + b) (+ residual)   -- bf16 MFMA 32x32x16, fp32 accumulate.
-//                    More than 128 rows: the LDS-staged GEMM of avc_vit_gemm.hip.  M = 50..100 tokens: the GEMM is weight-streaming / latency bound, so W is pre-packed in B-operand
-//                    fragment order and X is packed into A-operand fragments by a pre-pass (one coalesced 16-B load per
-//                    lane per k-step for both), the K range is dealt to the 8 wavefronts of a workgroup and reduced
-//                    through LDS, one workgroup per 32 output columns.
-//                    The same kernel computes dX = dY W with the pre-packed W^T (weights are frozen: no dW).
-//   avc_vit_attention_fwd / _bwd   12-head attention over 50 tokens, one workgroup per (image, head), fp32 in LDS.
-#include "avc_common.h"
+// CLIP ViT-B/32 image-encoder kernels (perceptor.encode_image, main.py:512; OpenAI clip/model.py VisionTransformer) and the entry
+// points of the whole tower (the shared device helpers and the other two sources' launchers: avc_vit.h).
+//   avc_vit_linear(_packed, _bwd_gelu)   Y[M,N] = act(X[M,K] W[N,K]^T + b) (+ residual) -- bf16 MFMA 32x32x16, fp32 accumulate; the same
+//                    kernels compute dX = dY W with the pre-packed W^T (weights are frozen: no dW).  Up to 128 rows the GEMM is weight-
+//                    streaming / latency bound: W is pre-packed in B-operand fragment order and X packed into A-operand fragments (one
+//                    coalesced 16-B load per lane per k-step for both), the K range is dealt to the 8 wavefronts of a workgroup and reduced
+//                    through LDS, one workgroup per (32 output columns, 32 rows).  More rows: the LDS-staged GEMM of avc_vit_gemm.hip.
+//   avc_vit_pack, avc_vit_ln_pack, avc_vit_ln_bwd   the packed pipeline's hand-offs: fp32 rows, LayerNorm and its backward straight into
+//                    the packed operand of the next linear.
+//   avc_vit_attention_fwd / _bwd (_packed)   the image tower's attention: one route rule, the matrix-core kernels of avc_vit_attn.hip
+//                    (50 tokens, or 1 .. 256 walked in 32-key tiles).
+//   avc_text_attention_fwd   the text tower's causal attention (<= 128 tokens), fp32 with an online softmax, forward only.
+#include "avc_vit.h"
 #include "../../include/avc.h"
 
 #define VIT_MAX_MT 4   // up to 128 rows (tokens): the latency kernel (one row tile per workgroup); more rows: avc_vit_gemm.hip, groups of 4
 #define VIT_WAVES 8    // wavefronts per workgroup = K-split factor
 
-// X[M,K] fp32 -> bf16 A-operand fragments [m-tile][k-step][lane][8] (lane (i,h) holds X[32m+i][16s+8h+j]): the GEMM then
-// reads its activations with the same coalesced 16-B-per-lane loads as its weights.
+// X[M,K] fp32 -> the packed bf16 operand (avc_vit.h).
 // With `pre` (the pre-activation of a QuickGELU layer, same shape as X) the rows are multiplied by gelu'(pre) on the way: the
 // backward of the activation is folded into the packing pass of the GEMM that follows it (dX = (dY * gelu'(pre)) W).
 __global__ __launch_bounds__(64) void vit_pack_x_kernel(const float* __restrict__ X, const float* __restrict__ pre,
@@ -29,11 +32,7 @@ __global__ __launch_bounds__(64) void vit_pack_x_kernel(const float* __restrict_
       const f4* pp = reinterpret_cast<const f4*>(pre + (long)row * K + 16 * s + 8 * h);
       const f4 pa = pp[0], pb = pp[1];
 #pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const float sa = sigmoidf_(1.702f * pa[j]), sb = sigmoidf_(1.702f * pb[j]);
-        a[j] *= sa + 1.702f * pa[j] * sa * (1.f - sa);
-        b[j] *= sb + 1.702f * pb[j] * sb * (1.f - sb);
-      }
+      for (int j = 0; j < 4; ++j) { a[j] *= quick_gelu_grad(pa[j]); b[j] *= quick_gelu_grad(pb[j]); }
     }
     xf[0] = (__bf16)a[0]; xf[1] = (__bf16)a[1]; xf[2] = (__bf16)a[2]; xf[3] = (__bf16)a[3];
     xf[4] = (__bf16)b[0]; xf[5] = (__bf16)b[1]; xf[6] = (__bf16)b[2]; xf[7] = (__bf16)b[3];
@@ -41,7 +40,7 @@ __global__ __launch_bounds__(64) void vit_pack_x_kernel(const float* __restrict_
 #pragma unroll
     for (int j = 0; j < 8; ++j) xf[j] = (__bf16)0.f;
   }
-  xs[((long)m * KS + s) * 64 + lane] = xf;
+  xs[packed_chunk(m, s, KS, lane)] = xf;
 }
 
 // One workgroup per 32 output columns; the K range is dealt round-robin to 8 wavefronts (k-step s goes to wave s % 8), each
@@ -108,7 +107,7 @@ __global__ __launch_bounds__(64 * VIT_WAVES) void vit_linear_kernel(const b8* __
 #pragma unroll
   for (int q = 0; q < PER_WAVE; ++q) {
     const int item = wv * PER_WAVE + q, m = item >> 4, r = item & 15;
-    const int row = row0 + 32 * m + (r & 3) + 8 * (r >> 2) + 4 * h;
+    const int row = row0 + 32 * m + acc_row(r, h);
     float v = 0.f;
 #pragma unroll
     for (int w = 0; w < VIT_WAVES; ++w) v += red[((w * MT + m) * 16 + r) * 64 + lane];
@@ -117,10 +116,9 @@ __global__ __launch_bounds__(64 * VIT_WAVES) void vit_linear_kernel(const b8* __
       const long o = (long)row * N + col;
       if (act == 1) {
         if (Ypre) Ypre[o] = v;
-        v = v * sigmoidf_(1.702f * v);
+        v = quick_gelu(v);
       } else if (act == 2) {          // backward of a QuickGELU layer: this product is the gradient of its OUTPUT
-        const float p = gpre[o], sg = sigmoidf_(1.702f * p);
-        v *= sg + 1.702f * p * sg * (1.f - sg);
+        v *= quick_gelu_grad(gpre[o]);
       }
       if (res) v += res[o];
       if (Y) Y[o] = v;
@@ -128,17 +126,13 @@ __global__ __launch_bounds__(64 * VIT_WAVES) void vit_linear_kernel(const b8* __
       v = 0.f;
     }
     // the packed pipeline (avc_vit_linear_packed): the result leaves (also) as the packed bf16 operand of the linear
-    // behind it -- element (row, col) is slot col & 7 of lane (row & 31, (col >> 3) & 1) of k-step col >> 4 of row tile row >> 5; the
-    // rows of the last tile past M are written as zeros
-    if (Ys) Ys[((((long)(row >> 5)) * (N >> 4) + (col >> 4)) * 64 + (row & 31) + 32 * ((col >> 3) & 1)) * 8 + (col & 7)] = (__bf16)v;
+    // behind it; the rows of the last tile past M are written as zeros
+    if (Ys) Ys[packed_elem(row, col, N >> 4)] = (__bf16)v;
   }
 }
 
-// batched calls: the LDS-staged GEMM of avc_vit_gemm.hip (128 x 128 blocks; 12.7 ms per encoder pass against 20.3 for the direct-from-L1
-// kernel above, profiles/r03_score_bench.txt), which returns false for the shapes it does not cover
-bool avc_vit_gemm_lds(const void* xs, const void* wp, const float* bias, const float* res, const float* gpre, float* y, float* y_pre,
-                      void* ys, int M, int N, int K, int act, int mt_packed, void* stream);
-
+// (batched calls: the LDS-staged GEMM of avc_vit_gemm.hip -- 128 x 128 blocks; 12.7 ms per encoder pass against 20.3 for the direct-from-L1
+// kernel above, profiles/r03_score_bench.txt)
 extern "C" long avc_vit_workspace_bytes(int M, int K) {
   const long mt = ((M + 127) / 128) * 4;   // whole groups of 4 row tiles (the rows past M are packed as zeros)
   return mt * (K / 16) * 1024L;
@@ -192,6 +186,20 @@ extern "C" int avc_vit_linear_bwd_gelu(const float* dy, const float* pre, const 
 }
 
 // ---- the packed pipeline (clip_vit.BlocksFn): activations stay packed bf16 between the kernels ----
+// a row's LayerNorm statistics (two-pass, fp32): a lane holds the 12 values 4 (lane + 64 c) + 0..3 of the 768
+__device__ __forceinline__ void ln_row_stats(f4 (&v)[3], float eps, float& rstd) {   // on return v = x - mean
+  constexpr int K = 768;
+  float s1 = 0.f;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) s1 += v[c][0] + v[c][1] + v[c][2] + v[c][3];
+  const float mean = wave_sum(s1) * (1.f / K);
+  float s2 = 0.f;
+#pragma unroll
+  for (int c = 0; c < 3; ++c)
+#pragma unroll
+    for (int u = 0; u < 4; ++u) { v[c][u] -= mean; s2 += v[c][u] * v[c][u]; }
+  rstd = rsqrtf(wave_sum(s2) * (1.f / K) + eps);
+}
 // LayerNorm (fp32 statistics, eps inside the square root like torch) of x[M,K] straight into the packed operand of the next linear.
 // One workgroup per 32-row tile: a wavefront normalises 8 rows into an LDS image of the tile, then the fragments go out whole.
 #define LNP_LD (768 + 8)
@@ -209,63 +217,20 @@ __global__ __launch_bounds__(256) void vit_ln_pack_kernel(const float* __restric
   for (int q = 0; q < 8; ++q) {
     const int i = 8 * wv + q, row = 32 * mt + i;
     f4 v[3];
-    float s1 = 0.f;
 #pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      v[c] = row < M ? *reinterpret_cast<const f4*>(X + (long)row * K + 4 * (lane + 64 * c)) : f4{0.f, 0.f, 0.f, 0.f};
-      s1 += v[c][0] + v[c][1] + v[c][2] + v[c][3];
-    }
+    for (int c = 0; c < 3; ++c) v[c] = row < M ? *reinterpret_cast<const f4*>(X + (long)row * K + 4 * (lane + 64 * c)) : f4{0.f, 0.f, 0.f, 0.f};
+    float rstd;
+    ln_row_stats(v, eps, rstd);
 #pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) s1 += __shfl_xor(s1, d);
-    const float mean = s1 * (1.f / K);
-    float s2 = 0.f;
-#pragma unroll
-    for (int c = 0; c < 3; ++c)
-#pragma unroll
-      for (int u = 0; u < 4; ++u) { const float dlt = v[c][u] - mean; s2 += dlt * dlt; }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) s2 += __shfl_xor(s2, d);
-    const float rstd = rsqrtf(s2 * (1.f / K) + eps);
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      typedef __bf16 bf4 __attribute__((ext_vector_type(4)));
-      bf4 o;
-#pragma unroll
-      for (int u = 0; u < 4; ++u) o[u] = (__bf16)((v[c][u] - mean) * rstd * g[c][u] + bt[c][u]);
-      *reinterpret_cast<bf4*>(&tile[i][4 * (lane + 64 * c)]) = o;
-    }
+    for (int c = 0; c < 3; ++c) put4(&tile[i][4 * (lane + 64 * c)], v[c] * rstd * g[c] + bt[c]);
   }
   __syncthreads();
   const int n = lane & 31, h = lane >> 5;
-  for (int s = wv; s < KS; s += 4) xs[((long)mt * KS + s) * 64 + lane] = *reinterpret_cast<const b8*>(&tile[n][16 * s + 8 * h]);
+  for (int s = wv; s < KS; s += 4) xs[packed_chunk(mt, s, KS, lane)] = *reinterpret_cast<const b8*>(&tile[n][16 * s + 8 * h]);
 }
 // Up to 128 rows (the per-iteration calls) the tile kernel above is four workgroups walking 8 rows per wavefront one after the
 // other -- a latency chain.  Here: one wavefront per row, all of a row's loads in flight at once, and no LDS: a lane holds 4
-// consecutive columns of its row = one 8-byte half of a packed 16-byte chunk (column c of row r is slot c & 7 of lane (r & 31,
-// (c >> 3) & 1) of k-step c >> 4 of row tile r >> 5).  Rows past M are not touched (the caller's buffer holds zeros there).
-__device__ __forceinline__ void ln_row_stats(f4 (&v)[3], float eps, float& rstd) {   // on return v = x - mean
-  constexpr int K = 768;
-  float s1 = 0.f;
-#pragma unroll
-  for (int c = 0; c < 3; ++c) s1 += v[c][0] + v[c][1] + v[c][2] + v[c][3];
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) s1 += __shfl_xor(s1, d);
-  const float mean = s1 * (1.f / K);
-  float s2 = 0.f;
-#pragma unroll
-  for (int c = 0; c < 3; ++c)
-#pragma unroll
-    for (int u = 0; u < 4; ++u) { v[c][u] -= mean; s2 += v[c][u] * v[c][u]; }
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) s2 += __shfl_xor(s2, d);
-  rstd = rsqrtf(s2 * (1.f / K) + eps);
-}
-__device__ __forceinline__ void put_packed4(b8* xs, int row, int col, f4 v) {   // 4 consecutive columns from col (col % 4 == 0), K = 768
-  typedef __bf16 bf4 __attribute__((ext_vector_type(4)));
-  bf4 o = {(__bf16)v[0], (__bf16)v[1], (__bf16)v[2], (__bf16)v[3]};
-  char* p = reinterpret_cast<char*>(xs + (((long)(row >> 5)) * 48 + (col >> 4)) * 64 + (row & 31) + 32 * ((col >> 3) & 1)) + 2 * (col & 7);
-  *reinterpret_cast<bf4*>(p) = o;
-}
+// consecutive columns of its row = one 8-byte half of a packed 16-byte chunk.  Rows past M are not touched (the caller's buffer holds zeros there).
 __global__ __launch_bounds__(256) void vit_ln_pack_rows_kernel(const float* __restrict__ X, const float* __restrict__ gamma,
                                                                const float* __restrict__ beta, float eps, b8* __restrict__ xs, int M) {
   constexpr int K = 768;
@@ -285,7 +250,7 @@ __global__ __launch_bounds__(256) void vit_ln_pack_rows_kernel(const float* __re
     f4 o;
 #pragma unroll
     for (int u = 0; u < 4; ++u) o[u] = v[c][u] * rstd * g[c][u] + bt[c][u];
-    put_packed4(xs, row, 4 * (lane + 64 * c), o);
+    put_packed4(xs, K / 16, row, 4 * (lane + 64 * c), o);
   }
 }
 extern "C" int avc_vit_ln_pack(const float* x, const float* gamma, const float* beta, float eps, int M, int K, void* xs_packed,
@@ -345,16 +310,14 @@ __global__ __launch_bounds__(256) void vit_ln_bwd_kernel(const float* __restrict
   for (int c = 0; c < 3; ++c)
 #pragma unroll
     for (int u = 0; u < 4; ++u) { v[c][u] *= rstd; c1 += gy[c][u]; c2 += gy[c][u] * v[c][u]; }
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) { c1 += __shfl_xor(c1, d); c2 += __shfl_xor(c2, d); }
-  c1 *= 1.f / K; c2 *= 1.f / K;
+  c1 = wave_sum(c1) * (1.f / K); c2 = wave_sum(c2) * (1.f / K);
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
     f4 dx;
 #pragma unroll
     for (int u = 0; u < 4; ++u) dx[u] = rstd * (gy[c][u] - c1 - v[c][u] * c2) + rs[c][u];
     *reinterpret_cast<f4*>(dX + (long)row * K + 4 * (lane + 64 * c)) = dx;
-    if (xs) put_packed4(xs, row, 4 * (lane + 64 * c), dx);
+    if (xs) put_packed4(xs, K / 16, row, 4 * (lane + 64 * c), dx);
   }
 }
 extern "C" int avc_vit_ln_bwd(const float* dy, const float* x, const float* gamma, float eps, const float* residual_grad, float* dx,
@@ -370,9 +333,7 @@ extern "C" int avc_vit_ln_bwd(const float* dy, const float* x, const float* gamm
 // attention: qkv [B,T,3*W] (q | k | v, head hd at column hd*64), out [B,T,W].  The image tower's kernels are the matrix-core ones of
 // avc_vit_attn.hip; the fp32 VALU kernels they replaced in round 3 (profiles/r03_ab_kernels.txt) are gone.
 // ---------------------------------------------------------------------------------------------------------
-#define AT_T 50
-#define AT_D 64
-#define AT_LD 65   // +1 padding: thread i reads row i -> conflict-free
+#define TA_LD (ATM_D + 1)   // +1 padding: thread i reads row i -> conflict-free
 
 // Text tower (clip/model.py encode_text: 77 tokens, 8 heads of 64, causal mask): forward only -- prompts are encoded once per
 // run (main.py:273-288).  One workgroup per (sequence, head), thread i = query row i, K/V rows in LDS, online softmax.
@@ -380,57 +341,47 @@ extern "C" int avc_vit_ln_bwd(const float* dy, const float* x, const float* gamm
 __global__ __launch_bounds__(TA_TMAX) void text_attn_fwd_kernel(const float* __restrict__ qkv, float* __restrict__ out, int T,
                                                                 int Wd, int heads, float scale, int causal) {
   extern __shared__ __attribute__((aligned(16))) float tsm[];
-  float (*Ks)[AT_LD] = reinterpret_cast<float (*)[AT_LD]>(tsm);
-  float (*Vs)[AT_LD] = Ks + T;
+  float (*Ks)[TA_LD] = reinterpret_cast<float (*)[TA_LD]>(tsm);
+  float (*Vs)[TA_LD] = Ks + T;
   const int b = blockIdx.x / heads, hd = blockIdx.x % heads;
   const int i = threadIdx.x;
-  const float* base = qkv + (long)b * T * 3 * Wd + hd * AT_D;
-  for (int e = threadIdx.x; e < T * AT_D; e += TA_TMAX) {
-    const int r = e / AT_D, c = e % AT_D;
+  const float* base = qkv + (long)b * T * 3 * Wd + hd * ATM_D;
+  for (int e = threadIdx.x; e < T * ATM_D; e += TA_TMAX) {
+    const int r = e / ATM_D, c = e % ATM_D;
     Ks[r][c] = base[(long)r * 3 * Wd + Wd + c];
     Vs[r][c] = base[(long)r * 3 * Wd + 2 * Wd + c];
   }
   __syncthreads();
   if (i >= T) return;
-  float q[AT_D], o[AT_D];
+  float q[ATM_D], o[ATM_D];
 #pragma unroll
-  for (int c = 0; c < AT_D; ++c) { q[c] = base[(long)i * 3 * Wd + c] * scale; o[c] = 0.f; }
+  for (int c = 0; c < ATM_D; ++c) { q[c] = base[(long)i * 3 * Wd + c] * scale; o[c] = 0.f; }
   float mx = -1e30f, sum = 0.f;
   const int jend = causal ? i + 1 : T;
   for (int j = 0; j < jend; ++j) {
     float sc = 0.f;
 #pragma unroll
-    for (int c = 0; c < AT_D; ++c) sc += q[c] * Ks[j][c];
+    for (int c = 0; c < ATM_D; ++c) sc += q[c] * Ks[j][c];
     const float mn = fmaxf(mx, sc);
     const float corr = __expf(mx - mn), pj = __expf(sc - mn);
     sum = sum * corr + pj;
 #pragma unroll
-    for (int c = 0; c < AT_D; ++c) o[c] = o[c] * corr + pj * Vs[j][c];
+    for (int c = 0; c < ATM_D; ++c) o[c] = o[c] * corr + pj * Vs[j][c];
     mx = mn;
   }
   const float inv = 1.f / sum;
-  float* op = out + ((long)b * T + i) * Wd + hd * AT_D;
+  float* op = out + ((long)b * T + i) * Wd + hd * ATM_D;
 #pragma unroll
-  for (int c = 0; c < AT_D; ++c) op[c] = o[c] * inv;
+  for (int c = 0; c < ATM_D; ++c) op[c] = o[c] * inv;
 }
 
-// matrix-core attention (avc_vit_attn.hip; against the fp32 VALU kernels it replaced: profiles/r03_ab_kernels.txt)
-int avc_attn_fwd_mfma(const float* qkv, float* out, int B, int width, int heads, void* stream);
-int avc_attn_bwd_mfma(const float* qkv, const float* dout, float* dqkv, int B, int width, int heads, void* stream);
-int avc_attn_fwd_mfma_packed(const float* qkv, void* out_packed, int B, int width, int heads, void* stream);
-int avc_attn_bwd_mfma_packed(const float* qkv, const float* dout, void* dqkv_packed, int B, int width, int heads, void* stream);
-// every other T in [1, 256]: the keys walked in 32-key tiles (avc_vit_attn.hip, second half)
-int avc_attn_fwd_tiled(const float* qkv, float* out, int B, int T, int width, int heads, void* stream);
-int avc_attn_bwd_tiled(const float* qkv, const float* dout, float* dqkv, int B, int T, int width, int heads, void* stream);
-int avc_attn_fwd_tiled_packed(const float* qkv, void* out_packed, int B, int T, int width, int heads, void* stream);
-int avc_attn_bwd_tiled_packed(const float* qkv, const float* dout, void* dqkv_packed, int B, int T, int width, int heads, void* stream);
 // one rule for the four entry points: 0 = refused (avc_last_error() says why), 1 = the 50-token kernels, 2 = the tiled ones
 static int vit_attn_route(int T, int width, int heads) {
-  if (T < 1 || T > 256 || heads < 1 || width != heads * AT_D) {
+  if (T < 1 || T > 256 || heads < 1 || width != heads * ATM_D) {
     avc_set_error("avc_vit_attention: 1 <= T <= 256 tokens, head dim 64 (width == heads * 64)");
     return 0;
   }
-  return T == AT_T ? 1 : 2;
+  return T == ATM_T ? 1 : 2;
 }
 extern "C" int avc_vit_attention_bwd_packed(const float* qkv, const float* dout, void* dqkv_packed, int B, int T, int width, int heads,
                                             void* stream) {
@@ -453,12 +404,12 @@ extern "C" int avc_vit_attention_fwd(const float* qkv, float* out, int B, int T,
   return avc_attn_fwd_mfma(qkv, out, B, width, heads, stream);
 }
 extern "C" int avc_text_attention_fwd(const float* qkv, float* out, int B, int T, int width, int heads, int causal, void* stream) {
-  if (T < 1 || T > TA_TMAX || width != heads * AT_D) { avc_set_error("avc_text_attention_fwd: 1 <= T <= 128, head dim 64"); return 1; }
+  if (T < 1 || T > TA_TMAX || width != heads * ATM_D) { avc_set_error("avc_text_attention_fwd: 1 <= T <= 128, head dim 64"); return 1; }
   if (B <= 0) return 0;
-  const size_t lds = 2 * (size_t)T * AT_LD * sizeof(float);
+  const size_t lds = 2 * (size_t)T * TA_LD * sizeof(float);
   static unsigned long long attr_seen = 0;
   if (avc_first_use_on_device(attr_seen)) {
-    hipFuncSetAttribute((const void*)text_attn_fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * TA_TMAX * AT_LD * 4);
+    hipFuncSetAttribute((const void*)text_attn_fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * TA_TMAX * TA_LD * 4);
   }
   hipLaunchKernelGGL(text_attn_fwd_kernel, dim3(B * heads), dim3(TA_TMAX), lds, (hipStream_t)stream, qkv, out, T, width, heads,
                      0.125f, causal);

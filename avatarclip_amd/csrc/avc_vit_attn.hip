@@ -10,12 +10,10 @@
 // and the A operand (V^T, K^T from LDS, stored [d][key]) is read with the same permutation (two 8-byte reads per fragment).
 // The products that contract over the QUERIES (dV = P^T dO, dK = dS^T Q) need P^T / dS^T as A operands, lane = key row: those two
 // tiles go through LDS once ([key][query], bf16).
-#include "avc_common.h"
+#include "avc_vit.h"
 #include "../../include/avc.h"
 
-#define ATM_T 50
-#define ATM_TP 64     // padded tokens
-#define ATM_D 64
+#define ATM_TP 64     // padded tokens (ATM_T, ATM_D: avc_vit.h)
 #define ATM_LD 72     // row stride of the bf16 LDS matrices (144 B: 16-byte aligned rows, 36-bank skew)
 
 typedef __bf16 bf;
@@ -44,12 +42,6 @@ __device__ __forceinline__ b8 frag_perm(const bf (*m)[ATM_LD], int r, int s, int
   v.hi = *reinterpret_cast<const s4v*>(&m[r][k0 + 8]);
   return __builtin_bit_cast(b8, v);
 }
-__device__ __forceinline__ void put4(bf* p, f4 v) {
-  typedef __bf16 bf4 __attribute__((ext_vector_type(4)));
-  bf4 o = {(bf)v[0], (bf)v[1], (bf)v[2], (bf)v[3]};
-  *reinterpret_cast<bf4*>(p) = o;
-}
-__device__ __forceinline__ int acc_row(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
 
 // S^T tiles of query tile `ti` (columns) against both key tiles, then the softmax over the keys: on return p[tj][r] = P[i][j] for
 // query i = 32 ti + (lane & 31), key j = 32 tj + acc_row(r, h)
@@ -91,11 +83,6 @@ __device__ __forceinline__ void acc_to_b(const facc (&a)[2], float scale, b8 (&f
     for (int j = 0; j < 8; ++j) { f[2 * tj][j] = (bf)(a[tj][j] * scale); f[2 * tj + 1][j] = (bf)(a[tj][8 + j] * scale); }
 }
 
-// element (row, col) of a packed bf16 operand with KS k-steps per row tile = slot col & 7 of lane (row & 31, (col >> 3) & 1) of k-step
-// col >> 4 of row tile row >> 5
-__device__ __forceinline__ void put_packed_elem(bf* xs, int KS, long row, int col, float v) {
-  xs[(((row >> 5) * KS + (col >> 4)) * 64 + (row & 31) + 32 * ((col >> 3) & 1)) * 8 + (col & 7)] = (bf)v;
-}
 // PACKED: `out` is the packed bf16 operand of the out-projection ([row tile][k-step][lane (row, half)][8 columns], rows = b * 50 +
 // token) instead of fp32 [B,T,W] -- the batched scoring pipeline (avc_vit_attention_fwd_packed)
 template <bool PACKED>

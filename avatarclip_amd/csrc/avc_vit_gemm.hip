@@ -14,7 +14,7 @@
 // same time, so what pays is MORE, SMALLER workgroups per CU whose epilogues overlap the others' main loops -- not fewer LDS bytes
 // per MFMA: 256 x 256 blocks (one workgroup per CU) 16.8 ms per encoder pass, 256 x 128 (two per CU) 14.9, 128 x 128 (three per CU)
 // 12.7; ring depth / slot size within 3 %.  The direct-from-L1 kernel this replaces: 20.3; the same linears through hipBLASLt: 17.1.
-#include "avc_common.h"
+#include "avc_vit.h"
 #include "../../include/avc.h"
 
 constexpr int G2_TM = 2, G2_TN = 2;   // 32-row MFMA tiles per wavefront (the workgroup is 2 x 2 wavefronts: 128 x 128 outputs)
@@ -120,10 +120,10 @@ __global__ __launch_bounds__(256, OCC) void vit_gemm_lds_kernel(const b8* __rest
     float gp[2][16];
     auto fetch_gp = [&](int t, int p) {
       const int col = 32 * (int)(nt_base + wn * TN + t / TM) + n;
-      const int row0 = 32 * (int)(mt_base + wm * TM + t % TM) + 4 * h;
+      const int row0 = 32 * (int)(mt_base + wm * TM + t % TM) + 4 * h;   // (the lane half's rows start 4 down: acc_row(r, h) = acc_row(r, 0) + 4 h)
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int row = row0 + (r & 3) + 8 * (r >> 2);
+        const int row = row0 + acc_row(r, 0);
         gp[p][r] = gpre[(long)(row < M ? row : M - 1) * N + col];
       }
     };
@@ -144,22 +144,21 @@ __global__ __launch_bounds__(256, OCC) void vit_gemm_lds_kernel(const b8* __rest
         if (GP && tt + 1 < TM * TN) fetch_gp(tt + 1, (tt + 1) & 1);
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int row = row0 + (r & 3) + 8 * (r >> 2);
+          const int row = row0 + acc_row(r, 0);
           float v = acc[i][j][r] + bv;
           if (PRE) { if (row < M) Ypre[(long)row * N + col] = v; }
-          if (ACT) v = v * sigmoidf_(1.702f * v);
+          if (ACT) v = quick_gelu(v);
           if (GP) {
-            const float p = gp[tt & 1][r], sg = sigmoidf_(1.702f * p);
-            v *= sg + 1.702f * p * sg * (1.f - sg);
+            v *= quick_gelu_grad(gp[tt & 1][r]);
             if (row >= M) v = 0.f;
           }
-          T[((r & 3) + 8 * (r >> 2) + 4 * h) * 40 + n] = (__bf16)v;
+          T[acc_row(r, h) * 40 + n] = (__bf16)v;
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 #pragma unroll
         for (int e = 0; e < 2; ++e) {                    // the two k-steps of the next layer this 32-column tile covers
           const b8 f = *reinterpret_cast<const b8*>(&T[n * 40 + 16 * e + 8 * h]);
-          Ys[((mt * KSo) + 2 * nt + e) * 64 + lane] = f;
+          Ys[packed_chunk(mt, 2 * nt + e, KSo, lane)] = f;
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       }
@@ -172,17 +171,17 @@ __global__ __launch_bounds__(256, OCC) void vit_gemm_lds_kernel(const b8* __rest
     const float bv = bias ? bias[col] : 0.f;
 #pragma unroll
     for (int i = 0; i < TM; ++i) {
-      const int row0 = 32 * (int)(mt_base + wm * TM + i) + 4 * h;
-      if (row0 - 4 * h >= M) continue;              // a row tile of padding (wave-uniform)
+      const int row0 = 32 * (int)(mt_base + wm * TM + i);
+      if (row0 >= M) continue;              // a row tile of padding (wave-uniform)
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int row = row0 + (r & 3) + 8 * (r >> 2);
+        const int row = row0 + acc_row(r, h);
         if (row < M) {
           float v = acc[i][j][r] + bv;
           const long o = (long)row * N + col;
           if (ACT) {
             if (PRE) Ypre[o] = v;
-            v = v * sigmoidf_(1.702f * v);
+            v = quick_gelu(v);
           }
           if (RES) v += res[o];
           Y[o] = v;

@@ -360,8 +360,8 @@ class Engine:
         return out
 
     def upsample_step(self, rays_o, rays_d, z, sdf, m, inv_s, lanes=0):
-        """`lanes` = lanes per ray: 0 lets the library group 16 or 32 lanes per ray by n; 64 = one wavefront per ray for every n (the
-        cross-check of the grouped kernels, tests/test_gpu_kernels.py)"""
+        """`lanes` = lanes per ray: 0 lets the library group 16 or 32 lanes per ray by n; 64 = the 64-lane instantiation of the same kernel,
+        one wavefront per ray, for every n (the cross-check of the grouped instantiations, tests/test_gpu_kernels.py)"""
         R, n = z.shape
         z_out = torch.empty(R, n + m, device=self.device, dtype=torch.float32)
         sdf_out = torch.empty(R, n + m, device=self.device, dtype=torch.float32)

@@ -387,7 +387,7 @@ def test_head_fusions_equal_their_torch_statements():
 @gpu
 @pytest.mark.parametrize("n,m", [(32, 8), (56, 8), (47, 5), (64, 16), (112, 16), (120, 8)])
 def test_grouped_upsample_kernel_equals_one_ray_per_wavefront(n, m):
-    """avc_upsample_step with several rays per wavefront (16 or 32 lanes per ray) against the one-wavefront-per-ray kernel (which
+    """avc_upsample_step with several rays per wavefront (16 or 32 lanes per ray) against the 64-lane instantiation of the same kernel (which
     the golden records of the reference pin, test_upsample_steps_match_reference): same algorithm, the scans add / multiply in a
     different order -> new depths equal to ~1e-6 except where the inversion lands on a bin edge; the merge invariants hold exactly."""
     from avatarclip_amd import engine, packing as PK

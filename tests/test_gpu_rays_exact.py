@@ -69,8 +69,8 @@ def _upsample(ro, rd, z, sdf, m, inv_s, lanes):
 @pytest.mark.parametrize("n,m", RR.UP_SHAPES)
 def test_upsample_every_sample_in_cdf_space_and_exact_merge(n, m):
     """n + m = 64 | 65 and 128 | 129 and m = 16 | 17 are the edges of the dispatch (16 / 32 lanes per ray / a wavefront); n - 1 > 128
-    gives the wavefront kernel three and four values per lane in its scans; R = 1, 3, 5 leave wavefronts or lane groups of the last
-    block without a ray; both kernels (lanes = 0: as dispatched, 64: a wavefront per ray) are judged independently."""
+    gives the 64-lane instantiation three and four values per lane in its scans; R = 1, 3, 5 leave wavefronts or lane groups of the last
+    block without a ray; both routes (lanes = 0: as dispatched, 64: the 64-lane instantiation) are judged independently."""
     from oracle import neus_oracle as O
     fig = {0: [0.0, 0.0, None], 64: [0.0, 0.0, None]}
     failed = []
