@@ -7,13 +7,14 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, os.environ.get("AVC_LIB_NAME", "libavc.so"))
-SOURCES = ["avc_core.hip", "avc_mlp_fwd.hip", "avc_mlp_bwd.hip", "avc_wgrad.hip", "avc_rays.hip", "avc_vit.hip", "avc_vit_attn.hip", "avc_vit_gemm.hip", "avc_mcubes.hip", "avc_raster.hip", "avc_raster_grad.hip", "avc_raster_tex.hip", "avc_params.hip", "avc_glue.hip", "avc_drive.hip", "avc_rig.hip", "avc_preview.hip", "avc_smpl.hip", "avc_smpl_grad.hip", "avc_codebook.hip", "avc_preview_clip.hip"]
+SOURCES = ["avc_core.hip", "avc_mlp_fwd.hip", "avc_mlp_bwd.hip", "avc_wgrad.hip", "avc_rays.hip", "avc_vit.hip", "avc_vit_attn.hip", "avc_vit_gemm.hip", "avc_mcubes.hip", "avc_raster.hip", "avc_raster_grad.hip", "avc_raster_tex.hip", "avc_params.hip", "avc_glue.hip", "avc_drive.hip", "avc_rig.hip", "avc_preview.hip", "avc_smpl.hip", "avc_smpl_grad.hip", "avc_codebook.hip", "avc_bake.hip", "avc_preview_clip.hip"]
 ABI_HEADER = os.path.join("..", "..", "include", "avc.h")          # the one declaration of the C ABI (lib.py parses it), relative to CSRC
 TEXTURE_HEADER = "avc_texture.h"                                   # the textured-render entry points (lib.py parses it too), in CSRC: include/ holds avc.h alone
 CODEBOOK_HEADER = "avc_codebook.h"                                 # the k-means entry points (csrc/avc_codebook.hip), declared beside their source as well
 PREVIEW_CLIP_HEADER = "avc_preview_clip.h"                         # the preview's clipping entry points (csrc/avc_preview_clip.hip), declared beside their source
+BAKE_HEADER = "avc_bake.h"                                         # the texture bake's entry points (csrc/avc_bake.hip) and the preview's textured shade, likewise
 HEADERS = ["avc_common.h", "avc_stage.h", "avc_mlp.h", "avc_bwd_body.h", "avc_offsets_gen.h", "avc_raster.h", "avc_raster_grad.h", "avc_smpl.h", "avc_vit.h", ABI_HEADER,
-           TEXTURE_HEADER, CODEBOOK_HEADER, "avc_preview.h", PREVIEW_CLIP_HEADER]
+           TEXTURE_HEADER, CODEBOOK_HEADER, BAKE_HEADER, "avc_preview.h", PREVIEW_CLIP_HEADER]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-comment"]
 
 

@@ -134,10 +134,51 @@ __device__ __forceinline__ float pv_flat_shade(const float* __restrict__ vw, int
   const float nn = sqrtf((nx * nx + ny * ny) + nz * nz) * sqrtf((l[0] * l[0] + l[1] * l[1]) + l[2] * l[2]);
   return nn > 0.f ? ambient + (1.f - ambient) * fminf(fabsf((nx * l[0] + ny * l[1]) + nz * l[2]) / nn, 1.f) : ambient;
 }
-// the colour of pixel (xi, yi), which the untouched face e won: perspective-correct vertex colours times the flat shade
-__device__ __forceinline__ void pv_shade_plain(const PvFace& e, const i4* __restrict__ proj, const float* __restrict__ vw,
-                                               const unsigned char* __restrict__ colors, int csize, const float* __restrict__ l, float ambient,
-                                               float grey, int xi, int yi, float c[3]) {
+// Where a shaded pixel takes its unlit colour from, given the winner's oriented corners and their perspective-correct weights l_i (den =
+// (l0 + l1) + l2): the corners' colours (a mesh without colours: a constant grey), or a texture under the corners' UVs (csrc/avc_bake.h).
+struct PvVertexColours {
+  const unsigned char* __restrict__ colors;
+  int csize;
+  float grey;
+  __device__ __forceinline__ void fetch(const PvFace& e, float l0, float l1, float l2, float den, float col[3]) const {
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) {
+      col[ch] = grey;
+      if (colors)
+        col[ch] = ((l0 * (float)colors[(long)csize * e.i0 + ch] + l1 * (float)colors[(long)csize * e.i1 + ch]) +
+                   l2 * (float)colors[(long)csize * e.i2 + ch]) / den;
+    }
+  }
+};
+struct PvTexture {
+  const float* __restrict__ uv;                // [V,2]
+  const unsigned char* __restrict__ texels;    // [T,T,3]
+  int T;
+  __device__ __forceinline__ void fetch(const PvFace& e, float l0, float l1, float l2, float den, float col[3]) const {
+    const float* a = uv + 2 * (long)e.i0;
+    const float* b = uv + 2 * (long)e.i1;
+    const float* c = uv + 2 * (long)e.i2;
+    const float u = ((l0 * a[0] + l1 * b[0]) + l2 * c[0]) / den, v = ((l0 * a[1] + l1 * b[1]) + l2 * c[1]) / den;
+    const float x = u * (float)T - 0.5f, y = v * (float)T - 0.5f;
+    const float xf = floorf(x), yf = floorf(y);
+    const float fx = x - xf, fy = y - yf;
+    // clamp-to-edge (a NaN goes to texel 0: fminf / fmaxf return the other operand)
+    const int x0 = (int)fminf(fmaxf(xf, 0.f), (float)(T - 1)), x1 = (int)fminf(fmaxf(xf + 1.f, 0.f), (float)(T - 1));
+    const int y0 = (int)fminf(fmaxf(yf, 0.f), (float)(T - 1)), y1 = (int)fminf(fmaxf(yf + 1.f, 0.f), (float)(T - 1));
+    const unsigned char* r0 = texels + 3 * (long)y0 * T;
+    const unsigned char* r1 = texels + 3 * (long)y1 * T;
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) {
+      const float top = (float)r0[3 * x0 + ch] * (1.f - fx) + (float)r0[3 * x1 + ch] * fx;
+      const float bottom = (float)r1[3 * x0 + ch] * (1.f - fx) + (float)r1[3 * x1 + ch] * fx;
+      col[ch] = top * (1.f - fy) + bottom * fy;
+    }
+  }
+};
+// the colour of pixel (xi, yi), which the untouched face e won: the source's perspective-correct colour times the flat shade
+template <typename Src>
+__device__ __forceinline__ void pv_shade_face(const PvFace& e, const i4* __restrict__ proj, const float* __restrict__ vw, const Src& src,
+                                              const float* __restrict__ l, float ambient, int xi, int yi, float c[3]) {
   long long w0, w1, w2;
   pv_weights(e, xi, yi, w0, w1, w2);
   const float l0 = (float)w0 * __uint_as_float((unsigned)proj[e.i0][3]);
@@ -145,14 +186,15 @@ __device__ __forceinline__ void pv_shade_plain(const PvFace& e, const i4* __rest
   const float l2 = (float)w2 * __uint_as_float((unsigned)proj[e.i2][3]);
   const float den = (l0 + l1) + l2;
   const float shade = pv_flat_shade(vw, e.i0, e.i1, e.i2, l, ambient);
+  float col[3];
+  src.fetch(e, l0, l1, l2, den, col);
 #pragma unroll
-  for (int ch = 0; ch < 3; ++ch) {
-    float col = grey;
-    if (colors)
-      col = ((l0 * (float)colors[(long)csize * e.i0 + ch] + l1 * (float)colors[(long)csize * e.i1 + ch]) +
-             l2 * (float)colors[(long)csize * e.i2 + ch]) / den;
-    c[ch] = col * shade;
-  }
+  for (int ch = 0; ch < 3; ++ch) c[ch] = col[ch] * shade;
+}
+__device__ __forceinline__ void pv_shade_plain(const PvFace& e, const i4* __restrict__ proj, const float* __restrict__ vw,
+                                               const unsigned char* __restrict__ colors, int csize, const float* __restrict__ l, float ambient,
+                                               float grey, int xi, int yi, float c[3]) {
+  pv_shade_face(e, proj, vw, PvVertexColours{colors, csize, grey}, l, ambient, xi, yi, c);
 }
 // the box average of an output pixel, rounded to nearest
 __device__ __forceinline__ void pv_store_pixel(unsigned char* __restrict__ image, long at, const float acc[3], int ss) {

@@ -46,6 +46,8 @@
 // 4. avc_skin_blend4: out[t, m] = sum_k weights[m, k] (joint_mats[t, joints[m, k]] (rest[m], 1)), k = 0..3 in this order, fp32.
 #include "avc_preview.h"         // the device functions shared with csrc/avc_preview_clip.hip: set-up, weights, key, the passes' pieces
 #include "../../include/avc.h"
+#include "avc_bake.h"            // avc_preview_shade_tex
+#include <stdio.h>
 
 #pragma clang fp contract(off)   // the projection must be the restatement's operation by operation
 
@@ -153,10 +155,12 @@ extern "C" int avc_preview_raster(const int* proj, int N, int V, const int* tris
 }
 
 // ------------------------------------------------------------------------------------------------------------- shading
+// Src: where the unlit colour comes from (csrc/avc_preview.h: PvVertexColours, PvTexture); everything else is one body
+template <typename Src>
 __global__ __launch_bounds__(PV_THREADS) void pv_shade_kernel(const i4* __restrict__ proj_all, const float* __restrict__ v_all, int V,
-                                                              const int* __restrict__ tris, int F, const unsigned char* __restrict__ colors,
-                                                              int csize, const float* __restrict__ lights, float ambient, float bg0, float bg1,
-                                                              float bg2, float grey, int S, int ss, void* __restrict__ scratch, long stride,
+                                                              const int* __restrict__ tris, int F, const Src src,
+                                                              const float* __restrict__ lights, float ambient, float bg0, float bg1,
+                                                              float bg2, int S, int ss, void* __restrict__ scratch, long stride,
                                                               unsigned char* __restrict__ image, int* __restrict__ face_ids) {
   const int n = blockIdx.y;
   const int p = blockIdx.x * PV_THREADS + threadIdx.x;
@@ -180,7 +184,7 @@ __global__ __launch_bounds__(PV_THREADS) void pv_shade_kernel(const i4* __restri
       PvFace e;
       if (key != PV_EMPTY && (unsigned)f < (unsigned)F && pv_setup(proj, tris, f, V, R, e)) {
         id = f;
-        pv_shade_plain(e, proj, vw, colors, csize, l, ambient, grey, xi, yi, c);
+        pv_shade_face(e, proj, vw, src, l, ambient, xi, yi, c);
       }
       if (face_ids) face_ids[((long)n * R + yi) * R + xi] = id;
 #pragma unroll
@@ -189,29 +193,52 @@ __global__ __launch_bounds__(PV_THREADS) void pv_shade_kernel(const i4* __restri
   pv_store_pixel(image, (long)n * S * S + p, acc, ss);
 }
 
-extern "C" int avc_preview_shade(const int* proj, const float* v, int N, int V, const int* tris, int F, const unsigned char* colors, int csize,
-                                 const float* lights, float ambient, float bg_r, float bg_g, float bg_b, float grey, int S, int ss,
-                                 void* scratch, unsigned char* image, int* face_ids, void* stream) {
-  if (N < 0 || V < 0 || F < 0 || N > 65535 || S <= 0) { avc_set_error("avc_preview_shade: bad sizes (at most 65535 frames a call)"); return 1; }
-  if (ss != 1 && ss != 2) { avc_set_error("avc_preview_shade: ss must be 1 or 2"); return 1; }
-  if ((long)S * ss > AVC_PREVIEW_MAX_RASTER) { avc_set_error("avc_preview_shade: raster size S * ss above 2048"); return 1; }
-  if (colors && csize != 3 && csize != 4) { avc_set_error("avc_preview_shade: colours are 3 or 4 bytes per vertex"); return 1; }
-  if (!(ambient >= 0.f && ambient <= 1.f)) { avc_set_error("avc_preview_shade: ambient outside [0, 1]"); return 1; }
+// the checks, the launch and the scratch's way back to all-ones that both shade entry points share
+template <typename Src>
+static int pv_shade_launch(const char* what, const int* proj, const float* v, int N, int V, const int* tris, int F, const Src& src, const float* lights,
+                           float ambient, float bg_r, float bg_g, float bg_b, int S, int ss, void* scratch, unsigned char* image, int* face_ids,
+                           void* stream) {
+  char msg[160];
+  const char* bad = nullptr;
+  if (N < 0 || V < 0 || F < 0 || N > 65535 || S <= 0) bad = "bad sizes (at most 65535 frames a call)";
+  else if (ss != 1 && ss != 2) bad = "ss must be 1 or 2";
+  else if ((long)S * ss > AVC_PREVIEW_MAX_RASTER) bad = "raster size S * ss above 2048";
+  else if (!(ambient >= 0.f && ambient <= 1.f)) bad = "ambient outside [0, 1]";
+  if (bad) { snprintf(msg, sizeof msg, "%s: %s", what, bad); avc_set_error(msg); return 1; }
   if (N == 0) return 0;
-  if (!scratch || !image || !lights || (F && V && (!proj || !v || !tris))) { avc_set_error("avc_preview_shade: NULL buffer"); return 1; }
-  if (((unsigned long long)proj & 15ull) || ((unsigned long long)scratch & 7ull)) { avc_set_error("avc_preview_shade: proj not 16-byte or scratch not 8-byte aligned"); return 1; }
+  if (!scratch || !image || !lights || (F && V && (!proj || !v || !tris))) bad = "NULL buffer";
+  else if (((unsigned long long)proj & 15ull) || ((unsigned long long)scratch & 7ull)) bad = "proj not 16-byte or scratch not 8-byte aligned";
+  if (bad) { snprintf(msg, sizeof msg, "%s: %s", what, bad); avc_set_error(msg); return 1; }
   const int Fe = V ? F : 0;                                   // no vertices: no face can have won
   const long stride = avc_preview_scratch_bytes(F, S * ss);
-  hipLaunchKernelGGL(pv_shade_kernel, dim3((S * S + PV_THREADS - 1) / PV_THREADS, N), dim3(PV_THREADS), 0, (hipStream_t)stream, (const i4*)proj, v, V,
-                     tris, Fe, colors, csize, lights, ambient, bg_r, bg_g, bg_b, grey, S, ss, scratch,
-                     stride, image, face_ids);
+  hipLaunchKernelGGL(pv_shade_kernel<Src>, dim3((S * S + PV_THREADS - 1) / PV_THREADS, N), dim3(PV_THREADS), 0, (hipStream_t)stream, (const i4*)proj, v, V,
+                     tris, Fe, src, lights, ambient, bg_r, bg_g, bg_b, S, ss, scratch, stride, image, face_ids);
   // the large-face lists (count and entries) back to all-ones: one strided fill over the N frames
   const long R = (long)S * ss;
   if (hipMemset2DAsync((char*)scratch + R * R * 8, (size_t)stride, 0xFF, (size_t)(stride - R * R * 8), (size_t)N, (hipStream_t)stream) != hipSuccess) {
-    avc_set_error("avc_preview_shade: hipMemset2DAsync failed");
+    snprintf(msg, sizeof msg, "%s: hipMemset2DAsync failed", what);
+    avc_set_error(msg);
     return 1;
   }
-  return avc_check_launch("avc_preview_shade");
+  return avc_check_launch(what);
+}
+
+extern "C" int avc_preview_shade(const int* proj, const float* v, int N, int V, const int* tris, int F, const unsigned char* colors, int csize,
+                                 const float* lights, float ambient, float bg_r, float bg_g, float bg_b, float grey, int S, int ss,
+                                 void* scratch, unsigned char* image, int* face_ids, void* stream) {
+  if (colors && csize != 3 && csize != 4) { avc_set_error("avc_preview_shade: colours are 3 or 4 bytes per vertex"); return 1; }
+  return pv_shade_launch("avc_preview_shade", proj, v, N, V, tris, F, PvVertexColours{colors, csize, grey}, lights, ambient, bg_r, bg_g, bg_b, S, ss,
+                         scratch, image, face_ids, stream);
+}
+
+// csrc/avc_bake.h declares it: the same shade with the colour fetched from a texture
+extern "C" int avc_preview_shade_tex(const int* proj, const float* v, int N, int V, const int* tris, int F, const float* uv, const unsigned char* texels,
+                                     int T, const float* lights, float ambient, float bg_r, float bg_g, float bg_b, int S, int ss, void* scratch,
+                                     unsigned char* image, int* face_ids, void* stream) {
+  if (T < 1 || T > 4096) { avc_set_error("avc_preview_shade_tex: texture size outside [1, 4096]"); return 1; }
+  if (!texels || (V && !uv)) { avc_set_error("avc_preview_shade_tex: NULL uv or texels"); return 1; }
+  return pv_shade_launch("avc_preview_shade_tex", proj, v, N, V, tris, F, PvTexture{uv, texels, T}, lights, ambient, bg_r, bg_g, bg_b, S, ss, scratch,
+                         image, face_ids, stream);
 }
 
 // ------------------------------------------------------------------------------------------------------------- four-influence skinning

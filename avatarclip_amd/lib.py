@@ -1,6 +1,6 @@
 """ctypes binding of libavc.so.  include/avc.h declares the C ABI, csrc/avc_texture.h the textured-render entry points and
 csrc/avc_codebook.h the k-means entry points added beside it, csrc/avc_preview_clip.h the preview's clipping entry points: load() parses the
-tuple headers() returns and then added_headers(), merges their prototypes and derives every restype / argtypes from them, and call() checks each tensor against the element type the header gives its parameter.  No
+tuple headers() returns, then added_headers(), then later_headers() (csrc/avc_bake.h: the texture bake and the preview's textured shade), merges their prototypes and derives every restype / argtypes from them, and call() checks each tensor against the element type the header gives its parameter.  No
 fallback: if the library is missing, lacks a symbol the header declares, or a call fails, an exception is raised."""
 import collections
 import ctypes
@@ -20,6 +20,7 @@ CODEBOOK_HEADER = os.path.join(_build.CSRC, _build.CODEBOOK_HEADER)   # the k-me
 
 
 PREVIEW_CLIP_HEADER = os.path.join(_build.CSRC, _build.PREVIEW_CLIP_HEADER)   # the preview's clipping entry points, likewise
+BAKE_HEADER = os.path.join(_build.CSRC, _build.BAKE_HEADER)                   # the texture bake's entry points and the textured shade, likewise
 
 
 def headers():
@@ -33,16 +34,21 @@ def added_headers():
     return (PREVIEW_CLIP_HEADER,)
 
 
+def later_headers():
+    """the headers load() parses last, after added_headers() and under the same rules (read when called)"""
+    return (BAKE_HEADER,)
+
+
 c_int, c_long, c_float, c_double, c_void_p, c_char_p = (ctypes.c_int, ctypes.c_long, ctypes.c_float, ctypes.c_double,
                                                         ctypes.c_void_p, ctypes.c_char_p)
 
 _SCALARS = {"int": c_int, "long": c_long, "float": c_float, "double": c_double}
 _RETURNS = {"int": c_int, "long": c_long, "const char*": c_char_p}
 _INTS = [getattr(torch, n) for n in ("bool", "int8", "uint8", "int16", "uint16", "int32", "uint32", "int64", "uint64") if hasattr(torch, n)]
-_FLOAT32 = frozenset([torch.float32])
+_FLOAT32, _FLOAT64 = frozenset([torch.float32]), frozenset([torch.float64])
 _INT1, _INT4, _INT8 = (frozenset(d for d in _INTS if d.itemsize == n) for n in (1, 4, 8))
 # element type of a pointer parameter -> the tensor dtypes it takes (None: any).  "void*" is the element of the host arrays of pointers.
-_ELEMENTS = {"float": _FLOAT32, "int": _INT4, "unsigned": _INT4, "long": _INT8, "long long": _INT8, "unsigned long long": _INT8,
+_ELEMENTS = {"float": _FLOAT32, "double": _FLOAT64, "int": _INT4, "unsigned": _INT4, "long": _INT8, "long long": _INT8, "unsigned long long": _INT8,
              "void*": _INT8, "signed char": _INT1, "unsigned char": _INT1, "void": None}
 _TYPE_WORDS = {"const", "void", "char", "short", "int", "long", "float", "double", "signed", "unsigned"}
 
@@ -159,7 +165,7 @@ def load():
         raise RuntimeError("libavc.so is not built (run `python -c 'import __graft_entry__ as g; g.build()'`); "
                            "there is no CPU fallback for the HIP hot path")
     protos, declared_in = {}, {}
-    for header in headers() + added_headers():
+    for header in headers() + added_headers() + later_headers():
         with open(header) as f:
             more, abi = parse_header(f.read())
         if header == HEADER:

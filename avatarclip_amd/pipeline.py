@@ -16,7 +16,8 @@
   mesh        Runner(mode="validate_mesh", is_continue).validate_mesh          exp_clip/meshes/*.ply
   motion      animate.AnimateContext, animate.run                              anim/candidate_<i>.npy, anim/motion.npy
   drive       drive.generate_animation                                         drive/<name>_cleaned_apose.ply, drive/motion.pc2
-  rig         rig.build_rig(..., motion=anim/motion.npy)                       rig/<name>.glb, rig/<name>_rig.npz
+  rig         rig.build_rig(..., motion=anim/motion.npy)                       rig/<name>.glb, rig/<name>_rig.npz (--bake_texture SIZE: a baked
+                                                                               base-colour texture, also rig/<name>_texture.png)
   preview     preview.preview, once per kind of result                         preview/{mesh,drive,rig,motion}.gif
 
 Every stage is a call into the module that implements it; none of their arithmetic is restated here.  What this module adds:
@@ -102,6 +103,7 @@ class PipelineSpec:
     mesh_resolution: int = 512
     mcube_threshold: float = 0.0
     voxel_divisor: int = 256
+    bake_texture: int = 0                    # rig: bake the mesh's colours into a texture of this size on the simplified mesh (0: vertex colours)
     preview_size: int = 512
     preview_views: int = 36
     renderer_gradient: bool = False
@@ -438,7 +440,10 @@ def stage_settings(spec, stage):
     if stage == "drive":
         return {"name": s.name}
     if stage == "rig":
-        return {"name": s.name, "voxel_divisor": int(s.voxel_divisor)}
+        out = {"name": s.name, "voxel_divisor": int(s.voxel_divisor)}
+        if int(s.bake_texture):                                 # (only when asked for: manifests from before the option keep their fingerprints)
+            out["bake_texture"] = int(s.bake_texture)
+        return out
     if stage == "preview":
         return {"size": int(s.preview_size), "views": int(s.preview_views)}
     raise ValueError("no stage %r" % (stage,))
@@ -704,8 +709,11 @@ def stage_rig(run):
     from . import rig
     s = run.spec
     glb, npz = rig.build_rig(run.output("mesh", "ply"), s.smpl, s.pose_npy, run.dir("rig"), name=s.name, motion=run.output("motion", "motion"),
-                             voxel_divisor=int(s.voxel_divisor), device=run.device)
-    return {"glb": glb, "npz": npz}
+                             voxel_divisor=int(s.voxel_divisor), device=run.device, bake_texture=int(s.bake_texture))
+    out = {"glb": glb, "npz": npz}
+    if int(s.bake_texture):
+        out["texture"] = os.path.join(run.dir("rig"), "%s_texture.png" % s.name)
+    return out
 
 
 def stage_preview(run):

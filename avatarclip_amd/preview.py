@@ -154,7 +154,8 @@ def scratch_bytes(num_faces, raster_size):
 
 
 def render_frames(vertices, triangles, colors=None, eyes=None, ats=None, up="y", fov=40.0, image_size=512, ss=2, light=None, ambient=0.4,
-                  background=(255, 255, 255), return_face_ids=False, near=None, far=None, chunk_bytes=CHUNK_BYTES, scratch=None, clip=False):
+                  background=(255, 255, 255), return_face_ids=False, near=None, far=None, chunk_bytes=CHUNK_BYTES, scratch=None, clip=False,
+                  texture=None):
     """uint8 [N,S,S,3] device tensor (row 0 = top) of N frames of ONE topology.  vertices [N,V,3] (or [V,3]: the same mesh for every
     camera), triangles [F,3], colors uint8 [V,3|4] or None (a constant grey) -- device tensors or arrays; eyes / ats [N,3] (or [3]);
     light [N,3] or [3] direction, None = a headlight (at - eye).  near / far default to the range of the frames' bounding sphere seen from
@@ -163,7 +164,15 @@ def render_frames(vertices, triangles, colors=None, eyes=None, ats=None, up="y",
     with clip=True they are clipped at the frustum instead (avc_preview_raster_clip / avc_preview_shade_clip) and every other face is
     drawn bit for bit as without it.
     scratch: a uint8 device tensor of at least scratch_bytes(F, S ss) bytes, all 0xFF, to use instead of a fresh one (it comes back all
-    0xFF)."""
+    0xFF).
+    texture = (uv float32 [V,2], image uint8 [T,T,3]) instead of colors: the colour is a bilinear, clamp-to-edge fetch at the
+    perspective-correct UV (avc_preview_shade_tex; a rig --bake_texture .glb).  The clipped path has no textured variant: clip=True with a
+    texture is a ValueError."""
+    if texture is not None and clip:
+        raise ValueError("render_frames: the clipped path has no textured variant yet (csrc/avc_preview_clip.hip interpolates vertex colours "
+                         "only): give clip=True or a texture, not both")
+    if texture is not None and colors is not None:
+        raise ValueError("render_frames: give colors or a texture, not both")
     check_raster(int(image_size), int(ss))
     S, ss = int(image_size), int(ss)
     R = S * ss
@@ -184,6 +193,14 @@ def render_frames(vertices, triangles, colors=None, eyes=None, ats=None, up="y",
         if c.dim() != 2 or c.shape[0] != V or c.shape[1] not in (3, 4) or c.dtype != torch.uint8:
             raise ValueError("colors must be [V, 3] or [V, 4] uint8, got %s %s" % (tuple(c.shape), c.dtype))
         c = c.to(dev).contiguous()
+    uv_d = tex_d = None
+    if texture is not None:
+        uv_d, tex_d = (x if torch.is_tensor(x) else torch.as_tensor(np.asarray(x)) for x in texture)
+        if uv_d.shape != (V, 2) or uv_d.dtype != torch.float32:
+            raise ValueError("texture uv must be float32 [V, 2], got %s %s" % (tuple(uv_d.shape), uv_d.dtype))
+        if tex_d.dim() != 3 or tex_d.shape[0] != tex_d.shape[1] or tex_d.shape[2] != 3 or tex_d.dtype != torch.uint8 or not 1 <= tex_d.shape[0] <= 4096:
+            raise ValueError("texture image must be uint8 [T, T, 3] with T in [1, 4096], got %s %s" % (tuple(tex_d.shape), tex_d.dtype))
+        uv_d, tex_d = uv_d.to(dev).contiguous(), tex_d.to(dev).contiguous()
     if eyes is None or ats is None:
         raise ValueError("render_frames needs eyes and ats (frame_cameras gives both)")
     eyes = np.asarray(eyes.cpu() if torch.is_tensor(eyes) else eyes, np.float64).reshape(-1, 3)
@@ -231,6 +248,11 @@ def render_frames(vertices, triangles, colors=None, eyes=None, ats=None, up="y",
             L.call("avc_preview_shade_clip", proj, vk if V else None, k, V, cams_d[f0:f0 + k], width, near, far, t if F else None, F, c,
                    c.shape[1] if c is not None else 0, lights_d[f0:f0 + k], float(ambient), bg[0], bg[1], bg[2], GREY, S, ss, scratch,
                    images[f0:f0 + k], ids[f0:f0 + k] if ids is not None else None, stream=s)
+            continue
+        if tex_d is not None:
+            L.call("avc_preview_shade_tex", proj, vk if V else None, k, V, t if F else None, F, uv_d if V else None, tex_d, tex_d.shape[0],
+                   lights_d[f0:f0 + k], float(ambient), bg[0], bg[1], bg[2], S, ss, scratch, images[f0:f0 + k],
+                   ids[f0:f0 + k] if ids is not None else None, stream=s)
             continue
         L.call("avc_preview_shade", proj, vk if V else None, k, V, t if F else None, F, c, c.shape[1] if c is not None else 0, lights_d[f0:f0 + k],
                float(ambient), bg[0], bg[1], bg[2], GREY, S, ss, scratch, images[f0:f0 + k], ids[f0:f0 + k] if ids is not None else None, stream=s)
@@ -330,14 +352,17 @@ def mesh_source(ply, pc2=None, every=1):
     return np.ascontiguousarray(frames[::max(1, int(every))], np.float32), t, c, True
 
 
-def glb_source(glb, every=1, device=None):
+def glb_source(glb, every=1, device=None, return_texture=False):
     """(vertices [T,M,3] device tensor, triangles, colors, moving): the skinned mesh of a rig's .glb at the key frames of its track
-    (forward kinematics in torch, the blend by avc_skin_blend4), or at the rest pose"""
+    (forward kinematics in torch, the blend by avc_skin_blend4), or at the rest pose.  return_texture: a fifth item, render_frames'
+    texture = (uv [M,2], image [T,T,3]) of a file with a baked texture, None of one without"""
     g = rig.read_glb(str(glb))
     rest, t, c, joints, weights = glb_skin(g)
     mats, _ = glb_joint_matrices(g, every)
     dev = torch.device(device) if device is not None else torch.device("cuda")
     v = skin_blend4(joints, weights, mats.to(torch.float32).to(dev), torch.from_numpy(rest).to(dev))
+    if return_texture:
+        return v, t, c, bool(g["animation"]), (None if g["image"] is None else (g["uv"], g["image"]))
     return v, t, c, bool(g["animation"])
 
 
@@ -423,10 +448,13 @@ def preview(out, mesh=None, pc2=None, glb=None, views=36, size=512, ss=2, up=Non
         raise ValueError("--out ends in .gif or .png, got %r" % out)
     if up is None:
         up = "z" if pc2 is not None else "y"
+    texture = None
     if mesh is not None:
         v, t, c, moving = mesh_source(mesh, pc2, every)
     elif glb is not None:
-        v, t, c, moving = glb_source(glb, every)
+        v, t, c, moving, texture = glb_source(glb, every, return_texture=True)
+        if texture is not None and clip:
+            raise ValueError("a .glb with a baked texture has no clipped preview yet: leave out --clip, --focus and --eye / --at")
     else:
         v, t, c, moving = smpl_source(smpl, poses, every)
     v = v if torch.is_tensor(v) else torch.from_numpy(v).cuda()
@@ -437,7 +465,8 @@ def preview(out, mesh=None, pc2=None, glb=None, views=36, size=512, ss=2, up=Non
         near = far = None                                     # render_frames' default: the whole mesh's range seen from the eye
     else:
         eyes, ats, near, far = frame_cameras(v, n if (orbit or not moving) else 1, elevation, up, fov, margin, focus=focus)
-    images = render_frames(v, t, c, eyes, ats, up=up, fov=fov, image_size=size, ss=ss, near=near, far=far, clip=clip)
+    images = render_frames(v, t, None if texture is not None else c, eyes, ats, up=up, fov=fov, image_size=size, ss=ss, near=near, far=far, clip=clip,
+                           texture=texture)
     return save_frames(images, out, fps, frames_dir), images
 
 

@@ -2,7 +2,7 @@
 
     python -m avatarclip_amd.rig --mesh X.ply --smpl SMPL.npz|pkl --pose_npy stand_pose.npy --out_dir D
                                  [--name NAME] [--motion motion.npy] [--fps 60] [--voxel_divisor 256] [--no_simplify]
-                                 [--cleanup] [--max_influences K] [--scale 1.0] [--keep_root] [--preview]
+                                 [--cleanup] [--max_influences K] [--scale 1.0] [--keep_root] [--bake_texture SIZE] [--preview]
 
 writes D/<name>.glb (mesh, vertex colours, the 24-joint SMPL skeleton under Mixamo's bone names, the skin, and with --motion one rotation
 track per joint) and D/<name>_rig.npz (the reference's `smpl_object`, export_fbx.py:102-109, under its own keys and shapes, plus `nearest`
@@ -22,7 +22,10 @@ JOINTS_n / WEIGHTS_n sets as the fullest vertex needs, unless --max_influences c
 up) and the tracks carry drive's root rotation (pi/2, 0, 0), which turns the PLAYED avatar into Blender's frame (z up, as drive's .pc2):
 this project's own renderer (avatarclip_amd.preview) shows the rest pose upright with --up y and a played track upright with --up z, so
 a viewer that takes glTF's y-up convention at its word would show the motion lying down unless --keep_root is given.  --preview renders
-the file into D/<name>_preview.gif with the up axis that fits what was written.  No third-party viewer has been tried."""
+the file into D/<name>_preview.gif with the up axis that fits what was written.  No third-party viewer has been tried.
+--bake_texture SIZE (this port's extension, avatarclip_amd/bake.py) separates colour resolution from triangle count: the colours of the
+mesh BEFORE the clustering are baked into a SIZE x SIZE base-colour texture on the mesh after it, and the .glb carries TEXCOORD_0, one
+material and the PNG (also written as D/<name>_texture.png) instead of COLOR_0, with one vertex per triangle corner."""
 import argparse
 import json
 import os
@@ -208,15 +211,51 @@ class _Bin:
         self.accessors.append(acc)
         return len(self.accessors) - 1
 
+    def add_bytes(self, data):
+        """a bufferView of its own without target or accessor (an image): its index"""
+        self.blob += b"\0" * (-len(self.blob) % 4)
+        self.views.append({"buffer": 0, "byteOffset": len(self.blob), "byteLength": len(data)})
+        self.blob += bytes(data)
+        return len(self.views) - 1
+
+
+LINEAR, CLAMP_TO_EDGE = 9729, 33071
+
+
+def encode_png(image):
+    """uint8 [T,T,3] -> the bytes of an RGB PNG (PIL)"""
+    import io
+    from PIL import Image
+    buf = io.BytesIO()
+    Image.fromarray(np.ascontiguousarray(image), "RGB").save(buf, format="PNG")
+    return buf.getvalue()
+
+
+def decode_png(data):
+    """the bytes of a PNG -> uint8 [H,W,C] (PIL); ValueError when they are no PNG"""
+    import io
+    from PIL import Image
+    try:
+        im = Image.open(io.BytesIO(bytes(data)))
+        if im.format != "PNG":
+            raise ValueError("the image is %s, not PNG" % im.format)
+        a = np.asarray(im)
+    except ValueError:
+        raise
+    except Exception as e:
+        raise ValueError("the image does not decode: %s" % e) from None
+    return a if a.ndim == 3 else a[:, :, None]
+
 
 def write_glb(path, positions, triangles, colors, joints, weights, joint_positions, parents=SMPL_PARENTS, names=JOINT_NAMES, times=None,
-              rotations=None, name="avatar"):
+              rotations=None, name="avatar", uv=None, texture=None):
     """One skinned mesh on a joint tree as binary glTF 2.0 (numpy + json + struct).  positions [M,3] float32; triangles [F,3] (uint32
     indices); colors [M,4] uint8 or None (COLOR_0, normalised); joints [S,M,4] uint8 and weights [S,M,4] float32 (JOINTS_n / WEIGHTS_n);
     joint_positions [J,3] in the positions' units; parents [J] (-1: the root).  Joint nodes 0..J-1 carry translation = joint - parent's
     joint (the root its joint) and no rest rotation; node J holds the mesh and is a sibling of the root (fbx_utils.CreateScene);
     inverseBindMatrices = translate(-joint), column-major.  times [T] float32 seconds and rotations [T,J,4] (x, y, z, w): one LINEAR
-    rotation channel per joint."""
+    rotation channel per joint.  uv [M,2] float32 with texture uint8 [T,T,3] (both or neither): TEXCOORD_0 and one material whose
+    pbrMetallicRoughness.baseColorTexture is that image, stored as PNG in a bufferView of its own, sampled LINEAR with CLAMP_TO_EDGE."""
     positions = np.asarray(positions, np.float32)
     triangles = np.asarray(triangles)
     joints, weights = np.asarray(joints), np.asarray(weights, np.float32)
@@ -236,10 +275,20 @@ def write_glb(path, positions, triangles, colors, joints, weights, joint_positio
         raise ValueError("write_glb: one root, every parent before its child")
     if colors is not None and (np.asarray(colors).dtype != np.uint8 or np.asarray(colors).shape != (M, 4)):
         raise ValueError("write_glb: colors must be uint8 [M, 4]")
+    if (uv is None) != (texture is None):
+        raise ValueError("write_glb: uv and texture go together")
+    if uv is not None:
+        uv, texture = np.asarray(uv), np.asarray(texture)
+        if uv.dtype != np.float32 or uv.shape != (M, 2):
+            raise ValueError("write_glb: uv must be float32 [M, 2]")
+        if texture.dtype != np.uint8 or texture.ndim != 3 or texture.shape[0] != texture.shape[1] or texture.shape[2] != 3 or texture.shape[0] == 0:
+            raise ValueError("write_glb: texture must be uint8 [T, T, 3]")
     b = _Bin()
     attributes = {"POSITION": b.add(positions, "VEC3", ARRAY_BUFFER, minmax=True)}
     if colors is not None:
         attributes["COLOR_0"] = b.add(np.asarray(colors), "VEC4", ARRAY_BUFFER, normalized=True)
+    if uv is not None:
+        attributes["TEXCOORD_0"] = b.add(uv, "VEC2", ARRAY_BUFFER)
     for s in range(joints.shape[0]):
         attributes["JOINTS_%d" % s] = b.add(joints[s], "VEC4", ARRAY_BUFFER)
         attributes["WEIGHTS_%d" % s] = b.add(weights[s], "VEC4", ARRAY_BUFFER)
@@ -259,6 +308,12 @@ def write_glb(path, positions, triangles, colors, joints, weights, joint_positio
     doc = {"asset": {"version": "2.0", "generator": "avatarclip_amd.rig"}, "scene": 0, "scenes": [{"nodes": [J, roots[0]]}], "nodes": nodes,
            "meshes": [{"name": str(name), "primitives": [{"attributes": attributes, "indices": indices, "mode": 4}]}],
            "skins": [{"inverseBindMatrices": ibm_acc, "joints": list(range(J)), "skeleton": roots[0]}]}
+    if uv is not None:
+        doc["meshes"][0]["primitives"][0]["material"] = 0
+        doc["materials"] = [{"name": str(name), "pbrMetallicRoughness": {"baseColorTexture": {"index": 0}, "metallicFactor": 0.0, "roughnessFactor": 1.0}}]
+        doc["textures"] = [{"sampler": 0, "source": 0}]
+        doc["samplers"] = [{"magFilter": LINEAR, "minFilter": LINEAR, "wrapS": CLAMP_TO_EDGE, "wrapT": CLAMP_TO_EDGE}]
+        doc["images"] = [{"bufferView": b.add_bytes(encode_png(texture)), "mimeType": "image/png"}]
     if rotations is not None:
         rotations, times = np.asarray(rotations, np.float32), np.asarray(times, np.float32)
         if rotations.ndim != 3 or rotations.shape[1:] != (J, 4) or times.shape != (rotations.shape[0],) or times.shape[0] == 0:
@@ -294,7 +349,8 @@ def read_glb(path):
     as numpy: [count] or [count, components], MAT4 as [count, 4, 4] in FILE order, i.e. column-major), `nodes` (name, children,
     translation and rotation as float64, mesh, skin, parent), `scene_nodes`, `attributes` (name -> array) and `indices` of the one mesh
     primitive, `skin` (joints, skeleton, inverse_bind_matrices [J,4,4] as mathematical matrices), `animation` (a list of node, path,
-    interpolation, times, values)."""
+    interpolation, times, values), `uv` (TEXCOORD_0, float32 [M,2]) and `image` (the base-colour texture decoded, uint8 [T,T,3]) of a
+    textured file, both None otherwise."""
     with open(path, "rb") as f:
         data = f.read()
     _need(len(data) >= 20, "shorter than a header and a chunk header")
@@ -375,6 +431,37 @@ def read_glb(path):
             _need(a["componentType"] == 5126 and a["type"] == "VEC4", "WEIGHTS_n is float32 VEC4")
         if k == "COLOR_0":
             _need(a["componentType"] == 5121 and a["type"] == "VEC4" and a.get("normalized") is True, "COLOR_0 is normalised uint8 VEC4")
+        if k == "TEXCOORD_0":
+            _need(a["componentType"] == 5126 and a["type"] == "VEC2" and not a.get("normalized"), "TEXCOORD_0 is float32 VEC2")
+    out["uv"], out["image"] = out["attributes"].get("TEXCOORD_0"), None
+    materials, textures, samplers, images = (doc.get(k, []) for k in ("materials", "textures", "samplers", "images"))
+    if "material" in prim or materials or textures or samplers or images:
+        _need(len(materials) == 1 and prim.get("material") == 0, "one material, the primitive's")
+        pbr = materials[0].get("pbrMetallicRoughness", {})
+        _need(pbr.get("metallicFactor") == 0 and pbr.get("roughnessFactor") == 1, "the material is metallicFactor 0, roughnessFactor 1")
+        ti = pbr.get("baseColorTexture", {}).get("index")
+        _need(isinstance(ti, int) and 0 <= ti < len(textures) and pbr["baseColorTexture"].get("texCoord", 0) == 0, "baseColorTexture names no texture on TEXCOORD_0")
+        si, ii = textures[ti].get("sampler"), textures[ti].get("source")
+        _need(isinstance(si, int) and 0 <= si < len(samplers), "the texture names no sampler")
+        _need(isinstance(ii, int) and 0 <= ii < len(images), "the texture names no image")
+        sm = samplers[si]
+        _need(sm.get("magFilter") == LINEAR and sm.get("minFilter") == LINEAR and sm.get("wrapS") == CLAMP_TO_EDGE and sm.get("wrapT") == CLAMP_TO_EDGE,
+              "the sampler is LINEAR / LINEAR, CLAMP_TO_EDGE both ways")
+        im = images[ii]
+        _need(im.get("mimeType") == "image/png" and "uri" not in im, "the image is a PNG in the buffer")
+        vi = im.get("bufferView")
+        _need(isinstance(vi, int) and 0 <= vi < len(views) and "target" not in views[vi], "the image names no bufferView without a target")
+        _need(all(a.get("bufferView") != vi for a in doc.get("accessors", [])), "an accessor reads the image's bufferView")
+        o = views[vi].get("byteOffset", 0)
+        try:
+            image = decode_png(blob[o:o + views[vi]["byteLength"]])
+        except ValueError as e:
+            _need(False, str(e))
+        _need(image.dtype == np.uint8 and image.ndim == 3 and image.shape[2] == 3 and image.shape[0] == image.shape[1], "the PNG decodes to uint8 [T, T, 3]")
+        _need(out["uv"] is not None, "a textured primitive without TEXCOORD_0")
+        out["image"] = np.ascontiguousarray(image)
+    else:
+        _need(out["uv"] is None, "TEXCOORD_0 without a material")
     skins = doc.get("skins", [])
     _need(len(skins) <= 1, "at most one skin")
     if skins:
@@ -404,10 +491,17 @@ def colors_to_u8(colors):
 
 # ---------------------------------------------------------------------------------------------------------------- the whole step
 def build_rig(mesh, smpl, pose_npy, out_dir, name="avatar", motion=None, fps=60.0, voxel_divisor=256, simplify=True, cleanup=False,
-              max_influences=0, scale=1.0, keep_root=False, device=None):
+              max_influences=0, scale=1.0, keep_root=False, device=None, bake_texture=0):
     """export_fbx.py:49-109.  mesh: a PLY path (Runner.validate_mesh's) or (vertices, triangles, colors uint8 or None); smpl: a path (.npz /
     official .pkl) or the arrays; pose_npy: stand_pose.npy; motion: None, a .npy path or an array (drive.read_pose_my's layouts).
-    Writes out_dir/<name>.glb and out_dir/<name>_rig.npz; returns both paths."""
+    Writes out_dir/<name>.glb and out_dir/<name>_rig.npz; returns both paths.
+    bake_texture = SIZE > 0 (this port's extension, avatarclip_amd.bake): the colours of the mesh as it is BEFORE the clustering (after
+    cleanup) are baked into a SIZE x SIZE atlas on the mesh as it is after it.  The .glb then holds one vertex per triangle corner
+    (position and skin gathered from the shared vertex), TEXCOORD_0 and the texture instead of COLOR_0; out_dir/<name>_texture.png is the
+    same image, and the .npz gains `uv` [F',3,2] while its other keys stay what they are without the option (shared vertices)."""
+    bake_texture = int(bake_texture)
+    if bake_texture < 0:
+        raise ValueError("bake_texture is a texture size, 0 for none, got %d" % bake_texture)
     device = torch.device(device) if device is not None else torch.device("cuda")
     v, t, c = _mesh.read_ply(str(mesh)) if isinstance(mesh, (str, os.PathLike)) else mesh
     a = smpl_lbs.load_smpl_arrays(smpl, device=str(device)) if isinstance(smpl, (str, os.PathLike)) else \
@@ -416,6 +510,9 @@ def build_rig(mesh, smpl, pose_npy, out_dir, name="avatar", motion=None, fps=60.
         raise ValueError("rig: the model is not on SMPL's 24-joint tree")
     if cleanup:                                               # this port's extension: the largest island only (drive.cleanup_mesh)
         v, t, c = drive.cleanup_mesh(v, t, c)
+    dense = (v, t, c)
+    if bake_texture and c is None:
+        raise ValueError("rig: --bake_texture needs a mesh with colours")
     if simplify:
         v, t, colors = simplify_mesh(v, t, c, voxel_divisor)
         colors = None if colors is None else colors.cpu().numpy()
@@ -424,6 +521,11 @@ def build_rig(mesh, smpl, pose_npy, out_dir, name="avatar", motion=None, fps=60.
         colors = None if c is None else unit_colors(c)
     v = v.cpu().numpy() if torch.is_tensor(v) else np.asarray(v, np.float32)
     triangles = (t.cpu().numpy() if torch.is_tensor(t) else np.asarray(t)).astype(np.int32)
+    uv = image = None
+    if bake_texture:
+        from . import bake as _bake
+        uv, image = _bake.bake_texture(v, triangles, dense[0], dense[1], dense[2], bake_texture)
+    del dense
     rot_vertices = torch.from_numpy(drive.rotate_vertices(v)).to(device)                      # export_fbx.py:56-62
     template, pose_rot = drive.load_template_smpl(a, pose_npy)
     nearest = drive.find_nearest_ind(rot_vertices, template)                                 # :71
@@ -435,13 +537,21 @@ def build_rig(mesh, smpl, pose_npy, out_dir, name="avatar", motion=None, fps=60.
     npz = os.path.join(out_dir, "%s_rig.npz" % name)
     np.savez(npz, vertices=tpose * 100, triangles=triangles, joints=tpose_joints * 100, blend_weights=blend.cpu().numpy(),
              colors=colors if colors is not None else np.zeros((0, 3), np.float32), name=np.array(str(name)), nearest=nearest.cpu().numpy(),
-             parents=np.asarray(SMPL_PARENTS, np.int32))
+             parents=np.asarray(SMPL_PARENTS, np.int32), **({} if uv is None else {"uv": uv}))
     times = quats = None
     if motion is not None:
         rot = motion_rotations(motion, keep_root).to(device)
         quats = rot_to_quat(rot).cpu().numpy()
         times = (np.arange(rot.shape[0], dtype=np.float64) / float(fps)).astype(np.float32)
     glb = os.path.join(out_dir, "%s.glb" % name)
+    if uv is not None:                                        # one vertex per corner: a chart's UVs belong to one triangle alone
+        corner = triangles.reshape(-1).astype(np.int64)
+        with open(os.path.join(out_dir, "%s_texture.png" % name), "wb") as f:
+            f.write(encode_png(image))
+        write_glb(glb, (tpose * np.float32(scale))[corner], np.arange(corner.shape[0], dtype=np.int32).reshape(-1, 3), None,
+                  np.ascontiguousarray(joints_n.cpu().numpy()[:, corner]), np.ascontiguousarray(weights_n.cpu().numpy()[:, corner]),
+                  tpose_joints * np.float32(scale), times=times, rotations=quats, name=name, uv=uv.reshape(-1, 2), texture=image)
+        return glb, npz
     write_glb(glb, tpose * np.float32(scale), triangles, None if colors is None else colors_to_u8(colors), joints_n.cpu().numpy(),
               weights_n.cpu().numpy(), tpose_joints * np.float32(scale), times=times, rotations=quats, name=name)
     return glb, npz
@@ -462,12 +572,14 @@ def main(argv=None):
     ap.add_argument("--max_influences", type=int, default=0, help="keep the K largest weights per vertex and renormalise (0: all)")
     ap.add_argument("--scale", type=float, default=1.0, help="unit of the .glb: 1.0 = metres (glTF's), 100 = the reference's centimetres")
     ap.add_argument("--keep_root", action="store_true", help="keep the motion's own root rotation instead of drive's (pi/2, 0, 0)")
+    ap.add_argument("--bake_texture", type=int, default=0, metavar="SIZE",
+                    help="bake the colours of the mesh before the clustering into a SIZE x SIZE texture on the mesh after it (0: vertex colours)")
     ap.add_argument("--preview", action="store_true", help="also render the .glb into <out_dir>/<name>_preview.gif (avatarclip_amd.preview)")
     args = ap.parse_args(argv)
     name = args.name or os.path.splitext(os.path.basename(args.mesh))[0]
     glb, npz = build_rig(args.mesh, args.smpl, args.pose_npy, args.out_dir, name=name, motion=args.motion, fps=args.fps,
                          voxel_divisor=args.voxel_divisor, simplify=not args.no_simplify, cleanup=args.cleanup,
-                         max_influences=args.max_influences, scale=args.scale, keep_root=args.keep_root)
+                         max_influences=args.max_influences, scale=args.scale, keep_root=args.keep_root, bake_texture=args.bake_texture)
     print(glb)
     print(npz)
     if args.preview:
